@@ -12,7 +12,10 @@ renders its tile into device memory, and the tiles are gathered to rank 0 over R
 (torch.distributed 'nccl') and de-interleaved on device — all inside the timed region.
 The total image is fixed, so this is STRONG scaling.
 
-Prints ONE JSON line on rank 0.  The `roofline` object is the dominant kernel's VALU roofline
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the
+headline figures (`value`, `ms_per_step`, the workload); `--dump-outputs DIR` also writes the last
+timed step's image to DIR/image.npy.  Everything below takes runs of its own and is measured only
+with `--full`.  The `roofline` object is the dominant kernel's VALU roofline
 (the path is neither HBM- nor MFMA-bound): algorithmic FP64 flops per launch (the
 reference's expressions over the kernel's own work counters, uecraytracing_amd/flops.py) over the
 launch duration = the union of the launches' HIP-event spans / launches (they overlap on two
@@ -369,6 +372,24 @@ def rank_tiles(ren, stream, seed0, frame, deal, steps, warmup):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs writes at most this much
+DUMP_SAMPLE_SEED = 404
+
+
+def dump_outputs(directory, image):
+    """--dump-outputs: what the timed path hands its caller, the assembled RGB8 image of the last
+    timed step (rank 0's, uint8[H, W, 3]), as DIR/image.npy in float32 (levels 0..255).  An image
+    over the size limit is written as a fixed, seeded sample of its bytes in image order (the same
+    positions every run), half the limit long."""
+    import numpy as np
+    out = image.cpu().numpy().astype(np.float32)
+    if out.nbytes > DUMP_LIMIT_BYTES:
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        out = out.reshape(-1)[np.sort(rng.choice(out.size, DUMP_LIMIT_BYTES // 8, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "image.npy"), out)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -382,6 +403,12 @@ def parse():
     ap.add_argument("--scene", default="final")
     ap.add_argument("--scene-seed", type=int, default=42)
     ap.add_argument("--seed0", type=int, default=404)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's assembled image (rank 0) to DIR/image.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline (a counting launch), the CPU "
+                         "baseline and parity, the FP32 / xor128 modes, configs 4 and 5 and the per-rank "
+                         "tiles (each has its own --no-... switch)")
     ap.add_argument("--cpu-row-step", type=int, default=45,
                     help="CPU baseline renders every k-th row at full spp")
     ap.add_argument("--cpu-threads", type=int, default=0,
@@ -400,6 +427,8 @@ def parse():
 
 def main():
     args = parse()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     if args.deal is None:
         from uecraytracing_amd.tiles import DEAL
         args.deal = DEAL
@@ -448,12 +477,13 @@ def main():
     # world + camera uploaded to HBM before any timing (the contract: inputs resident when the
     # timed region starts); SURVEY §8(d) counts the upload in the render call, so its cost (host
     # BVH builds + H2D copies, per rank) is timed here and reported beside the step
+    # (the median of three with --full; a plain run uploads once)
     up = []
-    for _ in range(3):
+    for _ in range(3 if args.full else 1):
         t = time.perf_counter()
         ren.set_scene(spheres, cam)
         up.append((time.perf_counter() - t) * 1e3)
-    scene_upload_ms = sorted(up)[1]
+    scene_upload_ms = sorted(up)[len(up) // 2]
     stream = torch.cuda.Stream(device=dev)
     tg = TileGather(rank, world, H, W, dev, deal=args.deal)  # tile, gather buffers and the assembled image
     ev = []
@@ -492,6 +522,54 @@ def main():
     # ms per step after the first (which starts synced): between the ends of steps 1
     # and K on the bench stream (HIP events; e1 of a step fires when its image is complete)
     step_in_flight_ms = (ev[0][1].elapsed_time(ev[-1][1]) / (len(ev) - 1)) if len(ev) > 1 else call_ms
+    total_samples = W * H * spp
+    value = total_samples * args.steps / elapsed / 1e6
+    ms_per_step = elapsed / args.steps * 1e3
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, tg.image)  # the last timed step's image, before any other call
+    head = {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "Msamples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": f"BASELINE config 3: {W}x{H}x{spp}spp, max_depth {depth}, RTIOW final "
+                        f"scene ({len(spheres)} spheres, generator seed {args.scene_seed}), "
+                        f"seed0 {args.seed0}, mt19937 + FP64 bit-exact",
+            "image": f"{W}x{H}", "spp": spp, "max_depth": depth, "spheres": len(spheres),
+            "scene_file": os.path.relpath(scene_file, ROOT) if scene_file else None,
+            "partition": ((f"rows dealt cyclically in bands of {1 << BAND_LOG2}" if BAND_LOG2 else
+                           "single rows dealt cyclically (row r -> rank r mod N)") if args.deal == "rows" else
+                          f"columns dealt cyclically in bands of {1 << COL_BAND_LOG2} (every row)")
+                         + f" over {world} GPU(s), "
+                         + ("RCCL gather to rank 0" if backend == "nccl" else
+                            f"{backend} gather to rank 0 through the host (rehearsal: ranks share a GPU)"),
+        },
+        "ms_per_step_in_flight": round(step_in_flight_ms, 3),
+        "scene_upload_ms": round(scene_upload_ms, 3),
+        "value_incl_scene_upload": round(total_samples * args.steps
+                                         / (elapsed + args.steps * scene_upload_ms * 1e-3) / 1e6, 3),
+    }
+
+    def finish(result):
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        ren.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:
+        # a plain run: the headline figures only; everything below takes runs of its own
+        return finish(head)
+
     tst = ren.stats()  # per-kernel event timings of the last timed step (same stream)
     launches = max(1, tst["launches"])
     # work counters: one more launch of the same workload with the counting instance, after the
@@ -500,9 +578,6 @@ def main():
                      tg.tile.data_ptr(), stream.cuda_stream)
     torch.cuda.synchronize()
     st = ren.stats()
-    total_samples = W * H * spp
-    value = total_samples * args.steps / elapsed / 1e6
-    ms_per_step = elapsed / args.steps * 1e3
 
     # Roofline of the dominant kernel, yk_render_persistent (`launches` launches per step).
     # Launch c + 1 starts on the CUs launch c's draining blocks free (two streams), so spans
@@ -567,35 +642,7 @@ def main():
                            "(64 SQ_ACTIVE_INST_VALU)"}
 
     result = {
-        "metric": METRIC,
-        "value": round(value, 3),
-        "unit": "Msamples/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": f"BASELINE config 3: {W}x{H}x{spp}spp, max_depth {depth}, RTIOW final "
-                        f"scene ({len(spheres)} spheres, generator seed {args.scene_seed}), "
-                        f"seed0 {args.seed0}, mt19937 + FP64 bit-exact",
-            "image": f"{W}x{H}", "spp": spp, "max_depth": depth, "spheres": len(spheres),
-            "scene_file": os.path.relpath(scene_file, ROOT) if scene_file else None,
-            "partition": ((f"rows dealt cyclically in bands of {1 << BAND_LOG2}" if BAND_LOG2 else
-                           "single rows dealt cyclically (row r -> rank r mod N)") if args.deal == "rows" else
-                          f"columns dealt cyclically in bands of {1 << COL_BAND_LOG2} (every row)")
-                         + f" over {world} GPU(s), "
-                         + ("RCCL gather to rank 0" if backend == "nccl" else
-                            f"{backend} gather to rank 0 through the host (rehearsal: ranks share a GPU)"),
-        },
-        "ms_per_step_in_flight": round(step_in_flight_ms, 3),
-        "scene_upload_ms": round(scene_upload_ms, 3),
-        "value_incl_scene_upload": round(total_samples * args.steps
-                                         / (elapsed + args.steps * scene_upload_ms * 1e-3) / 1e6, 3),
+        **head,
         # the path is VALU-bound (FP64 vector arithmetic under divergence), neither
         # HBM- nor MFMA-bound; the HBM view is a sub-object
         "roofline": {
@@ -755,11 +802,7 @@ def main():
         result["tiles"] = rank_tiles(ren, stream, args.seed0, {"ms": ms_per_step, "in_flight_ms": step_in_flight_ms},
                                      args.deal, args.steps, args.warmup)
 
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    ren.close()
-    if world > 1:
-        dist.destroy_process_group()
+    finish(result)
 
 
 if __name__ == "__main__":
