@@ -228,6 +228,67 @@ inline render_options options_from_env() {
   return o;
 }
 
+// A progressive film (ykgpu_film_*, include/ykgpu.h): the resumable accumulation state of one tile
+// on one context.  Any chunking of the samples gives the one-shot render's image.  Destroy it
+// before the renderer whose context it was made on.
+class film {
+ public:
+  film(ykgpu_context* ctx, const yk_render_params& p) {
+    check(ykgpu_film_create(ctx, &p, &f_), "ykgpu_film_create");
+    check(ykgpu_film_params(f_, &p_), "ykgpu_film_params");
+  }
+  ~film() { ykgpu_film_destroy(f_); }
+  film(const film&) = delete;
+  film& operator=(const film&) = delete;
+
+  // the params as the film keeps them (a RANDOM_DEVICE key drawn at create filled in)
+  const yk_render_params& params() const { return p_; }
+  size_t pixels() const { return (size_t)p_.row_count * (p_.col_count ? p_.col_count : p_.image_width); }
+  uint32_t done() const {
+    uint32_t n = 0;
+    check(ykgpu_film_read(f_, nullptr, nullptr, &n), "ykgpu_film_read");
+    return n;
+  }
+  void accumulate(uint32_t n) { check(ykgpu_film_accumulate(f_, n), "ykgpu_film_accumulate"); }
+  std::vector<uint8_t> resolve() {
+    std::vector<uint8_t> img(pixels() * 3);
+    check(ykgpu_film_resolve(f_, img.data()), "ykgpu_film_resolve");
+    return img;
+  }
+  yk_film_stats error_stats(double threshold2) {
+    yk_film_stats st;
+    check(ykgpu_film_error(f_, threshold2, nullptr, &st), "ykgpu_film_error");
+    return st;
+  }
+  // checkpoint: the state with the film's params and the scene's hash (yk_scene_hash)
+  void save(const std::string& path, uint64_t scene_hash) {
+    std::vector<double> s(pixels() * 3), q(pixels() * 3);
+    uint32_t n = 0;
+    check(ykgpu_film_read(f_, s.data(), q.data(), &n), "ykgpu_film_read");
+    if (yk_film_save(path.c_str(), &p_, scene_hash, n, s.data(), q.data()) != YK_OK)
+      throw error(YK_ERR_INVALID, "cannot write the film file " + path);
+  }
+  // resume: refuses a file saved with other params or for another scene
+  void load(const std::string& path, uint64_t scene_hash) {
+    yk_render_params fp;
+    uint64_t h = 0;
+    uint32_t n = 0;
+    if (yk_film_load(path.c_str(), &fp, &h, &n, nullptr, nullptr, 0) != YK_OK)
+      throw error(YK_ERR_INVALID, path + " is not a film file");
+    if (std::memcmp(&fp, &p_, sizeof fp) != 0)
+      throw error(YK_ERR_INVALID, path + " was saved with other render parameters");
+    if (h != scene_hash) throw error(YK_ERR_INVALID, path + " was saved for another scene");
+    std::vector<double> s(pixels() * 3), q(pixels() * 3);
+    if (yk_film_load(path.c_str(), &fp, &h, &n, s.data(), q.data(), pixels()) != YK_OK)
+      throw error(YK_ERR_INVALID, path + " is not a film file");
+    check(ykgpu_film_write(f_, s.data(), q.data(), n), "ykgpu_film_write");
+  }
+
+ private:
+  ykgpu_film* f_ = nullptr;
+  yk_render_params p_{};
+};
+
 // The render loop of source.cpp:122-172 on the GPU: one device context, or — given several
 // devices — a group of contexts over which the image's rows are dealt (tile row t → entry t mod k).
 // Tracing (-l 3) always runs on one context of the first device.
@@ -249,6 +310,14 @@ class renderer {
   renderer& operator=(const renderer&) = delete;
 
   const std::vector<int>& devices() const { return devices_; }
+
+  // the single context (films are made on it); a renderer over several devices has none
+  ykgpu_context* context() const {
+    if (!ctx_ || group_) throw error(YK_ERR_UNSUPPORTED, "a film belongs to one context: not a device group");
+    return ctx_;
+  }
+  // the scene last set (yk_scene_hash of it names the scene a saved film belongs to)
+  uint64_t scene_hash() const { return yk_scene_hash(spheres_.data(), (uint32_t)spheres_.size(), &cam_); }
 
   template <class World, class Cam>
   void set_scene(const World& world, const Cam& cam) {

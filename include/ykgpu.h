@@ -321,6 +321,79 @@ int ykgpu_render_devices(const int* devices, uint32_t n_devices, const yk_sphere
                          uint32_t count, const yk_camera* camera, const yk_render_params* params,
                          uint8_t* rgb_host);
 
+/* ---- progressive film: resumable accumulation with an error map ---------------------------
+ * (Entry points added under ABI 11: nothing that existed changed size or meaning, so a caller
+ * built against the earlier ABI 11 header keeps working; the version number stays.)
+ *
+ * A film is the device-resident accumulation state of one tile of one image: per pixel and
+ * channel the running colour sum s_c (the left fold ((0 + c_0) + c_1) + ... of source.cpp:137-167)
+ * and the running second moment q_c = q_c + (c*c) (product rounded to double, then the sum: no
+ * fused multiply-add), 6 doubles per pixel.  It is filled by any sequence of sample chunks, can be
+ * read at any point and can be saved and restored.
+ *
+ * ykgpu_film_create fixes, from params: the tile (rows, columns, bands), the mode (precision, rng,
+ * seed mode, t_min, max_depth, YK_FLAG_LINEAR_SCAN; the diagnostic flags are dropped) and
+ * samples_per_pixel, the film's TARGET.  The target stays the stride of the counter seed
+ * seed0 + (y*W + x)*spp + s and of the RANDOM_DEVICE index, so sample s of a film is sample s of
+ * the one-shot render with the same params: after any chunking the film's sums, and the image
+ * resolved from them, equal ykgpu_render_sums / ykgpu_render bit for bit.  YK_SEED_RANDOM_DEVICE
+ * with seed_key == 0 draws the key once, at create; every accumulate reports it in
+ * yk_render_stats.seed_key, and ykgpu_film_params returns it.
+ *
+ * Film calls are synchronous.  A film owns its state (sums, second moments, its copy of the
+ * processing order): other renders on its context between its calls, of any size or mode, do not
+ * disturb it, nor it them; several films may share a context.  After ykgpu_set_scene on the
+ * context a film's accumulate returns YK_ERR_INVALID (the scene generation it was created with
+ * has passed).  A film must be destroyed before its context.  Films belong to one context;
+ * a multi-device caller makes one film per tile. */
+typedef struct ykgpu_film ykgpu_film;
+
+typedef struct yk_film_stats { /* 32 bytes */
+  uint64_t pixels;             /* pixels of the tile                                      */
+  uint64_t pixels_over;        /* those with e2 > threshold2                              */
+  double max_e2;               /* the largest e2 of the tile                              */
+  uint32_t samples_done;       /* samples per pixel accumulated so far                    */
+  uint32_t samples_target;     /* params.samples_per_pixel                                */
+} yk_film_stats;
+
+int ykgpu_film_create(ykgpu_context* ctx, const yk_render_params* params, ykgpu_film** out);
+int ykgpu_film_destroy(ykgpu_film* film);
+/* The film's params as it keeps them (diagnostic flags dropped, the drawn seed_key filled in). */
+int ykgpu_film_params(const ykgpu_film* film, yk_render_params* out);
+/* Renders samples [done, done + n_samples) of every pixel and folds them, in sample order, into
+ * the film.  n_samples == 0 or done + n_samples > target: YK_ERR_INVALID, nothing changes.
+ * ykgpu_get_stats on the context then describes this chunk. */
+int ykgpu_film_accumulate(ykgpu_film* film, uint32_t n_samples);
+/* to_color3b (source.cpp:73-83) of the sums with the divisor `done` (/done, math::sqrt, clamp,
+ * *256, truncate) into row_count * Wt * 3 host bytes; legal at any done >= 1. */
+int ykgpu_film_resolve(ykgpu_film* film, uint8_t* rgb_host);
+/* The state: sums and sumsq are row_count * Wt * 3 host doubles each, laid out like
+ * ykgpu_render_sums (either may be NULL), *done the samples accumulated (may be NULL). */
+int ykgpu_film_read(ykgpu_film* film, double* sums, double* sumsq, uint32_t* done);
+/* Restores a state read earlier (checkpoint / resume); done <= target.  The caller vouches that
+ * the state belongs to these params and this scene (yk_film_load returns both to compare). */
+int ykgpu_film_write(ykgpu_film* film, const double* sums, const double* sumsq, uint32_t done);
+/* The error map, done >= 2.  With n = (double)done, per pixel and channel
+ *   v_c = (q_c - (s_c*s_c)/n) / (n*(n-1)),   e2 = max(0, v_r, v_g, v_b)
+ * every operation IEEE double in exactly that order, uncontracted: the squared standard error of
+ * the pixel mean, worst channel (no square root, so e2 > threshold2 is exact).  e2_host (NULL:
+ * not wanted) receives row_count * Wt doubles; stats (NULL: not wanted) the count and the
+ * maximum, which do not depend on the order of the reduction. */
+int ykgpu_film_error(ykgpu_film* film, double threshold2, double* e2_host, yk_film_stats* stats);
+
+/* Film files (host only, no device): a 32-byte header ("ykfilm1\0", the record sizes, done, the
+ * pixel count, scene_hash), the yk_render_params record, then the sums and the second moments as
+ * raw little-endian doubles (they round-trip exactly).  The pixel count is the params' tile,
+ * row_count * Wt.  yk_film_load with sums == NULL and sumsq == NULL reads the header only;
+ * otherwise capacity_pixels must hold the tile.  Truncated or foreign files: YK_ERR_INVALID. */
+int yk_film_save(const char* path, const yk_render_params* params, uint64_t scene_hash, uint32_t done,
+                 const double* sums, const double* sumsq);
+int yk_film_load(const char* path, yk_render_params* params, uint64_t* scene_hash, uint32_t* done,
+                 double* sums, double* sumsq, uint64_t capacity_pixels);
+/* FNV-1a (64 bit) over every field of the spheres (tuple order; `reserved` excluded) and of the
+ * camera, as their bit patterns: the scene a saved film belongs to. */
+uint64_t yk_scene_hash(const yk_sphere* spheres, uint32_t count, const yk_camera* camera);
+
 /* ---- host-side scene helpers (no device needed) ---------------------------------------- */
 
 /* camera<double>{} of camera.hpp:16-27 (16:9, viewport height 2, focal length 1, origin 0). */

@@ -10,11 +10,12 @@ from __future__ import annotations
 
 import ctypes
 import os
+import weakref
 
 import numpy as np
 
 from . import records
-from .records import Camera, RenderParams, RenderStats, Sphere, make_params, sphere_array
+from .records import Camera, FilmStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(PKG_DIR, "lib")
@@ -30,6 +31,9 @@ EXPORTS = (
     "yk_scene_build", "yk_scene_write", "yk_scene_read", "yk_image_height_for",
     "ykgpu_group_create", "ykgpu_group_destroy", "ykgpu_group_size", "ykgpu_group_set_scene",
     "ykgpu_group_render", "ykgpu_group_get_stats", "ykgpu_render_devices",
+    "ykgpu_film_create", "ykgpu_film_destroy", "ykgpu_film_params", "ykgpu_film_accumulate",
+    "ykgpu_film_resolve", "ykgpu_film_read", "ykgpu_film_write", "ykgpu_film_error",
+    "yk_film_save", "yk_film_load", "yk_scene_hash",
 )
 ABI_VERSION = 11
 SCENE_DIR = os.path.join(PKG_DIR, "scenes")  # committed scene files of the BASELINE configs
@@ -91,6 +95,19 @@ def load_library():
         "ykgpu_group_get_stats": ([c.c_void_p, c.c_int, P(RenderStats)], c.c_int),
         "ykgpu_render_devices": ([P(c.c_int), c.c_uint32, P(Sphere), c.c_uint32, P(Camera),
                                   P(RenderParams), c.c_void_p], c.c_int),
+        "ykgpu_film_create": ([c.c_void_p, P(RenderParams), P(c.c_void_p)], c.c_int),
+        "ykgpu_film_destroy": ([c.c_void_p], c.c_int),
+        "ykgpu_film_params": ([c.c_void_p, P(RenderParams)], c.c_int),
+        "ykgpu_film_accumulate": ([c.c_void_p, c.c_uint32], c.c_int),
+        "ykgpu_film_resolve": ([c.c_void_p, c.c_void_p], c.c_int),
+        "ykgpu_film_read": ([c.c_void_p, c.c_void_p, c.c_void_p, P(c.c_uint32)], c.c_int),
+        "ykgpu_film_write": ([c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint32], c.c_int),
+        "ykgpu_film_error": ([c.c_void_p, c.c_double, c.c_void_p, P(FilmStats)], c.c_int),
+        "yk_film_save": ([c.c_char_p, P(RenderParams), c.c_uint64, c.c_uint32, c.c_void_p, c.c_void_p],
+                         c.c_int),
+        "yk_film_load": ([c.c_char_p, P(RenderParams), P(c.c_uint64), P(c.c_uint32), c.c_void_p,
+                          c.c_void_p, c.c_uint64], c.c_int),
+        "yk_scene_hash": ([P(Sphere), c.c_uint32, P(Camera)], c.c_uint64),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
@@ -145,16 +162,169 @@ def read_scene(path: str):
     return arr, cam
 
 
+def scene_hash(spheres, camera: Camera) -> int:
+    """yk_scene_hash: the scene a saved film belongs to (host only)."""
+    arr = spheres if isinstance(spheres, ctypes.Array) else sphere_array(spheres)
+    return load_library().yk_scene_hash(arr, len(arr), ctypes.byref(camera))
+
+
+def save_film(path: str, params: RenderParams, scene: int, done: int, sums, sumsq):
+    """yk_film_save (host only): params, scene hash, done and the raw doubles of a film state."""
+    a = np.ascontiguousarray(sums, dtype=np.float64)
+    b = np.ascontiguousarray(sumsq, dtype=np.float64)
+    n = params.row_count * params.tile_width() * 3
+    if a.size != n or b.size != n:
+        raise YkError("save_film: sums and sumsq must hold row_count * tile width * 3 doubles")
+    rc = load_library().yk_film_save(os.fsencode(path), ctypes.byref(params), scene, done,
+                                     a.ctypes.data, b.ctypes.data)
+    if rc != 0:
+        raise YkError(f"{records.ERRORS.get(rc, rc)}: cannot save the film to {path}")
+
+
+def load_film(path: str):
+    """yk_film_load (host only).  Returns (RenderParams, scene hash, done, sums, sumsq), the arrays
+    float64[row_count, tile width, 3]."""
+    lib = load_library()
+    p, h, done = RenderParams(), ctypes.c_uint64(0), ctypes.c_uint32(0)
+    rc = lib.yk_film_load(os.fsencode(path), ctypes.byref(p), ctypes.byref(h), ctypes.byref(done),
+                          None, None, 0)
+    if rc == 0:
+        shape = (p.row_count, p.tile_width(), 3)
+        sums, sumsq = np.empty(shape, np.float64), np.empty(shape, np.float64)
+        rc = lib.yk_film_load(os.fsencode(path), ctypes.byref(p), ctypes.byref(h), ctypes.byref(done),
+                              sums.ctypes.data, sumsq.ctypes.data, shape[0] * shape[1])
+    if rc != 0:
+        raise YkError(f"{records.ERRORS.get(rc, rc)}: {path} is not a readable film file")
+    return p, h.value, done.value, sums, sumsq
+
+
+class Film:
+    """A progressive film (ykgpu_film, include/ykgpu.h): the resumable accumulation state of one
+    tile.  Made by Renderer.film(params); any chunking of the samples yields the one-shot render's
+    sums and image bit for bit."""
+
+    def __init__(self, renderer: "Renderer", params: RenderParams):
+        self._lib = renderer._lib
+        self._ren = renderer
+        self._f = ctypes.c_void_p()
+        _check(self._lib.ykgpu_film_create(renderer._ctx, ctypes.byref(params), ctypes.byref(self._f)))
+        self.params = RenderParams()
+        _check(self._lib.ykgpu_film_params(self._f, ctypes.byref(self.params)))
+        self._shape = (self.params.row_count, self.params.tile_width())
+        renderer._films.add(self)
+
+    def close(self):
+        if self._f:
+            self._lib.ykgpu_film_destroy(self._f)
+            self._f = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def target(self) -> int:
+        return self.params.samples_per_pixel
+
+    @property
+    def done(self) -> int:
+        n = ctypes.c_uint32(0)
+        _check(self._lib.ykgpu_film_read(self._f, None, None, ctypes.byref(n)))
+        return n.value
+
+    def accumulate(self, n_samples: int) -> int:
+        """Renders samples [done, done + n_samples) into the film; returns the new done."""
+        _check(self._lib.ykgpu_film_accumulate(self._f, n_samples))
+        return self.done
+
+    def resolve(self) -> np.ndarray:
+        """uint8[row_count, tile width, 3]: to_color3b of the sums at the divisor done."""
+        out = np.empty(self._shape + (3,), np.uint8)
+        _check(self._lib.ykgpu_film_resolve(self._f, out.ctypes.data))
+        return out
+
+    def read(self):
+        """(sums, sumsq, done): float64[row_count, tile width, 3] each."""
+        sums, sumsq = np.empty(self._shape + (3,), np.float64), np.empty(self._shape + (3,), np.float64)
+        n = ctypes.c_uint32(0)
+        _check(self._lib.ykgpu_film_read(self._f, sums.ctypes.data, sumsq.ctypes.data, ctypes.byref(n)))
+        return sums, sumsq, n.value
+
+    def write(self, sums, sumsq, done: int):
+        """Restores a state read earlier."""
+        a = np.ascontiguousarray(sums, dtype=np.float64)
+        b = np.ascontiguousarray(sumsq, dtype=np.float64)
+        if a.shape != self._shape + (3,) or b.shape != self._shape + (3,):
+            raise YkError(f"Film.write: sums and sumsq must have shape {self._shape + (3,)}")
+        _check(self._lib.ykgpu_film_write(self._f, a.ctypes.data, b.ctypes.data, done))
+
+    def error(self, threshold2: float = 0.0, want_map: bool = True):
+        """(e2 float64[row_count, tile width] | None, stats dict): the squared standard error of
+        each pixel's mean, worst channel, and the pixels with e2 > threshold2."""
+        e2 = np.empty(self._shape, np.float64) if want_map else None
+        st = FilmStats()
+        _check(self._lib.ykgpu_film_error(self._f, threshold2, e2.ctypes.data if want_map else None,
+                                          ctypes.byref(st)))
+        return e2, st.as_dict()
+
+    def render_until(self, threshold: float, chunk: int) -> dict:
+        """Accumulates `chunk` samples at a time until no pixel's standard error exceeds
+        `threshold` (e2 <= threshold**2 everywhere) or the target is reached; returns the stats
+        of the last error map."""
+        if chunk < 1:
+            raise YkError("render_until: chunk must be >= 1")
+        while True:
+            done = self.done
+            if done >= 2:
+                _, st = self.error(threshold * threshold, want_map=False)
+                if st["pixels_over"] == 0 or done >= self.target:
+                    return st
+            elif done >= self.target:  # a target of one sample has no error estimate
+                return FilmStats(self._shape[0] * self._shape[1], 0, 0.0, done, self.target).as_dict()
+            self.accumulate(min(chunk, self.target - done))
+
+    def save(self, path: str, scene: int):
+        """Checkpoint: the film's params, `scene` (scene_hash of the scene it renders) and state."""
+        sums, sumsq, done = self.read()
+        save_film(path, self.params, scene, done, sums, sumsq)
+
+    def load(self, path: str, scene: int) -> int:
+        """Resume: restores the state saved in `path`; refuses a file whose params or scene hash
+        differ from the film's.  Returns done."""
+        p, h, done, sums, sumsq = load_film(path)
+        if bytes(p) != bytes(self.params):
+            raise YkError(f"{path} was saved with other render params than this film's")
+        if h != scene:
+            raise YkError(f"{path} was saved for another scene")
+        self.write(sums, sumsq, done)
+        return done
+
+
 class Renderer:
     """One device context (ykgpu_context): owns the scene in HBM, scratch and a stream."""
 
     def __init__(self, device: int = 0):
         self._lib = load_library()
         self._ctx = ctypes.c_void_p()
+        self._films = weakref.WeakSet()
         _check(self._lib.ykgpu_context_create(device, ctypes.byref(self._ctx)))
         self.device = device
 
+    def film(self, params: RenderParams) -> Film:
+        """A progressive film of the tile `params` names (include/ykgpu.h)."""
+        return Film(self, params)
+
     def close(self):
+        for f in list(self._films):  # films go before their context
+            f.close()
         if self._ctx:
             self._lib.ykgpu_context_destroy(self._ctx)
             self._ctx = ctypes.c_void_p()
@@ -299,5 +469,5 @@ def render_devices(devices, spheres, camera: Camera, params: RenderParams) -> np
     return out
 
 
-__all__ = ["Renderer", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
+__all__ = ["Renderer", "Film", "scene_hash", "save_film", "load_film", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
            "make_params", "load_library", "records", "EXPORTS", "LIB_PATH", "CLI_PATH"]

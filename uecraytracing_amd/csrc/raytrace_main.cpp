@@ -18,7 +18,9 @@
 //
 // Added (render parameters are compile-time macros in the reference): --width, --spp,
 // --depth, --scene, --scene-seed, --scene-file, --save-scene, --seed0, --precision, --rng,
-// --device, --stats.  --seed0 fixes the per-sample seed base (seed0 + (y*W+x)*spp + s, the constexpr
+// --device, --stats, and the progressive film's --progressive, --until, --checkpoint, --stop-after
+// (include/ykgpu.h "progressive film": the image in chunks of samples, the same bytes as in one
+// call).  --seed0 fixes the per-sample seed base (seed0 + (y*W+x)*spp + s, the constexpr
 // build's formula, source.cpp:154-158); without it every sample gets its own seed from a
 // per-call std::random_device key (YK_SEED_RANDOM_DEVICE), like the reference's runtime build
 // (source.cpp:159).  --precision fp32 renders render<float> (T = float, source.cpp:98);
@@ -78,7 +80,14 @@ const char* kHelp =
     "      --precision arg       fp64|fp32: the T of render<T> (default: fp64)\n"
     "      --rng arg             mt19937|xor128: the per-sample engine (default: mt19937)\n"
     "      --device arg          GPU index (default: 0)\n"
-    "      --stats               print kernel time and throughput\n";
+    "      --stats               print kernel time and throughput\n"
+    "      --progressive arg     render in chunks of arg samples per pixel, rewriting the image\n"
+    "                            after each chunk (the same image as in one call)\n"
+    "      --until arg           stop once no pixel's standard error exceeds arg; prints the\n"
+    "                            samples used (chunks of --progressive, default 16)\n"
+    "      --checkpoint arg      save the film to this file after every chunk; resume from it\n"
+    "                            when it exists (same parameters and scene, else an error)\n"
+    "      --stop-after arg      render at most arg chunks in this run (resume with --checkpoint)\n";
 
 struct args {
   bool help = false, verbose_flag = false, stats = false;
@@ -93,6 +102,12 @@ struct args {
   std::string rng = "mt19937";
   std::string scene = "ref4";
   std::string scene_file, save_scene;
+  // the progressive film
+  bool have_progressive = false, have_until = false, have_stop_after = false;
+  uint32_t progressive = 0, stop_after = 0;
+  double until = 0;
+  std::string checkpoint;
+  bool film() const { return have_progressive || have_until || have_stop_after || !checkpoint.empty(); }
 };
 
 uint32_t to_u32(const std::string& opt, const std::string& v) {
@@ -101,6 +116,20 @@ uint32_t to_u32(const std::string& opt, const std::string& v) {
   if (v.empty() || *end || x > 0xffffffffull || v[0] == '-')
     throw option_error{"Argument '" + v + "' failed to parse (option " + opt + ")"};
   return (uint32_t)x;
+}
+
+double to_error_bound(const std::string& opt, const std::string& v) {
+  char* end = nullptr;
+  const double x = std::strtod(v.c_str(), &end);
+  if (v.empty() || *end || !(x >= 0) || !std::isfinite(x))
+    throw option_error{"Argument '" + v + "' failed to parse (option " + opt + ")"};
+  return x;
+}
+
+uint32_t to_count(const std::string& opt, const std::string& v) {
+  const uint32_t x = to_u32(opt, v);
+  if (!x) throw option_error{"Argument '" + v + "' must be at least 1 (option " + opt + ")"};
+  return x;
 }
 
 args parse(int argc, char** argv) {
@@ -144,6 +173,13 @@ args parse(int argc, char** argv) {
       else if (n == "seed0") { a.seed0 = to_u32(n, value(i, n, inl)); a.have_seed0 = true; }
       else if (n == "precision") a.precision = value(i, n, inl);
       else if (n == "rng") a.rng = value(i, n, inl);
+      else if (n == "progressive") { a.progressive = to_count(n, value(i, n, inl)); a.have_progressive = true; }
+      else if (n == "until") { a.until = to_error_bound(n, value(i, n, inl)); a.have_until = true; }
+      else if (n == "stop-after") { a.stop_after = to_count(n, value(i, n, inl)); a.have_stop_after = true; }
+      else if (n == "checkpoint") {
+        a.checkpoint = value(i, n, inl);
+        if (a.checkpoint.empty()) throw option_error{"Option 'checkpoint' needs a file name"};
+      }
       else throw option_error{"Option '" + n + "' does not exist"};
     } else if (s.size() > 1 && s[0] == '-') {
       for (size_t k = 1; k < s.size(); ++k) {
@@ -249,8 +285,61 @@ int main(int argc, char* argv[]) {
       if (!a.save_scene.empty()) yk_scene_write(a.save_scene.c_str(), s.data(), n, &cam);
     }
     std::cout << "rendering..." << std::endl;
-    image = gpu.render(W, H, a.spp, a.depth, seed0, ro);
-    const yk_render_stats st = gpu.stats();
+    yk_render_stats st{};
+    if (!a.film()) {
+      image = gpu.render(W, H, a.spp, a.depth, seed0, ro);
+      st = gpu.stats();
+    } else {
+      // The progressive film: the image in chunks of samples.  Sample s of the film is sample s of
+      // the one-shot render, so every way through here ends in the bytes the branch above renders.
+      if (!a.spp) throw ykgpu::error(YK_ERR_INVALID, "--spp must be at least 1");
+      yk_render_params p = ykgpu::renderer::params(W, H, a.spp, a.depth, seed0, ro);
+      const uint64_t scene = gpu.scene_hash();
+      bool resume = false;
+      if (!a.checkpoint.empty()) {
+        yk_render_params fp;
+        if (FILE* f = std::fopen(a.checkpoint.c_str(), "rb")) {
+          std::fclose(f);
+          resume = true;
+          // a run seeded from random_device continues with the key its checkpoint holds
+          if (yk_film_load(a.checkpoint.c_str(), &fp, nullptr, nullptr, nullptr, nullptr, 0) == YK_OK &&
+              p.seed_mode == YK_SEED_RANDOM_DEVICE && fp.seed_mode == YK_SEED_RANDOM_DEVICE)
+            p.seed_key = fp.seed_key;
+        }
+      }
+      ykgpu::film film(gpu.context(), p);
+      if (resume) {
+        try {
+          film.load(a.checkpoint, scene);
+        } catch (const ykgpu::error& e) {
+          std::cerr << "raytrace: cannot resume: " << e.what() << std::endl;
+          return EXIT_FAILURE;
+        }
+      }
+      const uint32_t chunk = a.have_progressive ? a.progressive : a.have_until ? 16u : a.spp;
+      const double threshold2 = a.until * a.until;
+      auto converged = [&]() { return a.have_until && film.done() >= 2 && film.error_stats(threshold2).pixels_over == 0; };
+      uint32_t chunks = 0;
+      bool stop = converged();
+      while (!stop && film.done() < a.spp && !(a.have_stop_after && chunks >= a.stop_after)) {
+        film.accumulate(std::min(chunk, a.spp - film.done()));
+        ++chunks;
+        const yk_render_stats cs = gpu.stats();
+        st.kernel_ms += cs.kernel_ms;
+        st.samples += cs.samples;
+        st.seed_key = cs.seed_key;
+        if (!a.checkpoint.empty()) film.save(a.checkpoint, scene);
+        stop = converged();
+        // the image so far, for whoever watches the file (the last chunk's is written below)
+        if (!stop && film.done() < a.spp) ykpng::write_rgb(a.output.c_str(), W, H, film.resolve().data());
+      }
+      if (film.done() == 0) throw ykgpu::error(YK_ERR_INVALID, "nothing rendered");
+      image = film.resolve();
+      st.seed_key = film.params().seed_key;
+      if (a.have_until) std::cout << "samples used : " << film.done() << std::endl;
+      if (film.done() < a.spp && !stop)
+        std::cout << "stopped at " << film.done() << " of " << a.spp << " samples" << std::endl;
+    }
     if (verbose) {
       ykgpu::render_options vo = ro;
       vo.seed_key = st.seed_key;  // level 3 traces the same samples the image summed

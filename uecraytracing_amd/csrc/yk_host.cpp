@@ -299,3 +299,106 @@ int yk_scene_read(const char* path, yk_sphere* spheres, uint32_t capacity, uint3
   return YK_OK;
 }
 
+
+// ---- film files (include/ykgpu.h "progressive film") -----------------------------------------
+// Binary, little-endian (the only byte order the library is built for): FilmHeader, the
+// yk_render_params record, pixels * 3 sums, pixels * 3 second moments.  The doubles are written
+// as they lie in memory, so every bit pattern round-trips.
+namespace {
+struct FilmHeader {  // 32 bytes
+  char magic[8];     // "ykfilm1\0"
+  uint32_t params_bytes, done;
+  uint64_t pixels, scene_hash;
+};
+static_assert(sizeof(FilmHeader) == 32, "film header layout");
+const char kFilmMagic[8] = {'y', 'k', 'f', 'i', 'l', 'm', '1', '\0'};
+
+uint64_t film_pixels(const yk_render_params* p) {
+  return (uint64_t)p->row_count * (p->col_count ? p->col_count : p->image_width);
+}
+
+uint64_t fnv1a(uint64_t h, const void* data, size_t n) {
+  const unsigned char* b = (const unsigned char*)data;
+  for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 0x100000001b3ull;
+  return h;
+}
+}  // namespace
+
+uint64_t yk_scene_hash(const yk_sphere* spheres, uint32_t count, const yk_camera* camera) {
+  uint64_t h = 0xcbf29ce484222325ull;
+  h = fnv1a(h, &count, sizeof count);
+  for (uint32_t i = 0; spheres && i < count; ++i) {
+    const yk_sphere& s = spheres[i];
+    h = fnv1a(h, s.center, sizeof s.center);
+    h = fnv1a(h, &s.radius, sizeof s.radius);
+    h = fnv1a(h, s.albedo, sizeof s.albedo);
+    h = fnv1a(h, &s.fuzz, sizeof s.fuzz);
+    h = fnv1a(h, &s.ior, sizeof s.ior);
+    h = fnv1a(h, &s.material, sizeof s.material);
+  }
+  if (camera) {
+    const double* cv[6] = {camera->origin, camera->lower_left_corner, camera->horizontal,
+                           camera->vertical, camera->lens_u, camera->lens_v};
+    for (const double* v : cv) h = fnv1a(h, v, 3 * sizeof(double));
+    h = fnv1a(h, &camera->lens_radius, sizeof(double));
+  }
+  return h;
+}
+
+int yk_film_save(const char* path, const yk_render_params* params, uint64_t scene_hash, uint32_t done,
+                 const double* sums, const double* sumsq) {
+  if (!path || !params || !sums || !sumsq) return YK_ERR_INVALID;
+  const uint64_t pixels = film_pixels(params);
+  if (!pixels || done > params->samples_per_pixel) return YK_ERR_INVALID;
+  // written beside the target and renamed over it: an interrupted save leaves the previous
+  // checkpoint whole
+  const std::string tmp = std::string(path) + ".part";
+  FILE* f = std::fopen(tmp.c_str(), "wb");
+  if (!f) return YK_ERR_INVALID;
+  FilmHeader h;
+  std::memcpy(h.magic, kFilmMagic, sizeof h.magic);
+  h.params_bytes = (uint32_t)sizeof(yk_render_params);
+  h.done = done;
+  h.pixels = pixels;
+  h.scene_hash = scene_hash;
+  const size_t n = (size_t)pixels * 3;
+  bool ok = std::fwrite(&h, sizeof h, 1, f) == 1 && std::fwrite(params, sizeof *params, 1, f) == 1 &&
+            std::fwrite(sums, sizeof(double), n, f) == n && std::fwrite(sumsq, sizeof(double), n, f) == n;
+  ok = std::fclose(f) == 0 && ok;
+  if (ok) ok = std::rename(tmp.c_str(), path) == 0;
+  if (!ok) std::remove(tmp.c_str());
+  return ok ? YK_OK : YK_ERR_INVALID;
+}
+
+int yk_film_load(const char* path, yk_render_params* params, uint64_t* scene_hash, uint32_t* done,
+                 double* sums, double* sumsq, uint64_t capacity_pixels) {
+  if (!path) return YK_ERR_INVALID;
+  FILE* f = std::fopen(path, "rb");
+  if (!f) return YK_ERR_INVALID;
+  FilmHeader h;
+  yk_render_params p;
+  bool ok = std::fread(&h, sizeof h, 1, f) == 1 && std::memcmp(h.magic, kFilmMagic, sizeof h.magic) == 0 &&
+            h.params_bytes == sizeof(yk_render_params) && std::fread(&p, sizeof p, 1, f) == 1;
+  ok = ok && h.pixels != 0 && h.pixels == film_pixels(&p) && h.pixels < (1ull << 31) &&
+       h.done <= p.samples_per_pixel;
+  // the whole payload must be there, and nothing after it, whether or not it is read
+  if (ok) {
+    const long at = std::ftell(f);
+    ok = at >= 0 && std::fseek(f, 0, SEEK_END) == 0 &&
+         (uint64_t)std::ftell(f) == (uint64_t)at + h.pixels * 6 * sizeof(double) && std::fseek(f, at, SEEK_SET) == 0;
+  }
+  if (ok && (sums || sumsq)) {
+    const size_t n = (size_t)h.pixels * 3;
+    ok = capacity_pixels >= h.pixels;
+    std::vector<double> skip;
+    if (ok && !(sums && sumsq)) skip.resize(n);
+    ok = ok && std::fread(sums ? sums : skip.data(), sizeof(double), n, f) == n &&
+         std::fread(sumsq ? sumsq : skip.data(), sizeof(double), n, f) == n;
+  }
+  std::fclose(f);
+  if (!ok) return YK_ERR_INVALID;
+  if (params) *params = p;
+  if (scene_hash) *scene_hash = h.scene_hash;
+  if (done) *done = h.done;
+  return YK_OK;
+}

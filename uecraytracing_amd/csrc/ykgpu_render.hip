@@ -870,6 +870,122 @@ __global__ __launch_bounds__(256) void yk_reduce_samples(ReduceArgs ra) {
     reduce_slot(ra, p);
 }
 
+// ---- progressive film (include/ykgpu.h) ------------------------------------------------------
+// A film keeps, per processing slot p and channel c, the running sum s and the running second
+// moment q as six planes plane[c * npix_slots + p] (s: c = 0..2, q: c = 3..5) — slot order, the
+// order the launches' colours arrive in, so every access of the fold below is coalesced like
+// yk_reduce_samples' — and its own copy of the slot → pixel order, so that neither the planes nor
+// their meaning depend on what the context renders between two chunks.
+// The arithmetic the host tests restate in numpy: each operation rounded on its own, never fused.
+// (the unit is built with -ffp-contract=off; the pragma says so for these four whatever the flags)
+__device__ __forceinline__ double film_add(double a, double b) {
+#pragma clang fp contract(off)
+  return __dadd_rn(a, b);
+}
+__device__ __forceinline__ double film_sub(double a, double b) {
+#pragma clang fp contract(off)
+  return __dsub_rn(a, b);
+}
+__device__ __forceinline__ double film_mul(double a, double b) {
+#pragma clang fp contract(off)
+  return __dmul_rn(a, b);
+}
+__device__ __forceinline__ double film_div(double a, double b) {
+#pragma clang fp contract(off)
+  return __ddiv_rn(a, b);
+}
+
+// A launch's sample colours folded into a film: s = s + c (the reference's left fold, continued
+// from the film's sums: carry-in and carry-out are the planes) and q = q + (c * c), per sample in
+// sample order.  A new film's planes are zero, so its first launch computes (0 + c_0) like
+// yk_reduce_samples' `first`.  Slots without a pixel keep their zeros.
+struct FilmReduceArgs {
+  const double* col;  // as ReduceArgs::col
+  double* plane;
+  const uint32_t* order;  // the film's own
+  uint32_t npix_slots, ks;
+};
+__global__ __launch_bounds__(256) void yk_film_reduce(FilmReduceArgs fa) {
+  for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < fa.npix_slots; p += gridDim.x * blockDim.x) {
+    if (fa.order[p] == kNoPixel) continue;
+    double s[3], q[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      s[c] = fa.plane[(size_t)c * fa.npix_slots + p];
+      q[c] = fa.plane[(size_t)(3 + c) * fa.npix_slots + p];
+    }
+    for (uint32_t k = 0; k < fa.ks; ++k) {
+      const double* rec = fa.col + ((size_t)k * fa.npix_slots + p) * kColStride;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double v = rec[c];
+        s[c] = film_add(s[c], v);
+        q[c] = film_add(q[c], film_mul(v, v));
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      fa.plane[(size_t)c * fa.npix_slots + p] = s[c];
+      fa.plane[(size_t)(3 + c) * fa.npix_slots + p] = q[c];
+    }
+  }
+}
+
+// to_color3b (source.cpp:73-83) of a film's sums at the divisor `done`, as reduce_slot's last step
+__global__ __launch_bounds__(256) void yk_film_resolve(const double* plane, const uint32_t* order, uint8_t* rgb,
+                                                      uint32_t npix_slots, uint32_t done) {
+  const double n = (double)done;
+  for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < npix_slots; p += gridDim.x * blockDim.x) {
+    const uint32_t px = order[p];
+    if (px == kNoPixel) continue;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      double v = ykd::nsqrt(plane[(size_t)c * npix_slots + p] / n);
+      v = (v < 0.0) ? 0.0 : (0.999 < v) ? 0.999 : v;
+      rgb[(size_t)px * 3 + c] = (uint8_t)(uint32_t)(v * 256);
+    }
+  }
+}
+
+// The error map of a film (include/ykgpu.h ykgpu_film_error): per pixel e2 = max(0, v_r, v_g, v_b),
+// v_c = (q_c - (s_c * s_c) / n) / (n * (n - 1)).  Optionally stores the map (pixel order), and
+// reduces the number of pixels with e2 > threshold2 and the maximum: each thread keeps its own
+// over its grid-stride pixels, a wave combines them with lane exchanges, and lane 0 issues one
+// atomic each per wave.  e2 >= 0, so doubles order like their bit patterns and the maximum is an
+// integer atomicMax; both results are independent of the order of combination.
+__global__ __launch_bounds__(256) void yk_film_error(const double* plane, const uint32_t* order, double* e2_out,
+                                                    unsigned long long* result, uint32_t npix_slots, uint32_t done,
+                                                    double threshold2) {
+  const double n = (double)done;
+  const double den = film_mul(n, film_sub(n, 1.0));
+  unsigned long long over = 0, top = 0;
+  for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < npix_slots; p += gridDim.x * blockDim.x) {
+    const uint32_t px = order[p];
+    if (px == kNoPixel) continue;
+    double e2 = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double s = plane[(size_t)c * npix_slots + p], q = plane[(size_t)(3 + c) * npix_slots + p];
+      const double v = film_div(film_sub(q, film_div(film_mul(s, s), n)), den);
+      if (v > e2) e2 = v;
+    }
+    if (e2_out) e2_out[px] = e2;
+    over += e2 > threshold2 ? 1u : 0u;
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(e2);
+    top = bits > top ? bits : top;
+  }
+  // (every lane reaches this point: the loop above has no early exit)
+  for (int off = 32; off > 0; off >>= 1) {
+    over += __shfl_xor(over, off, 64);
+    const unsigned long long o = __shfl_xor(top, off, 64);
+    top = o > top ? o : top;
+  }
+  if ((threadIdx.x & 63u) == 0) {
+    if (over) atomicAdd(&result[0], over);
+    if (top) atomicMax(&result[1], top);
+  }
+}
+
 // The refined reciprocal of every radius, by the same instructions the division sequence uses
 // (rcp_refined), so the hit normal's (p - c) / radius reuses it (divs_fast_r: bit-identical to
 // divs_fast).  Run once per set_scene.
@@ -2558,6 +2674,7 @@ struct ykgpu_context {
   uint32_t nspheres = 0;
   yk_camera cam{};
   bool have_scene = false;
+  uint64_t scene_gen = 0;  // counts ykgpu_set_scene calls: a film renders only the scene it was created with
   uint32_t* d_counter = nullptr;        // sample-slot counters, one per launch of a call
   uint32_t counter_cap = 0;
   unsigned long long* d_clk = nullptr;  // shader-clock probes, 4 words per launch (YK_CLOCK_*)
@@ -2576,6 +2693,25 @@ struct ykgpu_context {
   uint32_t* d_trace_counts = nullptr;
   uint32_t trace_cap = 0;
   std::chrono::steady_clock::time_point t0;
+};
+
+// A film (include/ykgpu.h): the accumulation state of one tile, owned by the film — the six planes
+// (yk_film_reduce) and the processing order they are laid out in, on the device and on the host
+// (read and write permute there) — plus what fixes its samples: the params, with the seed key
+// drawn at create, and the scene generation.
+struct ykgpu_film {
+  ykgpu_context* ctx = nullptr;
+  int device = 0;
+  yk_render_params p{};
+  uint64_t scene_gen = 0;
+  uint32_t done = 0;
+  uint32_t nps = 0;   // processing slots (>= pixels)
+  uint64_t npix = 0;  // pixels of the tile
+  double* d_plane = nullptr;   // 6 * nps
+  uint32_t* d_order = nullptr;  // nps
+  unsigned long long* d_result = nullptr;  // yk_film_error's count and maximum
+  std::vector<uint32_t> order;
+  bool torn = false;  // an accumulate failed part-way: the planes hold part of a chunk (until a write)
 };
 
 struct ykgpu_group {
@@ -2797,13 +2933,17 @@ constexpr uint32_t kTile = YK_TILE;  // processing blocks of kTile x kTile pixel
 // 2: 16 x 4 tile rows = 16 x 8 image rows; 4: 16 x 4 = 16 x 16; 8: 32 x 2 = 32 x 16): the rays a
 // wave starts together stay coherent (8 x 8 tile blocks of a 4-way tile, 8 x 32 image pixels,
 // cost 17% more per sample, measured).
-int ensure_order(ykgpu_context* ctx, uint32_t W, uint32_t rows, uint32_t stride) {
+uint32_t order_mode() {
   // (A/B knob: YKGPU_ORDER=1 takes the block rows bottom-up)
   const char* oe = ab_knob("YKGPU_ORDER");
-  const uint32_t mode = oe ? (uint32_t)std::atoi(oe) : 0u;
-  if (ctx->d_order && ctx->order_w == W && ctx->order_rows == rows && ctx->order_stride == stride &&
-      ctx->order_mode == mode)
-    return YK_OK;
+  return oe ? (uint32_t)std::atoi(oe) : 0u;
+}
+// image rows per tile row, for the shape of the processing blocks (bands of >= 8 rows: 1, an
+// 8 x 8 block stays inside one band)
+uint32_t order_stride(const yk_render_params* p) {
+  return p->row_count > 1 && p->row_band_log2 < 3 ? p->row_stride : 1;
+}
+std::vector<uint32_t> build_order(uint32_t W, uint32_t rows, uint32_t stride, uint32_t mode) {
   std::vector<uint32_t> ord;
   if (kTile == 0) {
     ord.resize((size_t)W * rows);
@@ -2821,6 +2961,14 @@ int ensure_order(ykgpu_context* ctx, uint32_t W, uint32_t rows, uint32_t stride)
           ord.push_back(x < W && y < rows ? y * W + x : kNoPixel);
         }
   }
+  return ord;
+}
+int ensure_order(ykgpu_context* ctx, uint32_t W, uint32_t rows, uint32_t stride) {
+  const uint32_t mode = order_mode();
+  if (ctx->d_order && ctx->order_w == W && ctx->order_rows == rows && ctx->order_stride == stride &&
+      ctx->order_mode == mode)
+    return YK_OK;
+  const std::vector<uint32_t> ord = build_order(W, rows, stride, mode);
   if (int rc = quiesce(ctx)) return rc;
   (void)hipFree(ctx->d_order);
   ctx->d_order = nullptr;
@@ -2905,8 +3053,13 @@ inline uint32_t warm_blocks_for(uint64_t n, uint64_t cap, uint32_t ilp) {
   return (uint32_t)wb;
 }
 
+// Renders samples [s_begin, s_end) of every pixel.  The one-shot entry points pass [0, spp) and no
+// film: the fold starts from zero, runs through ctx->d_acc and ends in rgb_dev / sums_dev.  A film
+// chunk (ykgpu_film_accumulate) passes its window and the film: the same schedule rule applied to
+// the window's length, the same rings and streams, each launch folded into the film's own planes
+// by yk_film_reduce (carry-in and carry-out), in the film's own processing order.
 int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, double* sums_dev,
-           hipStream_t st) {
+           hipStream_t st, uint32_t s_begin, uint32_t s_end, ykgpu_film* film) {
   const bool f32 = p->precision == YK_PRECISION_FP32;
   const bool x128 = p->rng == YK_RNG_XOR128;  // no warm-ups, no MT scratch
   const DevTree& tree = f32 ? ctx->t32 : ctx->t64;
@@ -2923,11 +3076,9 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
       while (!seed_key) seed_key = ((uint64_t)rd() << 32) | rd();
     }
   }
-  // image rows per tile row, for the shape of the processing blocks (bands of >= 8 rows: 1,
-  // an 8 x 8 block stays inside one band)
-  rc = ensure_order(ctx, tile_width(p), p->row_count,
-                    p->row_count > 1 && p->row_band_log2 < 3 ? p->row_stride : 1);
-  if (rc) return rc;
+  // (a film brings its own order, and leaves the context's alone)
+  if (!film && (rc = ensure_order(ctx, tile_width(p), p->row_count, order_stride(p)))) return rc;
+  const uint32_t* const order = film ? film->d_order : ctx->d_order;
   // Launch schedule (samples per pixel per launch): kFirstLaunch (4), growing by kSchedGrow (2)
   // up to kmax (kLaunchSpp = 32, or more for a small tile), also capped by the colour budget (32 B
   // per sample slot, kLaunchBytes per launch); a short remainder is folded into the launches before
@@ -2938,8 +3089,9 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
   // next launch: many
   // mid-sized launches beat a few large ones.  Independent of the image size, which matters
   // for the per-rank tiles of N GPUs.
-  const uint32_t nps = ctx->order_slots;  // processing slots (>= pixels)
-  const uint32_t spp = p->samples_per_pixel;
+  const uint32_t nps = film ? film->nps : ctx->order_slots;  // processing slots (>= pixels)
+  // samples per pixel of this call (p->samples_per_pixel stays the stride of the seeds)
+  const uint32_t spp = s_end - s_begin;
   // (slots of a launch stay below 2^31: the kernels' fdiv takes 31-bit numerators)
   // A launch of few pixels still gets enough slots to fill the persistent grid (16 per lane):
   // a thin row tile at high spp would otherwise run dozens of launches that each pay a ramp and
@@ -3044,7 +3196,7 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
       const uint32_t rest = spp - (s0 + take);
       if (rest > 0 && rest < std::max(1u, take / 4))
         take = spp - s0 <= kcap ? spp - s0 : (spp - s0 + 1) / 2;
-      sched.emplace_back(s0, take);
+      sched.emplace_back(s_begin + s0, take);
       s0 += take;
       // past kSchedSlow spp the ramp grows by half: a warm-up twice its render's size no longer
       // hides under it (64-spp launches: the 64-spp warm-up under the 32-spp render cost the
@@ -3087,7 +3239,7 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
     if (rc) return rc;
     break;
   }
-  if (sched.size() > 1 && (rc = grow(ctx->d_acc, ctx->acc_cap, (size_t)nps * 3, sizeof(double)))) return rc;
+  if (!film && sched.size() > 1 && (rc = grow(ctx->d_acc, ctx->acc_cap, (size_t)nps * 3, sizeof(double)))) return rc;
   // The FP64 lens warm-ups of launches with at most kDeferSlots slots per warm-up wave draw their
   // lens retries after the walks (yk_mt_warmup_defer) from a ring per wave, sized to the largest
   // such launch (the frame's 32-spp launches: 640 records, 1.0 GB); longer launches run the
@@ -3156,7 +3308,7 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
   ka.flags = p->flags;
   ka.id_stride = ctx->id_stride;
   ka.start = nullptr;
-  ka.order = ctx->d_order;
+  ka.order = order;
   ka.t_min = p->t_min;
   ka.origin_bound = tree.origin_bound;
   ka.inv_w = 1.0 / (double)ka.W;
@@ -3216,7 +3368,7 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
   fastdiv(ka.Wt, wa.w_m, wa.w_sh);
   wa.seed_mode = p->seed_mode;
   wa.seed_key = seed_key;
-  wa.order = ctx->d_order;
+  wa.order = order;
   ka.npix_slots = nps;
   ka.nps_m = wa.nps_m;
   ka.nps_sh = wa.nps_sh;
@@ -3225,12 +3377,18 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
   ka.stack_check = plan.stack_check ? 1u : 0u;
   ReduceArgs ra;
   ra.acc = ctx->d_acc;
-  ra.order = ctx->d_order;
+  ra.order = order;
   ra.rgb = rgb_dev;
   ra.sums = sums_dev;
   ra.npix_slots = nps;
-  ra.spp = spp;
+  ra.spp = p->samples_per_pixel;
   ra.pad0 = ra.pad1 = 0;
+  FilmReduceArgs fa{};
+  if (film) {
+    fa.plane = film->d_plane;
+    fa.order = order;
+    fa.npix_slots = nps;
+  }
   // Cross-call pipelining: the launches are numbered across calls (ctx->g_next) and a launch's
   // ring slots (start records, colours, slot counter), scratch parity and render stream follow its
   // global number, so a call whose rings have the previous call's geometry needs no barrier
@@ -3401,11 +3559,18 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
     ra.nsl = nsl;
     ra.ks = ks;
     ra.first = s0 == 0;
-    ra.last = s0 + ks == spp;
+    ra.last = s0 + ks == s_end;
     YK_HIP(hipStreamWaitEvent(ctx->red, ev[3], 0));
-    if (ov && ra.last) YK_HIP(hipStreamWaitEvent(ctx->red, ctx->ev0, 0));  // the caller's image
+    if (ov && !film && ra.last) YK_HIP(hipStreamWaitEvent(ctx->red, ctx->ev0, 0));  // the caller's image
     YK_HIP(hipEventRecord(ev[4], ctx->red));
-    hipLaunchKernelGGL(yk_reduce_samples, dim3(reduce_blocks(ctx, nps)), dim3(256), 0, ctx->red, ra);
+    if (film) {
+      // (the reduces of a chunk, and of the chunks before it, run in order on ctx->red)
+      fa.col = col;
+      fa.ks = ks;
+      hipLaunchKernelGGL(yk_film_reduce, dim3(reduce_blocks(ctx, nps)), dim3(256), 0, ctx->red, fa);
+    } else {
+      hipLaunchKernelGGL(yk_reduce_samples, dim3(reduce_blocks(ctx, nps)), dim3(256), 0, ctx->red, ra);
+    }
     YK_HIP(hipGetLastError());
     YK_HIP(hipEventRecord(ev[5], ctx->red));
     YK_HIP(hipEventRecord(gdep(g, 1), ctx->red));
@@ -3423,7 +3588,7 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
   ctx->prev_enqueued = true;
   ctx->dirty = false;
   ctx->stats = yk_render_stats{};
-  ctx->stats.samples = (uint64_t)p->row_count * tile_width(p) * p->samples_per_pixel;
+  ctx->stats.samples = (uint64_t)p->row_count * tile_width(p) * spp;
   ctx->stats.launches = launches;
   ctx->stats.grid_blocks = (uint32_t)grid;
   ctx->stats.launch_spp = K;
@@ -3435,7 +3600,8 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
     uint64_t cb = ctx->t64.bytes + ctx->t32.bytes +
                   (uint64_t)ctx->nspheres * (sizeof(SphereGeo) + sizeof(SphereMat) + sizeof(float4));
     cb += (uint64_t)kColRing * nps * K * kColStride * sizeof(double) + (x128 ? 0 : (uint64_t)kWarmRing * nps * K * welem);
-    cb += (nlaunch > 1 ? (uint64_t)nps * 3 * sizeof(double) : 0) + (uint64_t)nps * sizeof(uint32_t);
+    cb += (film ? (uint64_t)nps * 6 * sizeof(double) : nlaunch > 1 ? (uint64_t)nps * 3 * sizeof(double) : 0) +
+          (uint64_t)nps * sizeof(uint32_t);
     cb += nlaunch * sizeof(uint32_t) + kCounters * sizeof(unsigned long long);
     if (retry_cap) cb += retry_n * sizeof(uint4);
     if (!x128) cb += 2 * lanes * ykd::kMtN * sizeof(uint32_t);
@@ -3793,6 +3959,7 @@ int ykgpu_set_scene(ykgpu_context* ctx, const yk_sphere* spheres, uint32_t count
   // ... and for every stream of the context: a launch() that failed part-way may have queued
   // warm-ups, renders or reduces without recording ev1 (still not the rest of the device)
   for (hipStream_t s : {ctx->aux, ctx->red, ctx->ren, ctx->alt}) YK_HIP(hipStreamSynchronize(s));
+  ++ctx->scene_gen;  // from here on the device holds another scene: the context's films are over
   if (count > ctx->nspheres || !ctx->d_geo) {
     (void)hipFree(ctx->d_geo);
     (void)hipFree(ctx->d_mat);
@@ -3861,7 +4028,7 @@ int ykgpu_render_async(ykgpu_context* ctx, const yk_render_params* p, void* rgb_
   YK_HIP(hipSetDevice(ctx->device));
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
   ctx->t0 = std::chrono::steady_clock::now();
-  return launch(ctx, p, (uint8_t*)rgb_device, nullptr, st);
+  return launch(ctx, p, (uint8_t*)rgb_device, nullptr, st, 0, p->samples_per_pixel, nullptr);
 }
 
 static int render_host(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_host,
@@ -3883,7 +4050,7 @@ static int render_host(ykgpu_context* ctx, const yk_render_params* p, uint8_t* r
     YK_HIP(hipMalloc(&ctx->d_sums, npix * 3 * sizeof(double)));
     ctx->sums_cap = npix * 3;
   }
-  rc = launch(ctx, p, ctx->d_rgb, sums_host ? ctx->d_sums : nullptr, ctx->stream);
+  rc = launch(ctx, p, ctx->d_rgb, sums_host ? ctx->d_sums : nullptr, ctx->stream, 0, p->samples_per_pixel, nullptr);
   if (rc) return rc;
   if (rgb_host) YK_HIP(hipMemcpyAsync(rgb_host, ctx->d_rgb, npix * 3, hipMemcpyDeviceToHost, ctx->stream));
   if (sums_host)
@@ -4020,6 +4187,184 @@ int ykgpu_get_stats(ykgpu_context* ctx, yk_render_stats* out) {
   int rc = finish_stats(ctx);
   if (rc) return rc;
   *out = ctx->stats;
+  return YK_OK;
+}
+
+// ---- progressive film (include/ykgpu.h "progressive film") ------------------------------------
+namespace {
+int film_ready(const ykgpu_film* film) {
+  if (!film) return fail(YK_ERR_INVALID, "null film");
+  if (film->torn) return fail(YK_ERR_INVALID, "the film's last accumulate failed part-way: restore it with ykgpu_film_write");
+  return YK_OK;
+}
+uint32_t film_blocks(const ykgpu_film* film) { return std::max(1u, std::min((film->nps + 255) / 256, (uint32_t)film->ctx->cus * 8)); }
+}  // namespace
+
+int ykgpu_film_create(ykgpu_context* ctx, const yk_render_params* params, ykgpu_film** out) {
+  if (!out) return fail(YK_ERR_INVALID, "null out");
+  *out = nullptr;
+  if (!ctx || !params) return fail(YK_ERR_INVALID, "null context or params");
+  yk_render_params p = *params;
+  p.flags &= YK_FLAG_LINEAR_SCAN;  // the diagnostic flags (counting, one lane, tracing) are not a film's
+  int rc = check_params(ctx, &p);
+  if (rc) return rc;
+  if (p.seed_mode == YK_SEED_RANDOM_DEVICE) {
+    // the key of every chunk: the caller's, or one from std::random_device now (source.cpp:159)
+    std::random_device rd;
+    while (!p.seed_key) p.seed_key = ((uint64_t)rd() << 32) | rd();
+  }
+  YK_HIP(hipSetDevice(ctx->device));
+  auto* film = new ykgpu_film();
+  film->ctx = ctx;
+  film->device = ctx->device;
+  film->p = p;
+  film->scene_gen = ctx->scene_gen;
+  film->npix = (uint64_t)p.row_count * tile_width(&p);
+  film->order = build_order(tile_width(&p), p.row_count, order_stride(&p), order_mode());
+  film->nps = (uint32_t)film->order.size();
+  const size_t plane_bytes = (size_t)film->nps * 6 * sizeof(double);
+  hipError_t e = hipMalloc(&film->d_plane, plane_bytes);
+  if (e == hipSuccess) e = hipMalloc(&film->d_order, film->nps * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&film->d_result, 2 * sizeof(unsigned long long));
+  const bool nomem = e == hipErrorOutOfMemory;
+  if (e == hipSuccess) e = hipMemcpy(film->d_order, film->order.data(), film->nps * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(film->d_plane, 0, plane_bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    ykgpu_film_destroy(film);
+    return fail(nomem ? YK_ERR_NOMEM : YK_ERR_DEVICE, std::string("ykgpu_film_create: ") + hipGetErrorString(e));
+  }
+  *out = film;
+  return YK_OK;
+}
+
+int ykgpu_film_destroy(ykgpu_film* film) {
+  if (!film) return YK_OK;
+  (void)hipSetDevice(film->device);
+  (void)hipFree(film->d_plane);
+  (void)hipFree(film->d_order);
+  (void)hipFree(film->d_result);
+  delete film;
+  return YK_OK;
+}
+
+int ykgpu_film_params(const ykgpu_film* film, yk_render_params* out) {
+  if (!film || !out) return fail(YK_ERR_INVALID, "null argument");
+  *out = film->p;
+  return YK_OK;
+}
+
+int ykgpu_film_accumulate(ykgpu_film* film, uint32_t n_samples) {
+  int rc = film_ready(film);
+  if (rc) return rc;
+  ykgpu_context* ctx = film->ctx;
+  if (film->scene_gen != ctx->scene_gen)
+    return fail(YK_ERR_INVALID, "the context's scene was set after the film was created");
+  if (n_samples == 0) return fail(YK_ERR_INVALID, "n_samples must be > 0");
+  if (n_samples > film->p.samples_per_pixel - film->done)
+    return fail(YK_ERR_INVALID, "the chunk passes the film's target (samples_per_pixel)");
+  YK_HIP(hipSetDevice(ctx->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  film->torn = true;  // (until the chunk is whole)
+  rc = launch(ctx, &film->p, nullptr, nullptr, ctx->stream, film->done, film->done + n_samples, film);
+  if (rc) return rc;
+  YK_HIP(hipStreamSynchronize(ctx->stream));
+  rc = finish_stats(ctx);
+  if (rc) return rc;
+  ctx->stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  film->done += n_samples;
+  film->torn = false;
+  return YK_OK;
+}
+
+int ykgpu_film_resolve(ykgpu_film* film, uint8_t* rgb_host) {
+  int rc = film_ready(film);
+  if (rc) return rc;
+  if (!rgb_host) return fail(YK_ERR_INVALID, "null output");
+  if (film->done < 1) return fail(YK_ERR_INVALID, "resolve needs at least one accumulated sample");
+  ykgpu_context* ctx = film->ctx;
+  YK_HIP(hipSetDevice(ctx->device));
+  uint8_t* d_rgb = nullptr;
+  YK_HIP(hipMalloc(&d_rgb, film->npix * 3));
+  hipLaunchKernelGGL(yk_film_resolve, dim3(film_blocks(film)), dim3(256), 0, ctx->stream, film->d_plane, film->d_order,
+                     d_rgb, film->nps, film->done);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(rgb_host, d_rgb, film->npix * 3, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(d_rgb);
+  if (e != hipSuccess) return fail(YK_ERR_DEVICE, std::string("ykgpu_film_resolve: ") + hipGetErrorString(e));
+  return YK_OK;
+}
+
+int ykgpu_film_read(ykgpu_film* film, double* sums, double* sumsq, uint32_t* done) {
+  int rc = film_ready(film);
+  if (rc) return rc;
+  if (done) *done = film->done;
+  if (!sums && !sumsq) return YK_OK;
+  YK_HIP(hipSetDevice(film->device));
+  // the planes are in slot order: copied whole, and permuted to pixel order here
+  const size_t nps = film->nps;
+  std::vector<double> host(nps * 6);
+  YK_HIP(hipMemcpy(host.data(), film->d_plane, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t p = 0; p < nps; ++p) {
+    const uint32_t px = film->order[p];
+    if (px == kNoPixel) continue;
+    for (int c = 0; c < 3; ++c) {
+      if (sums) sums[(size_t)px * 3 + c] = host[c * nps + p];
+      if (sumsq) sumsq[(size_t)px * 3 + c] = host[(3 + c) * nps + p];
+    }
+  }
+  return YK_OK;
+}
+
+int ykgpu_film_write(ykgpu_film* film, const double* sums, const double* sumsq, uint32_t done) {
+  if (!film || !sums || !sumsq) return fail(YK_ERR_INVALID, "null argument");
+  if (done > film->p.samples_per_pixel) return fail(YK_ERR_INVALID, "done passes the film's target (samples_per_pixel)");
+  YK_HIP(hipSetDevice(film->device));
+  const size_t nps = film->nps;
+  std::vector<double> host(nps * 6, 0.0);
+  for (size_t p = 0; p < nps; ++p) {
+    const uint32_t px = film->order[p];
+    if (px == kNoPixel) continue;
+    for (int c = 0; c < 3; ++c) {
+      host[c * nps + p] = sums[(size_t)px * 3 + c];
+      host[(3 + c) * nps + p] = sumsq[(size_t)px * 3 + c];
+    }
+  }
+  YK_HIP(hipMemcpy(film->d_plane, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice));
+  film->done = done;
+  film->torn = false;
+  return YK_OK;
+}
+
+int ykgpu_film_error(ykgpu_film* film, double threshold2, double* e2_host, yk_film_stats* stats) {
+  int rc = film_ready(film);
+  if (rc) return rc;
+  if (film->done < 2) return fail(YK_ERR_INVALID, "the error map needs at least two accumulated samples");
+  ykgpu_context* ctx = film->ctx;
+  YK_HIP(hipSetDevice(ctx->device));
+  double* d_e2 = nullptr;
+  if (e2_host) YK_HIP(hipMalloc(&d_e2, film->npix * sizeof(double)));
+  unsigned long long res[2] = {0, 0};
+  hipError_t e = hipMemsetAsync(film->d_result, 0, sizeof res, ctx->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(yk_film_error, dim3(film_blocks(film)), dim3(256), 0, ctx->stream, film->d_plane, film->d_order,
+                       d_e2, film->d_result, film->nps, film->done, threshold2);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(res, film->d_result, sizeof res, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && e2_host)
+    e = hipMemcpyAsync(e2_host, d_e2, film->npix * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(d_e2);
+  if (e != hipSuccess) return fail(YK_ERR_DEVICE, std::string("ykgpu_film_error: ") + hipGetErrorString(e));
+  if (stats) {
+    stats->pixels = film->npix;
+    stats->pixels_over = res[0];
+    std::memcpy(&stats->max_e2, &res[1], sizeof(double));
+    stats->samples_done = film->done;
+    stats->samples_target = film->p.samples_per_pixel;
+  }
   return YK_OK;
 }
 

@@ -135,7 +135,22 @@ class RenderStats(ctypes.Structure):
         return d
 
 
+class FilmStats(ctypes.Structure):
+    """yk_film_stats (include/ykgpu.h): the error map's count and maximum."""
+    _fields_ = [
+        ("pixels", ctypes.c_uint64),
+        ("pixels_over", ctypes.c_uint64),  # pixels with e2 > threshold2
+        ("max_e2", ctypes.c_double),
+        ("samples_done", ctypes.c_uint32),
+        ("samples_target", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 assert ctypes.sizeof(Sphere) == 80
+assert ctypes.sizeof(FilmStats) == 32
 assert ctypes.sizeof(Camera) == 19 * 8
 assert ctypes.sizeof(RenderParams) == 88
 assert ctypes.sizeof(RenderStats) == 344
