@@ -27,6 +27,7 @@
 #include <string>
 #include <tuple>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../ykgpu.h"
@@ -250,6 +251,29 @@ class film {
     return n;
   }
   void accumulate(uint32_t n) { check(ykgpu_film_accumulate(f_, n), "ykgpu_film_accumulate"); }
+  // one adaptive pass: up to n more samples for every unfinished pixel with fewer than two samples
+  // or e2 > threshold2 (include/ykgpu.h "adaptive passes")
+  yk_film_pass accumulate_adaptive(double threshold2, uint32_t n) {
+    yk_film_pass out{};
+    check(ykgpu_film_accumulate_adaptive(f_, threshold2, n, &out), "ykgpu_film_accumulate_adaptive");
+    return out;
+  }
+  std::vector<uint32_t> counts() {
+    std::vector<uint32_t> c(pixels());
+    check(ykgpu_film_counts(f_, c.data(), nullptr, nullptr), "ykgpu_film_counts");
+    return c;
+  }
+  // (min, max) of the counts, without reading the map
+  std::pair<uint32_t, uint32_t> count_range() {
+    uint32_t lo = 0, hi = 0;
+    check(ykgpu_film_counts(f_, nullptr, &lo, &hi), "ykgpu_film_counts");
+    return {lo, hi};
+  }
+  void write_counts(const std::vector<double>& s, const std::vector<double>& q, const std::vector<uint32_t>& c) {
+    if (s.size() != pixels() * 3 || q.size() != pixels() * 3 || c.size() != pixels())
+      throw error(YK_ERR_INVALID, "write_counts: the arrays do not have the film's size");
+    check(ykgpu_film_write_counts(f_, s.data(), q.data(), c.data()), "ykgpu_film_write_counts");
+  }
   std::vector<uint8_t> resolve() {
     std::vector<uint8_t> img(pixels() * 3);
     check(ykgpu_film_resolve(f_, img.data()), "ykgpu_film_resolve");
@@ -265,23 +289,27 @@ class film {
     std::vector<double> s(pixels() * 3), q(pixels() * 3);
     uint32_t n = 0;
     check(ykgpu_film_read(f_, s.data(), q.data(), &n), "ykgpu_film_read");
-    if (yk_film_save(path.c_str(), &p_, scene_hash, n, s.data(), q.data()) != YK_OK)
-      throw error(YK_ERR_INVALID, "cannot write the film file " + path);
+    const auto range = count_range();
+    // (a v2 file, with the counts, only when they differ: uniform films stay readable by yk_film_load)
+    const int rc = range.first != range.second
+                       ? yk_film_save_counts(path.c_str(), &p_, scene_hash, counts().data(), s.data(), q.data())
+                       : yk_film_save(path.c_str(), &p_, scene_hash, n, s.data(), q.data());
+    if (rc != YK_OK) throw error(YK_ERR_INVALID, "cannot write the film file " + path);
   }
   // resume: refuses a file saved with other params or for another scene
   void load(const std::string& path, uint64_t scene_hash) {
     yk_render_params fp;
     uint64_t h = 0;
-    uint32_t n = 0;
-    if (yk_film_load(path.c_str(), &fp, &h, &n, nullptr, nullptr, 0) != YK_OK)
+    if (yk_film_load_counts(path.c_str(), &fp, &h, nullptr, nullptr, nullptr, 0) != YK_OK)
       throw error(YK_ERR_INVALID, path + " is not a film file");
     if (std::memcmp(&fp, &p_, sizeof fp) != 0)
       throw error(YK_ERR_INVALID, path + " was saved with other render parameters");
     if (h != scene_hash) throw error(YK_ERR_INVALID, path + " was saved for another scene");
     std::vector<double> s(pixels() * 3), q(pixels() * 3);
-    if (yk_film_load(path.c_str(), &fp, &h, &n, s.data(), q.data(), pixels()) != YK_OK)
+    std::vector<uint32_t> c(pixels());
+    if (yk_film_load_counts(path.c_str(), &fp, &h, c.data(), s.data(), q.data(), pixels()) != YK_OK)
       throw error(YK_ERR_INVALID, path + " is not a film file");
-    check(ykgpu_film_write(f_, s.data(), q.data(), n), "ykgpu_film_write");
+    write_counts(s, q, c);
   }
 
  private:

@@ -394,6 +394,51 @@ int yk_film_load(const char* path, yk_render_params* params, uint64_t* scene_has
  * camera, as their bit patterns: the scene a saved film belongs to. */
 uint64_t yk_scene_hash(const yk_sphere* spheres, uint32_t count, const yk_camera* camera);
 
+/* ---- adaptive passes: sample only the pixels still over the error bound ---------------------
+ * (Added under ABI 11 like the film: nothing that existed changed size or meaning.)
+ *
+ * A film keeps a sample count per pixel (zero at create).  While all counts are equal the film is
+ * UNIFORM and every call above behaves as described there.  ykgpu_film_accumulate_adaptive gives
+ * samples only to the pixels that still need them, so counts may differ afterwards.
+ *
+ * Selection, on the state before the pass: pixel p with count n_p is selected iff
+ *   n_p < target  and  (n_p < 2  or  e2_p > threshold2)
+ * e2_p being ykgpu_film_error's formula with n = (double)n_p.  The comparison is strict.  e2 >= 0,
+ * so threshold2 < 0 selects every unfinished pixel (on a fresh film: a uniform chunk).  A selected
+ * pixel receives take_p = min(n_samples, target - n_p) samples: samples [n_p, n_p + take_p) of the
+ * one-shot render (same seeds), folded in sample order.  So every pixel always holds exactly the
+ * first n_p terms of the one-shot render's fold, bit for bit.
+ *
+ * n_samples == 0 or a stale scene: YK_ERR_INVALID.  Nothing selected: YK_OK, a zero pass (but for
+ * min/max_count) and no launch.  ykgpu_get_stats then describes the whole pass: samples ==
+ * samples_added, launches and times summed over the groups (all zero for an empty pass).
+ *
+ * On a non-uniform film: ykgpu_film_accumulate returns YK_ERR_INVALID; ykgpu_film_read's *done and
+ * yk_film_stats.samples_done are the smallest count; ykgpu_film_resolve divides each pixel by its
+ * own count (count 0: black); ykgpu_film_error uses each pixel's own count, and a count below 2
+ * gives e2 = +inf (over any threshold, max_e2 = inf); ykgpu_film_write makes the film uniform. */
+typedef struct yk_film_pass {   /* 32 bytes */
+  uint64_t pixels_selected;     /* pixels that received samples in this pass            */
+  uint64_t samples_added;       /* sum over them of the samples each received           */
+  uint32_t groups;              /* distinct (count, take) groups rendered               */
+  uint32_t launches;            /* path-tracing launches, summed over the groups        */
+  uint32_t min_count, max_count;/* over the tile's pixels, after the pass               */
+} yk_film_pass;
+
+int ykgpu_film_accumulate_adaptive(ykgpu_film* film, double threshold2, uint32_t n_samples, yk_film_pass* out);
+/* The counts: row_count * Wt host words in pixel order (NULL: not wanted), and their extremes. */
+int ykgpu_film_counts(ykgpu_film* film, uint32_t* counts_host, uint32_t* min_count, uint32_t* max_count);
+/* ykgpu_film_write with a count per pixel (each <= target). */
+int ykgpu_film_write_counts(ykgpu_film* film, const double* sums, const double* sumsq, const uint32_t* counts);
+/* "ykfilm2\0" files: the v1 header (done = the smallest count) and params record, then the counts
+ * (uint32, little-endian), the sums and the second moments.  yk_film_load reads v1 only;
+ * yk_film_load_counts reads v2, and v1 with every count equal to the header's done.  A count above
+ * the target, a wrong pixel count, truncated or foreign files: YK_ERR_INVALID. */
+int yk_film_save_counts(const char* path, const yk_render_params* params, uint64_t scene_hash,
+                        const uint32_t* counts, const double* sums, const double* sumsq);
+int yk_film_load_counts(const char* path, yk_render_params* params, uint64_t* scene_hash, uint32_t* counts,
+                        double* sums, double* sumsq, uint64_t capacity_pixels);
+
 /* ---- host-side scene helpers (no device needed) ---------------------------------------- */
 
 /* camera<double>{} of camera.hpp:16-27 (16:9, viewport height 2, focal length 1, origin 0). */

@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 from . import records
-from .records import Camera, FilmStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
+from .records import Camera, FilmPass, FilmStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(PKG_DIR, "lib")
@@ -34,6 +34,8 @@ EXPORTS = (
     "ykgpu_film_create", "ykgpu_film_destroy", "ykgpu_film_params", "ykgpu_film_accumulate",
     "ykgpu_film_resolve", "ykgpu_film_read", "ykgpu_film_write", "ykgpu_film_error",
     "yk_film_save", "yk_film_load", "yk_scene_hash",
+    "ykgpu_film_accumulate_adaptive", "ykgpu_film_counts", "ykgpu_film_write_counts",
+    "yk_film_save_counts", "yk_film_load_counts",
 )
 ABI_VERSION = 11
 SCENE_DIR = os.path.join(PKG_DIR, "scenes")  # committed scene files of the BASELINE configs
@@ -108,6 +110,13 @@ def load_library():
         "yk_film_load": ([c.c_char_p, P(RenderParams), P(c.c_uint64), P(c.c_uint32), c.c_void_p,
                           c.c_void_p, c.c_uint64], c.c_int),
         "yk_scene_hash": ([P(Sphere), c.c_uint32, P(Camera)], c.c_uint64),
+        "ykgpu_film_accumulate_adaptive": ([c.c_void_p, c.c_double, c.c_uint32, P(FilmPass)], c.c_int),
+        "ykgpu_film_counts": ([c.c_void_p, c.c_void_p, P(c.c_uint32), P(c.c_uint32)], c.c_int),
+        "ykgpu_film_write_counts": ([c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p], c.c_int),
+        "yk_film_save_counts": ([c.c_char_p, P(RenderParams), c.c_uint64, c.c_void_p, c.c_void_p, c.c_void_p],
+                                c.c_int),
+        "yk_film_load_counts": ([c.c_char_p, P(RenderParams), P(c.c_uint64), c.c_void_p, c.c_void_p,
+                                 c.c_void_p, c.c_uint64], c.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
@@ -198,6 +207,37 @@ def load_film(path: str):
     return p, h.value, done.value, sums, sumsq
 
 
+def save_film_counts(path: str, params: RenderParams, scene: int, counts, sums, sumsq):
+    """yk_film_save_counts (host only): a v2 film file, with a sample count per pixel."""
+    n = params.row_count * params.tile_width()
+    k = np.ascontiguousarray(counts, dtype=np.uint32)
+    a = np.ascontiguousarray(sums, dtype=np.float64)
+    b = np.ascontiguousarray(sumsq, dtype=np.float64)
+    if k.size != n or a.size != 3 * n or b.size != 3 * n:
+        raise YkError("save_film_counts: counts must hold row_count * tile width words, sums and sumsq 3 doubles each")
+    rc = load_library().yk_film_save_counts(os.fsencode(path), ctypes.byref(params), scene, k.ctypes.data,
+                                            a.ctypes.data, b.ctypes.data)
+    if rc != 0:
+        raise YkError(f"{records.ERRORS.get(rc, rc)}: cannot save the film to {path}")
+
+
+def load_film_counts(path: str):
+    """yk_film_load_counts (host only): a v2 film file, or a v1 file with every count equal to its
+    done.  Returns (RenderParams, scene hash, counts uint32[row_count, tile width], sums, sumsq)."""
+    lib = load_library()
+    p, h = RenderParams(), ctypes.c_uint64(0)
+    rc = lib.yk_film_load_counts(os.fsencode(path), ctypes.byref(p), ctypes.byref(h), None, None, None, 0)
+    if rc == 0:
+        shape = (p.row_count, p.tile_width())
+        counts = np.empty(shape, np.uint32)
+        sums, sumsq = np.empty(shape + (3,), np.float64), np.empty(shape + (3,), np.float64)
+        rc = lib.yk_film_load_counts(os.fsencode(path), ctypes.byref(p), ctypes.byref(h), counts.ctypes.data,
+                                     sums.ctypes.data, sumsq.ctypes.data, shape[0] * shape[1])
+    if rc != 0:
+        raise YkError(f"{records.ERRORS.get(rc, rc)}: {path} is not a readable film file")
+    return p, h.value, counts, sums, sumsq
+
+
 class Film:
     """A progressive film (ykgpu_film, include/ykgpu.h): the resumable accumulation state of one
     tile.  Made by Renderer.film(params); any chunking of the samples yields the one-shot render's
@@ -245,8 +285,37 @@ class Film:
         _check(self._lib.ykgpu_film_accumulate(self._f, n_samples))
         return self.done
 
+    def accumulate_adaptive(self, threshold2: float, n_samples: int) -> FilmPass:
+        """One adaptive pass (ykgpu_film_accumulate_adaptive): up to n_samples more samples for every
+        pixel below the target that has fewer than two samples or e2 > threshold2."""
+        out = FilmPass()
+        _check(self._lib.ykgpu_film_accumulate_adaptive(self._f, threshold2, n_samples, ctypes.byref(out)))
+        return out
+
+    def counts(self) -> np.ndarray:
+        """uint32[row_count, tile width]: the samples each pixel holds."""
+        out = np.empty(self._shape, np.uint32)
+        _check(self._lib.ykgpu_film_counts(self._f, out.ctypes.data, None, None))
+        return out
+
+    def count_range(self):
+        """(min, max) of counts(), without reading the map."""
+        lo, hi = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(self._lib.ykgpu_film_counts(self._f, None, ctypes.byref(lo), ctypes.byref(hi)))
+        return lo.value, hi.value
+
+    def write_counts(self, sums, sumsq, counts):
+        """Restores a state with a count per pixel."""
+        a = np.ascontiguousarray(sums, dtype=np.float64)
+        b = np.ascontiguousarray(sumsq, dtype=np.float64)
+        k = np.ascontiguousarray(counts, dtype=np.uint32)
+        if a.shape != self._shape + (3,) or b.shape != self._shape + (3,) or k.shape != self._shape:
+            raise YkError(f"Film.write_counts: sums and sumsq must have shape {self._shape + (3,)}, counts {self._shape}")
+        _check(self._lib.ykgpu_film_write_counts(self._f, a.ctypes.data, b.ctypes.data, k.ctypes.data))
+
     def resolve(self) -> np.ndarray:
-        """uint8[row_count, tile width, 3]: to_color3b of the sums at the divisor done."""
+        """uint8[row_count, tile width, 3]: to_color3b of the sums at the divisor done (each
+        pixel's own count once they differ)."""
         out = np.empty(self._shape + (3,), np.uint8)
         _check(self._lib.ykgpu_film_resolve(self._f, out.ctypes.data))
         return out
@@ -294,18 +363,25 @@ class Film:
     def save(self, path: str, scene: int):
         """Checkpoint: the film's params, `scene` (scene_hash of the scene it renders) and state."""
         sums, sumsq, done = self.read()
-        save_film(path, self.params, scene, done, sums, sumsq)
+        lo, hi = self.count_range()
+        if lo != hi:  # (a v2 file only when it is needed: uniform films stay readable by yk_film_load)
+            save_film_counts(path, self.params, scene, self.counts(), sums, sumsq)
+        else:
+            save_film(path, self.params, scene, done, sums, sumsq)
 
     def load(self, path: str, scene: int) -> int:
         """Resume: restores the state saved in `path`; refuses a file whose params or scene hash
-        differ from the film's.  Returns done."""
-        p, h, done, sums, sumsq = load_film(path)
+        differ from the film's.  Returns done (the smallest count)."""
+        p, h, counts, sums, sumsq = load_film_counts(path)
         if bytes(p) != bytes(self.params):
             raise YkError(f"{path} was saved with other render params than this film's")
         if h != scene:
             raise YkError(f"{path} was saved for another scene")
-        self.write(sums, sumsq, done)
-        return done
+        if counts.min() == counts.max():
+            self.write(sums, sumsq, int(counts.min()))
+        else:
+            self.write_counts(sums, sumsq, counts)
+        return int(counts.min())
 
 
 class Renderer:
@@ -469,5 +545,5 @@ def render_devices(devices, spheres, camera: Camera, params: RenderParams) -> np
     return out
 
 
-__all__ = ["Renderer", "Film", "scene_hash", "save_film", "load_film", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
+__all__ = ["Renderer", "Film", "FilmPass", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
            "make_params", "load_library", "records", "EXPORTS", "LIB_PATH", "CLI_PATH"]

@@ -85,6 +85,8 @@ const char* kHelp =
     "                            after each chunk (the same image as in one call)\n"
     "      --until arg           stop once no pixel's standard error exceeds arg; prints the\n"
     "                            samples used (chunks of --progressive, default 16)\n"
+    "      --adaptive            with --until: every chunk samples only the pixels still over the\n"
+    "                            bound; prints the samples used per pixel\n"
     "      --checkpoint arg      save the film to this file after every chunk; resume from it\n"
     "                            when it exists (same parameters and scene, else an error)\n"
     "      --stop-after arg      render at most arg chunks in this run (resume with --checkpoint)\n";
@@ -107,7 +109,8 @@ struct args {
   uint32_t progressive = 0, stop_after = 0;
   double until = 0;
   std::string checkpoint;
-  bool film() const { return have_progressive || have_until || have_stop_after || !checkpoint.empty(); }
+  bool adaptive = false;
+  bool film() const { return adaptive || have_progressive || have_until || have_stop_after || !checkpoint.empty(); }
 };
 
 uint32_t to_u32(const std::string& opt, const std::string& v) {
@@ -176,6 +179,7 @@ args parse(int argc, char** argv) {
       else if (n == "progressive") { a.progressive = to_count(n, value(i, n, inl)); a.have_progressive = true; }
       else if (n == "until") { a.until = to_error_bound(n, value(i, n, inl)); a.have_until = true; }
       else if (n == "stop-after") { a.stop_after = to_count(n, value(i, n, inl)); a.have_stop_after = true; }
+      else if (n == "adaptive") { a.adaptive = true; }
       else if (n == "checkpoint") {
         a.checkpoint = value(i, n, inl);
         if (a.checkpoint.empty()) throw option_error{"Option 'checkpoint' needs a file name"};
@@ -201,6 +205,7 @@ args parse(int argc, char** argv) {
       }
     }
   }
+  if (a.adaptive && !a.have_until) throw option_error{"Option 'adaptive' needs --until"};
   return a;
 }
 
@@ -302,7 +307,7 @@ int main(int argc, char* argv[]) {
           std::fclose(f);
           resume = true;
           // a run seeded from random_device continues with the key its checkpoint holds
-          if (yk_film_load(a.checkpoint.c_str(), &fp, nullptr, nullptr, nullptr, nullptr, 0) == YK_OK &&
+          if (yk_film_load_counts(a.checkpoint.c_str(), &fp, nullptr, nullptr, nullptr, nullptr, 0) == YK_OK &&
               p.seed_mode == YK_SEED_RANDOM_DEVICE && fp.seed_mode == YK_SEED_RANDOM_DEVICE)
             p.seed_key = fp.seed_key;
         }
@@ -320,25 +325,49 @@ int main(int argc, char* argv[]) {
       const double threshold2 = a.until * a.until;
       auto converged = [&]() { return a.have_until && film.done() >= 2 && film.error_stats(threshold2).pixels_over == 0; };
       uint32_t chunks = 0;
-      bool stop = converged();
-      while (!stop && film.done() < a.spp && !(a.have_stop_after && chunks >= a.stop_after)) {
-        film.accumulate(std::min(chunk, a.spp - film.done()));
-        ++chunks;
-        const yk_render_stats cs = gpu.stats();
-        st.kernel_ms += cs.kernel_ms;
-        st.samples += cs.samples;
-        st.seed_key = cs.seed_key;
-        if (!a.checkpoint.empty()) film.save(a.checkpoint, scene);
-        stop = converged();
-        // the image so far, for whoever watches the file (the last chunk's is written below)
-        if (!stop && film.done() < a.spp) ykpng::write_rgb(a.output.c_str(), W, H, film.resolve().data());
+      if (a.adaptive) {
+        // every chunk is an adaptive pass at the bound: the first, on a fresh film, is uniform, the
+        // later ones sample only the pixels still over it; the pass that selects nothing ends the run
+        bool stop = false;
+        while (!stop && !(a.have_stop_after && chunks >= a.stop_after)) {
+          stop = film.accumulate_adaptive(threshold2, chunk).pixels_selected == 0;
+          if (stop) break;
+          ++chunks;
+          const yk_render_stats cs = gpu.stats();
+          st.kernel_ms += cs.kernel_ms;
+          st.samples += cs.samples;
+          if (!a.checkpoint.empty()) film.save(a.checkpoint, scene);
+          ykpng::write_rgb(a.output.c_str(), W, H, film.resolve().data());
+        }
+        const auto range = film.count_range();
+        if (range.second == 0) throw ykgpu::error(YK_ERR_INVALID, "nothing rendered");
+        uint64_t total = 0;
+        for (uint32_t c : film.counts()) total += c;
+        image = film.resolve();
+        std::cout << "samples used : " << range.first << ".." << range.second << " per pixel, " << total << " in all"
+                  << std::endl;
+        if (!stop) std::cout << "stopped after " << chunks << " passes" << std::endl;
+      } else {
+        bool stop = converged();
+        while (!stop && film.done() < a.spp && !(a.have_stop_after && chunks >= a.stop_after)) {
+          film.accumulate(std::min(chunk, a.spp - film.done()));
+          ++chunks;
+          const yk_render_stats cs = gpu.stats();
+          st.kernel_ms += cs.kernel_ms;
+          st.samples += cs.samples;
+          st.seed_key = cs.seed_key;
+          if (!a.checkpoint.empty()) film.save(a.checkpoint, scene);
+          stop = converged();
+          // the image so far, for whoever watches the file (the last chunk's is written below)
+          if (!stop && film.done() < a.spp) ykpng::write_rgb(a.output.c_str(), W, H, film.resolve().data());
+        }
+        if (film.done() == 0) throw ykgpu::error(YK_ERR_INVALID, "nothing rendered");
+        image = film.resolve();
+        if (a.have_until) std::cout << "samples used : " << film.done() << std::endl;
+        if (film.done() < a.spp && !stop)
+          std::cout << "stopped at " << film.done() << " of " << a.spp << " samples" << std::endl;
       }
-      if (film.done() == 0) throw ykgpu::error(YK_ERR_INVALID, "nothing rendered");
-      image = film.resolve();
       st.seed_key = film.params().seed_key;
-      if (a.have_until) std::cout << "samples used : " << film.done() << std::endl;
-      if (film.done() < a.spp && !stop)
-        std::cout << "stopped at " << film.done() << " of " << a.spp << " samples" << std::endl;
     }
     if (verbose) {
       ykgpu::render_options vo = ro;

@@ -402,3 +402,81 @@ int yk_film_load(const char* path, yk_render_params* params, uint64_t* scene_has
   if (done) *done = h.done;
   return YK_OK;
 }
+
+// ---- film files with per-pixel counts (include/ykgpu.h "adaptive passes") ----------------------
+// "ykfilm2\0": the v1 header (its `done` holds the smallest count) and params record, then
+// pixels counts (uint32), pixels * 3 sums, pixels * 3 second moments.  yk_film_load keeps to v1.
+namespace {
+const char kFilmMagic2[8] = {'y', 'k', 'f', 'i', 'l', 'm', '2', '\0'};
+}
+
+int yk_film_save_counts(const char* path, const yk_render_params* params, uint64_t scene_hash, const uint32_t* counts,
+                        const double* sums, const double* sumsq) {
+  if (!path || !params || !counts || !sums || !sumsq) return YK_ERR_INVALID;
+  const uint64_t pixels = film_pixels(params);
+  if (!pixels) return YK_ERR_INVALID;
+  uint32_t lo = counts[0];
+  for (uint64_t i = 0; i < pixels; ++i) {
+    if (counts[i] > params->samples_per_pixel) return YK_ERR_INVALID;
+    lo = counts[i] < lo ? counts[i] : lo;
+  }
+  const std::string tmp = std::string(path) + ".part";
+  FILE* f = std::fopen(tmp.c_str(), "wb");
+  if (!f) return YK_ERR_INVALID;
+  FilmHeader h;
+  std::memcpy(h.magic, kFilmMagic2, sizeof h.magic);
+  h.params_bytes = (uint32_t)sizeof(yk_render_params);
+  h.done = lo;
+  h.pixels = pixels;
+  h.scene_hash = scene_hash;
+  const size_t n = (size_t)pixels * 3;
+  bool ok = std::fwrite(&h, sizeof h, 1, f) == 1 && std::fwrite(params, sizeof *params, 1, f) == 1 &&
+            std::fwrite(counts, sizeof(uint32_t), (size_t)pixels, f) == (size_t)pixels &&
+            std::fwrite(sums, sizeof(double), n, f) == n && std::fwrite(sumsq, sizeof(double), n, f) == n;
+  ok = std::fclose(f) == 0 && ok;
+  if (ok) ok = std::rename(tmp.c_str(), path) == 0;
+  if (!ok) std::remove(tmp.c_str());
+  return ok ? YK_OK : YK_ERR_INVALID;
+}
+
+int yk_film_load_counts(const char* path, yk_render_params* params, uint64_t* scene_hash, uint32_t* counts,
+                        double* sums, double* sumsq, uint64_t capacity_pixels) {
+  if (!path) return YK_ERR_INVALID;
+  FILE* f = std::fopen(path, "rb");
+  if (!f) return YK_ERR_INVALID;
+  FilmHeader h;
+  yk_render_params p;
+  bool ok = std::fread(&h, sizeof h, 1, f) == 1;
+  const bool v2 = ok && std::memcmp(h.magic, kFilmMagic2, sizeof h.magic) == 0;
+  ok = ok && (v2 || std::memcmp(h.magic, kFilmMagic, sizeof h.magic) == 0) &&
+       h.params_bytes == sizeof(yk_render_params) && std::fread(&p, sizeof p, 1, f) == 1;
+  ok = ok && h.pixels != 0 && h.pixels == film_pixels(&p) && h.pixels < (1ull << 31) &&
+       h.done <= p.samples_per_pixel;
+  // the whole payload must be there, and nothing after it, whether or not it is read
+  if (ok) {
+    const long at = std::ftell(f);
+    const uint64_t payload = h.pixels * 6 * sizeof(double) + (v2 ? h.pixels * sizeof(uint32_t) : 0);
+    ok = at >= 0 && std::fseek(f, 0, SEEK_END) == 0 && (uint64_t)std::ftell(f) == (uint64_t)at + payload &&
+         std::fseek(f, at, SEEK_SET) == 0;
+  }
+  if (ok && (counts || sums || sumsq)) ok = capacity_pixels >= h.pixels;
+  if (ok) {
+    // the counts are always read: one above the target makes the file foreign
+    std::vector<uint32_t> cn((size_t)h.pixels, h.done);
+    if (v2) ok = std::fread(cn.data(), sizeof(uint32_t), cn.size(), f) == cn.size();
+    for (size_t i = 0; ok && i < cn.size(); ++i) ok = cn[i] <= p.samples_per_pixel && cn[i] >= h.done;
+    if (ok && counts) std::memcpy(counts, cn.data(), cn.size() * sizeof(uint32_t));
+  }
+  if (ok && (sums || sumsq)) {
+    const size_t n = (size_t)h.pixels * 3;
+    std::vector<double> skip;
+    if (!(sums && sumsq)) skip.resize(n);
+    ok = std::fread(sums ? sums : skip.data(), sizeof(double), n, f) == n &&
+         std::fread(sumsq ? sumsq : skip.data(), sizeof(double), n, f) == n;
+  }
+  std::fclose(f);
+  if (!ok) return YK_ERR_INVALID;
+  if (params) *params = p;
+  if (scene_hash) *scene_hash = h.scene_hash;
+  return YK_OK;
+}

@@ -149,7 +149,23 @@ class FilmStats(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class FilmPass(ctypes.Structure):
+    """yk_film_pass (include/ykgpu.h): what one adaptive pass did."""
+    _fields_ = [
+        ("pixels_selected", ctypes.c_uint64),
+        ("samples_added", ctypes.c_uint64),
+        ("groups", ctypes.c_uint32),  # distinct (count, take) groups rendered
+        ("launches", ctypes.c_uint32),
+        ("min_count", ctypes.c_uint32),  # over the tile's pixels, after the pass
+        ("max_count", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 assert ctypes.sizeof(Sphere) == 80
+assert ctypes.sizeof(FilmPass) == 32
 assert ctypes.sizeof(FilmStats) == 32
 assert ctypes.sizeof(Camera) == 19 * 8
 assert ctypes.sizeof(RenderParams) == 88
