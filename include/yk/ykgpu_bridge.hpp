@@ -279,6 +279,13 @@ class film {
     check(ykgpu_film_resolve(f_, img.data()), "ykgpu_film_resolve");
     return img;
   }
+  // the RGB8 image of the variance-guided non-local-means filter (include/ykgpu.h "film denoise");
+  // every pixel needs at least two samples and the tile must be consecutive rows and columns
+  std::vector<uint8_t> denoise(const yk_denoise_params& dp, yk_denoise_stats* stats = nullptr) {
+    std::vector<uint8_t> img(pixels() * 3);
+    check(ykgpu_film_denoise(f_, &dp, nullptr, img.data(), stats), "ykgpu_film_denoise");
+    return img;
+  }
   yk_film_stats error_stats(double threshold2) {
     yk_film_stats st;
     check(ykgpu_film_error(f_, threshold2, nullptr, &st), "ykgpu_film_error");

@@ -439,6 +439,59 @@ int yk_film_save_counts(const char* path, const yk_render_params* params, uint64
 int yk_film_load_counts(const char* path, yk_render_params* params, uint64_t* scene_hash, uint32_t* counts,
                         double* sums, double* sumsq, uint64_t capacity_pixels);
 
+/* ---- film denoise: a variance-guided non-local-means filter, defined exactly -----------------
+ * (Added under ABI 11 like the film: nothing that existed changed size or meaning.)
+ *
+ * The film's tile is a grid of row_count x Wt pixels; the filter runs on that grid and never looks
+ * outside it.  Pixel p = (i, j) with count n, sums s_c and second moments q_c has, with nd = (double)n,
+ *   m_c = s_c / nd
+ *   v_c = max(0, (q_c - (s_c*s_c)/nd) / (nd*(nd - 1)))            (ykgpu_film_error's v_c; v > 0 ? v : 0)
+ * Window offsets d run row-major, dy = -R..R outside, dx inside.  For each d with q = p + d inside the tile:
+ *   S = 0
+ *   for o row-major over the patch (oy = -F..F outside, ox inside):
+ *     p' = clamp(p + o), q' = clamp(q + o)                         (each coordinate clamped to the tile)
+ *     for c in r, g, b:
+ *       d   = m_c(p') - m_c(q')
+ *       t_c = ((d*d) - alpha*(v_c(p') + min(v_c(q'), v_c(p')))) / (eps + k2*(v_c(p') + v_c(q')))
+ *     S = S + ((t_r + t_g) + t_b)
+ *   D = S / (double)(3*(2F+1)^2);  D = D > 0 ? D : 0
+ *   t = 1 - 0.25*D;  t = t > 0 ? t : 0
+ *   w = (t*t)*(t*t)                                                (compact stand-in for exp(-D))
+ *   acc_c = acc_c + (w * m_c(q));  wsum = wsum + w
+ * out_c(p) = acc_c / wsum.  Every + - * / is one IEEE double operation, rounded on its own and never
+ * fused, in exactly that order, so numpy reproduces the result bit for bit.  The centre term has D = 0
+ * and w = 1, so wsum >= 1; radius 0 returns m.  The RGB8 image is ykgpu_film_resolve's steps after its
+ * division applied to out_c (math::sqrt, clamp to [0, 0.999], *256, truncate).
+ *
+ * ykgpu_film_denoise is synchronous and only reads the film: sums, second moments and counts stay as
+ * they are.  It works on uniform and on adaptive (non-uniform) films, each pixel using its own count.
+ * The buffers it needs (9 doubles and 3 bytes per pixel) are allocated at the film's first denoise and
+ * freed with the film.  Errors, with nothing written to mean_host / rgb_host / stats:
+ *   YK_ERR_INVALID      a parameter out of range (radius > 10, patch > 3, k2 <= 0, alpha < 0, eps <= 0)
+ *                       or not finite; mean_host and rgb_host both NULL; any pixel's count below 2
+ *   YK_ERR_UNSUPPORTED  the tile is not consecutive image rows and consecutive image columns (a strided
+ *                       tile has no neighbours to filter over) */
+typedef struct yk_denoise_params { /* 32 bytes */
+  uint32_t radius;                 /* R, 0..10: the window is (2R+1)^2 neighbours    */
+  uint32_t patch;                  /* F, 0..3: patches of (2F+1)^2 pixels            */
+  double k2;                       /* > 0: the distance's variance scale             */
+  double alpha;                    /* >= 0: the variance cancellation                */
+  double eps;                      /* > 0: keeps the division defined at v = 0       */
+} yk_denoise_params;
+
+typedef struct yk_denoise_stats {  /* 24 bytes */
+  double moments_ms;               /* the gather of m and v (device)                 */
+  double filter_ms;                /* the filter and the RGB8 conversion (device)    */
+  double total_ms;                 /* the call's host wall clock, copies included    */
+} yk_denoise_stats;
+
+/* radius 5, patch 1, k2 0.5, alpha 1.0, eps 1e-10 (host only) */
+int yk_denoise_defaults(yk_denoise_params* out);
+/* params NULL: the defaults.  mean_host: row_count * Wt * 3 doubles, pixel order (may be NULL);
+ * rgb_host: row_count * Wt * 3 bytes (may be NULL); stats may be NULL. */
+int ykgpu_film_denoise(ykgpu_film* film, const yk_denoise_params* params, double* mean_host, uint8_t* rgb_host,
+                       yk_denoise_stats* stats);
+
 /* ---- host-side scene helpers (no device needed) ---------------------------------------- */
 
 /* camera<double>{} of camera.hpp:16-27 (16:9, viewport height 2, focal length 1, origin 0). */

@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 from . import records
-from .records import Camera, FilmPass, FilmStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
+from .records import Camera, DenoiseParams, DenoiseStats, FilmPass, FilmStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(PKG_DIR, "lib")
@@ -36,6 +36,7 @@ EXPORTS = (
     "yk_film_save", "yk_film_load", "yk_scene_hash",
     "ykgpu_film_accumulate_adaptive", "ykgpu_film_counts", "ykgpu_film_write_counts",
     "yk_film_save_counts", "yk_film_load_counts",
+    "yk_denoise_defaults", "ykgpu_film_denoise",
 )
 ABI_VERSION = 11
 SCENE_DIR = os.path.join(PKG_DIR, "scenes")  # committed scene files of the BASELINE configs
@@ -117,6 +118,8 @@ def load_library():
                                 c.c_int),
         "yk_film_load_counts": ([c.c_char_p, P(RenderParams), P(c.c_uint64), c.c_void_p, c.c_void_p,
                                  c.c_void_p, c.c_uint64], c.c_int),
+        "yk_denoise_defaults": ([P(DenoiseParams)], c.c_int),
+        "ykgpu_film_denoise": ([c.c_void_p, P(DenoiseParams), c.c_void_p, c.c_void_p, P(DenoiseStats)], c.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
@@ -238,6 +241,13 @@ def load_film_counts(path: str):
     return p, h.value, counts, sums, sumsq
 
 
+def denoise_defaults() -> DenoiseParams:
+    """yk_denoise_defaults (host only): radius 5, patch 1, k2 0.5, alpha 1.0, eps 1e-10."""
+    dp = DenoiseParams()
+    _check(load_library().yk_denoise_defaults(ctypes.byref(dp)))
+    return dp
+
+
 class Film:
     """A progressive film (ykgpu_film, include/ykgpu.h): the resumable accumulation state of one
     tile.  Made by Renderer.film(params); any chunking of the samples yields the one-shot render's
@@ -343,6 +353,18 @@ class Film:
         _check(self._lib.ykgpu_film_error(self._f, threshold2, e2.ctypes.data if want_map else None,
                                           ctypes.byref(st)))
         return e2, st.as_dict()
+
+    def denoise(self, radius: int = 5, patch: int = 1, k2: float = 0.5, alpha: float = 1.0, eps: float = 1e-10,
+                want_mean: bool = True, want_rgb: bool = True):
+        """(mean float64[row_count, tile width, 3] | None, rgb uint8[row_count, tile width, 3] | None,
+        stats dict): the variance-guided non-local-means filter of include/ykgpu.h "film denoise" on
+        the film's tile.  Reads the film only; every pixel needs at least two samples."""
+        mean = np.empty(self._shape + (3,), np.float64) if want_mean else None
+        rgb = np.empty(self._shape + (3,), np.uint8) if want_rgb else None
+        dp, st = DenoiseParams(radius, patch, k2, alpha, eps), DenoiseStats()
+        _check(self._lib.ykgpu_film_denoise(self._f, ctypes.byref(dp), mean.ctypes.data if want_mean else None,
+                                            rgb.ctypes.data if want_rgb else None, ctypes.byref(st)))
+        return mean, rgb, st.as_dict()
 
     def render_until(self, threshold: float, chunk: int) -> dict:
         """Accumulates `chunk` samples at a time until no pixel's standard error exceeds
@@ -545,5 +567,5 @@ def render_devices(devices, spheres, camera: Camera, params: RenderParams) -> np
     return out
 
 
-__all__ = ["Renderer", "Film", "FilmPass", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
+__all__ = ["Renderer", "Film", "FilmPass", "DenoiseParams", "DenoiseStats", "denoise_defaults", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
            "make_params", "load_library", "records", "EXPORTS", "LIB_PATH", "CLI_PATH"]

@@ -18,9 +18,10 @@
 //
 // Added (render parameters are compile-time macros in the reference): --width, --spp,
 // --depth, --scene, --scene-seed, --scene-file, --save-scene, --seed0, --precision, --rng,
-// --device, --stats, and the progressive film's --progressive, --until, --checkpoint, --stop-after
+// --device, --stats, the progressive film's --progressive, --until, --checkpoint, --stop-after
 // (include/ykgpu.h "progressive film": the image in chunks of samples, the same bytes as in one
-// call).  --seed0 fixes the per-sample seed base (seed0 + (y*W+x)*spp + s, the constexpr
+// call), and --denoise with --denoise-radius, --denoise-patch, --denoise-k2 (include/ykgpu.h "film
+// denoise": the final image and every preview through the film's variance-guided filter).  --seed0 fixes the per-sample seed base (seed0 + (y*W+x)*spp + s, the constexpr
 // build's formula, source.cpp:154-158); without it every sample gets its own seed from a
 // per-call std::random_device key (YK_SEED_RANDOM_DEVICE), like the reference's runtime build
 // (source.cpp:159).  --precision fp32 renders render<float> (T = float, source.cpp:98);
@@ -89,7 +90,13 @@ const char* kHelp =
     "                            bound; prints the samples used per pixel\n"
     "      --checkpoint arg      save the film to this file after every chunk; resume from it\n"
     "                            when it exists (same parameters and scene, else an error)\n"
-    "      --stop-after arg      render at most arg chunks in this run (resume with --checkpoint)\n";
+    "      --stop-after arg      render at most arg chunks in this run (resume with --checkpoint)\n"
+    "      --denoise             write the variance-guided non-local-means filter of the film's\n"
+    "                            mean (the final image and every --progressive preview) instead\n"
+    "                            of the raw mean; needs at least 2 samples per pixel\n"
+    "      --denoise-radius arg  the filter's window radius, 0..10 (default: 5)\n"
+    "      --denoise-patch arg   the filter's patch radius, 0..3 (default: 1)\n"
+    "      --denoise-k2 arg      the filter's variance scale, > 0 (default: 0.5)\n";
 
 struct args {
   bool help = false, verbose_flag = false, stats = false;
@@ -110,7 +117,10 @@ struct args {
   double until = 0;
   std::string checkpoint;
   bool adaptive = false;
-  bool film() const { return adaptive || have_progressive || have_until || have_stop_after || !checkpoint.empty(); }
+  // the film's denoise filter (the options other than --denoise only set its parameters)
+  bool denoise = false, have_denoise_params = false;
+  yk_denoise_params dn{};
+  bool film() const { return denoise || adaptive || have_progressive || have_until || have_stop_after || !checkpoint.empty(); }
 };
 
 uint32_t to_u32(const std::string& opt, const std::string& v) {
@@ -129,6 +139,12 @@ double to_error_bound(const std::string& opt, const std::string& v) {
   return x;
 }
 
+double to_positive(const std::string& opt, const std::string& v) {
+  const double x = to_error_bound(opt, v);
+  if (!(x > 0)) throw option_error{"Argument '" + v + "' must be greater than 0 (option " + opt + ")"};
+  return x;
+}
+
 uint32_t to_count(const std::string& opt, const std::string& v) {
   const uint32_t x = to_u32(opt, v);
   if (!x) throw option_error{"Argument '" + v + "' must be at least 1 (option " + opt + ")"};
@@ -137,6 +153,7 @@ uint32_t to_count(const std::string& opt, const std::string& v) {
 
 args parse(int argc, char** argv) {
   args a;
+  yk_denoise_defaults(&a.dn);
   int positional = 0;
   auto value = [&](int& i, const std::string& name, const std::string& inl) -> std::string {
     if (!inl.empty()) return inl;
@@ -180,6 +197,10 @@ args parse(int argc, char** argv) {
       else if (n == "until") { a.until = to_error_bound(n, value(i, n, inl)); a.have_until = true; }
       else if (n == "stop-after") { a.stop_after = to_count(n, value(i, n, inl)); a.have_stop_after = true; }
       else if (n == "adaptive") { a.adaptive = true; }
+      else if (n == "denoise") { a.denoise = true; }
+      else if (n == "denoise-radius") { a.dn.radius = to_u32(n, value(i, n, inl)); a.have_denoise_params = true; }
+      else if (n == "denoise-patch") { a.dn.patch = to_u32(n, value(i, n, inl)); a.have_denoise_params = true; }
+      else if (n == "denoise-k2") { a.dn.k2 = to_positive(n, value(i, n, inl)); a.have_denoise_params = true; }
       else if (n == "checkpoint") {
         a.checkpoint = value(i, n, inl);
         if (a.checkpoint.empty()) throw option_error{"Option 'checkpoint' needs a file name"};
@@ -206,6 +227,9 @@ args parse(int argc, char** argv) {
     }
   }
   if (a.adaptive && !a.have_until) throw option_error{"Option 'adaptive' needs --until"};
+  if (a.have_denoise_params && !a.denoise) throw option_error{"The denoise parameters need --denoise"};
+  if (a.dn.radius > 10) throw option_error{"Option 'denoise-radius' must be at most 10"};
+  if (a.dn.patch > 3) throw option_error{"Option 'denoise-patch' must be at most 3"};
   return a;
 }
 
@@ -324,6 +348,12 @@ int main(int argc, char* argv[]) {
       const uint32_t chunk = a.have_progressive ? a.progressive : a.have_until ? 16u : a.spp;
       const double threshold2 = a.until * a.until;
       auto converged = [&]() { return a.have_until && film.done() >= 2 && film.error_stats(threshold2).pixels_over == 0; };
+      // the picture of the film's state: its mean, or with --denoise the filtered mean (a preview
+      // of a film that still has a pixel below two samples stays the raw mean; the final image
+      // does not: the filter's error is the run's)
+      auto picture = [&](bool preview) {
+        return a.denoise && !(preview && film.count_range().first < 2) ? film.denoise(a.dn) : film.resolve();
+      };
       uint32_t chunks = 0;
       if (a.adaptive) {
         // every chunk is an adaptive pass at the bound: the first, on a fresh film, is uniform, the
@@ -337,13 +367,13 @@ int main(int argc, char* argv[]) {
           st.kernel_ms += cs.kernel_ms;
           st.samples += cs.samples;
           if (!a.checkpoint.empty()) film.save(a.checkpoint, scene);
-          ykpng::write_rgb(a.output.c_str(), W, H, film.resolve().data());
+          ykpng::write_rgb(a.output.c_str(), W, H, picture(true).data());
         }
         const auto range = film.count_range();
         if (range.second == 0) throw ykgpu::error(YK_ERR_INVALID, "nothing rendered");
         uint64_t total = 0;
         for (uint32_t c : film.counts()) total += c;
-        image = film.resolve();
+        image = picture(false);
         std::cout << "samples used : " << range.first << ".." << range.second << " per pixel, " << total << " in all"
                   << std::endl;
         if (!stop) std::cout << "stopped after " << chunks << " passes" << std::endl;
@@ -359,10 +389,10 @@ int main(int argc, char* argv[]) {
           if (!a.checkpoint.empty()) film.save(a.checkpoint, scene);
           stop = converged();
           // the image so far, for whoever watches the file (the last chunk's is written below)
-          if (!stop && film.done() < a.spp) ykpng::write_rgb(a.output.c_str(), W, H, film.resolve().data());
+          if (!stop && film.done() < a.spp) ykpng::write_rgb(a.output.c_str(), W, H, picture(true).data());
         }
         if (film.done() == 0) throw ykgpu::error(YK_ERR_INVALID, "nothing rendered");
-        image = film.resolve();
+        image = picture(false);
         if (a.have_until) std::cout << "samples used : " << film.done() << std::endl;
         if (film.done() < a.spp && !stop)
           std::cout << "stopped at " << film.done() << " of " << a.spp << " samples" << std::endl;

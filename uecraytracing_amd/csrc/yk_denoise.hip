@@ -1,0 +1,301 @@
+// yk_denoise.hip — ykgpu_film_denoise (include/ykgpu.h "film denoise"): a
+// variance-guided non-local-means filter over a film's own tile, defined operation by operation in
+// IEEE double so that numpy restates it bit for bit (tests/film_denoise_ref.py).
+//
+// A unit of its own: the render unit's kernels compile exactly as before, and this one reaches a
+// film only through yk_film_view (yk_film_internal.hpp).  Three kernels on the context's stream:
+//   yk_film_moments  slot-order sums and second moments → pixel-order planes m_c, v_c
+//   yk_film_nlm      the filter, one workgroup per 32 x 8 pixels, m and v of the block and its
+//                    halo in LDS
+//   yk_film_rgb8     to_color3b's steps after its division on the filtered mean
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "../../include/ykgpu.h"
+#include "yk_device.hpp"
+#include "yk_film_internal.hpp"
+
+namespace {
+
+constexpr uint32_t kNoPixel = 0xffffffffu;
+constexpr uint32_t kMaxRadius = 10, kMaxPatch = 3;
+// The block of output pixels of one workgroup.  32 wide: a wave is two rows of 32 threads, and the
+// 32 lanes an 8-byte LDS read is serviced in (ds_read_b64: two groups of 32 lanes over 64 banks of
+// 4 B) are one row — 32 consecutive doubles, every bank once — whatever the plane's pitch and
+// whatever the window offset.
+constexpr uint32_t kBlockW = 32, kBlockH = 8, kThreads = kBlockW * kBlockH;
+
+#define YKD_HIP(call)                                                                             \
+  do {                                                                                            \
+    hipError_t e_ = (call);                                                                       \
+    if (e_ != hipSuccess)                                                                         \
+      return yk_film_fail(e_ == hipErrorOutOfMemory ? YK_ERR_NOMEM : YK_ERR_DEVICE,               \
+                          (std::string(#call) + ": " + hipGetErrorString(e_)).c_str());           \
+  } while (0)
+
+// m_c = s_c / nd and v_c = max(0, (q_c - (s_c*s_c)/nd) / (nd*(nd - 1))) (film_e2's v_c) of every
+// slot, gathered through the film's slot → pixel order into six pixel-order planes
+// mv[c * npix + px] (m: c = 0..2, v: 3..5).  count (null for a uniform film): each slot's own n.
+// *low receives the number of pixels whose count is below 2 (their planes are zeroed), reduced like
+// yk_film_error's results: per thread, then lane exchanges, then one atomic per wave.
+__global__ __launch_bounds__(256) void yk_film_moments(const double* plane, const uint32_t* order,
+                                                      const uint32_t* count, double* mv, unsigned long long* low,
+                                                      uint32_t npix_slots, uint32_t npix, uint32_t done) {
+  unsigned long long below = 0;
+  for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < npix_slots; p += gridDim.x * blockDim.x) {
+    const uint32_t px = order[p];
+    if (px == kNoPixel) continue;
+    const uint32_t np = count ? count[p] : done;
+    const bool ok = np >= 2;
+    below += ok ? 0u : 1u;
+    const double nd = (double)np;
+    const double den = film_mul(nd, film_sub(nd, 1.0));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double s = plane[(size_t)c * npix_slots + p], q = plane[(size_t)(3 + c) * npix_slots + p];
+      const double m = film_div(s, nd);
+      const double v = film_div(film_sub(q, film_div(film_mul(s, s), nd)), den);
+      mv[(size_t)c * npix + px] = ok ? m : 0.0;
+      mv[(size_t)(3 + c) * npix + px] = ok && v > 0.0 ? v : 0.0;
+    }
+  }
+  // (every lane reaches this point: the loop above has no early exit)
+  for (int off = 32; off > 0; off >>= 1) below += __shfl_xor(below, off, 64);
+  if ((threadIdx.x & 63u) == 0 && below) atomicAdd(low, below);
+}
+
+struct NlmArgs {
+  const double* mv;  // yk_film_moments' planes
+  double* out;       // rows * wt * 3, pixel order
+  uint32_t rows, wt, npix;
+  uint32_t radius, patch;
+  double k2, alpha, eps, npatch;  // npatch = (double)(3 * (2F+1)^2)
+};
+
+// The filter.  With H = R + F, a workgroup keeps m_c and v_c of its block grown by H on every side
+// in LDS — six planes of (8 + 2H) x (32 + 2H) doubles, the coordinates clamped to the tile at load,
+// so that clamp(u) is simply position u — and two planes of (8 + 2F) x (32 + 2F) doubles for the
+// patch terms.  For every window offset d, row-major:
+//   1. the term ((t_r + t_g) + t_b)(u) between clamp(u) and clamp(u + d) for every u of the block
+//      grown by F: with u = p + o the term of (p, o) depends on u alone, so it is computed once
+//      (3 divisions) and not once per patch that covers it;
+//   2. after a barrier, each thread sums the (2F+1)^2 terms of its pixel in patch order — the
+//      additions of the definition in the definition's order — and folds w * m(q) into its
+//      registers when q = p + d is inside the tile.
+// The term planes alternate, so step 1 of the next offset may begin while other waves are still in
+// step 2 of this one: one barrier per offset.  Offsets for which no pixel of the block has its
+// neighbour inside the tile are skipped by the whole workgroup.
+__global__ __launch_bounds__(kThreads) void yk_film_nlm(NlmArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int R = (int)a.radius, F = (int)a.patch, H = R + F;
+  const int pw = (int)kBlockW + 2 * H, ph = (int)kBlockH + 2 * H;  // the six m / v planes
+  const int tw = (int)kBlockW + 2 * F, th = (int)kBlockH + 2 * F;  // the term planes
+  const int plane = pw * ph;
+  double* const term = lds + 6 * plane;
+  const int rows = (int)a.rows, wt = (int)a.wt;
+  const int x0 = (int)(blockIdx.x * kBlockW), y0 = (int)(blockIdx.y * kBlockH);
+  const int tid = (int)threadIdx.x;
+
+  for (int i = tid; i < plane; i += (int)kThreads) {
+    const int ly = i / pw, lx = i - ly * pw;
+    int gy = y0 - H + ly, gx = x0 - H + lx;
+    gy = gy < 0 ? 0 : gy > rows - 1 ? rows - 1 : gy;
+    gx = gx < 0 ? 0 : gx > wt - 1 ? wt - 1 : gx;
+    const size_t g = (size_t)gy * a.wt + gx;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) lds[c * plane + i] = a.mv[(size_t)c * a.npix + g];
+  }
+  __syncthreads();
+
+  const int tx = tid & (int)(kBlockW - 1), ty = tid / (int)kBlockW;
+  const int py = y0 + ty, px = x0 + tx;
+  const bool mine = py < rows && px < wt;
+  // the rows and columns of the block that exist in the tile (for the whole-block skip)
+  const int by1 = (y0 + (int)kBlockH < rows ? y0 + (int)kBlockH : rows) - 1;
+  const int bx1 = (x0 + (int)kBlockW < wt ? x0 + (int)kBlockW : wt) - 1;
+  double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, wsum = 0.0;
+  int buf = 0;
+  for (int dy = -R; dy <= R; ++dy) {
+    if (by1 + dy < 0 || y0 + dy > rows - 1) continue;  // (uniform over the workgroup)
+    for (int dx = -R; dx <= R; ++dx) {
+      if (bx1 + dx < 0 || x0 + dx > wt - 1) continue;  // (uniform over the workgroup)
+      double* const t = term + buf * (tw * th);
+      for (int i = tid; i < tw * th; i += (int)kThreads) {
+        const int uy = i / tw, ux = i - uy * tw;
+        const int ip = (uy + R) * pw + (ux + R);  // u in the m / v planes: the term plane starts at -F, they at -H
+        const int iq = ip + dy * pw + dx;         // u + d
+        double s3[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const double mp = lds[c * plane + ip], mq = lds[c * plane + iq];
+          const double vp = lds[(3 + c) * plane + ip], vq = lds[(3 + c) * plane + iq];
+          const double d = film_sub(mp, mq);
+          const double num = film_sub(film_mul(d, d), film_mul(a.alpha, film_add(vp, vq < vp ? vq : vp)));
+          const double den = film_add(a.eps, film_mul(a.k2, film_add(vp, vq)));
+          s3[c] = film_div(num, den);
+        }
+        t[i] = film_add(film_add(s3[0], s3[1]), s3[2]);
+      }
+      __syncthreads();
+      if (mine && py + dy >= 0 && py + dy < rows && px + dx >= 0 && px + dx < wt) {
+        double S = 0.0;
+        for (int oy = 0; oy <= 2 * F; ++oy)
+          for (int ox = 0; ox <= 2 * F; ++ox) S = film_add(S, t[(ty + oy) * tw + tx + ox]);
+        double D = film_div(S, a.npatch);
+        D = D > 0.0 ? D : 0.0;
+        double w = film_sub(1.0, film_mul(0.25, D));
+        w = w > 0.0 ? w : 0.0;
+        w = film_mul(film_mul(w, w), film_mul(w, w));
+        const int iq = (ty + H + dy) * pw + tx + H + dx;
+        acc0 = film_add(acc0, film_mul(w, lds[iq]));
+        acc1 = film_add(acc1, film_mul(w, lds[plane + iq]));
+        acc2 = film_add(acc2, film_mul(w, lds[2 * plane + iq]));
+        wsum = film_add(wsum, w);
+      }
+      buf ^= 1;
+    }
+  }
+  if (mine) {
+    double* o = a.out + ((size_t)py * a.wt + px) * 3;
+    o[0] = film_div(acc0, wsum);
+    o[1] = film_div(acc1, wsum);
+    o[2] = film_div(acc2, wsum);
+  }
+}
+
+// ykgpu_film_resolve's steps after its division on n values: math::sqrt, clamp to [0, 0.999],
+// * 256, truncate
+__global__ __launch_bounds__(256) void yk_film_rgb8(const double* mean, uint8_t* rgb, uint64_t n) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    double v = ykd::nsqrt(mean[i]);
+    v = (v < 0.0) ? 0.0 : (0.999 < v) ? 0.999 : v;
+    rgb[i] = (uint8_t)(uint32_t)(v * 256);
+  }
+}
+
+size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+size_t nlm_lds_bytes(uint32_t R, uint32_t F) {
+  const size_t H = R + F;
+  return (6 * (kBlockW + 2 * H) * (kBlockH + 2 * H) + 2 * (kBlockW + 2 * F) * (kBlockH + 2 * F)) * sizeof(double);
+}
+
+}  // namespace
+
+extern "C" {
+
+int yk_denoise_defaults(yk_denoise_params* out) {
+  if (!out) return yk_film_fail(YK_ERR_INVALID, "null out");
+  out->radius = 5;
+  out->patch = 1;
+  out->k2 = 0.5;
+  out->alpha = 1.0;
+  out->eps = 1e-10;
+  return YK_OK;
+}
+
+int ykgpu_film_denoise(ykgpu_film* film, const yk_denoise_params* params, double* mean_host, uint8_t* rgb_host,
+                       yk_denoise_stats* stats) {
+  const auto t0 = std::chrono::steady_clock::now();
+  yk_film_view f{};
+  if (int rc = yk_film_view_of(film, &f)) return rc;
+  yk_denoise_params dp;
+  yk_denoise_defaults(&dp);
+  if (params) dp = *params;
+  if (dp.radius > kMaxRadius) return yk_film_fail(YK_ERR_INVALID, "denoise: radius must be <= 10");
+  if (dp.patch > kMaxPatch) return yk_film_fail(YK_ERR_INVALID, "denoise: patch must be <= 3");
+  if (!(dp.k2 > 0) || !std::isfinite(dp.k2)) return yk_film_fail(YK_ERR_INVALID, "denoise: k2 must be finite and > 0");
+  if (!(dp.alpha >= 0) || !std::isfinite(dp.alpha)) return yk_film_fail(YK_ERR_INVALID, "denoise: alpha must be finite and >= 0");
+  if (!(dp.eps > 0) || !std::isfinite(dp.eps)) return yk_film_fail(YK_ERR_INVALID, "denoise: eps must be finite and > 0");
+  if (!mean_host && !rgb_host) return yk_film_fail(YK_ERR_INVALID, "denoise: mean_host and rgb_host are both null");
+  if (!f.consecutive)
+    return yk_film_fail(YK_ERR_UNSUPPORTED, "denoise: the film's tile is not consecutive image rows and columns");
+  if (!f.count && f.done < 2) return yk_film_fail(YK_ERR_INVALID, "denoise needs at least two samples in every pixel");
+
+  YKD_HIP(hipSetDevice(f.device));
+  const size_t npix = (size_t)f.rows * f.wt;
+  // the film's denoise buffers: [m, v planes: 6 npix doubles][out: 3 npix doubles][rgb: 3 npix bytes][low]
+  const size_t off_out = align256(6 * npix * sizeof(double)), off_rgb = off_out + align256(3 * npix * sizeof(double));
+  const size_t off_low = off_rgb + align256(3 * npix), bytes = off_low + 256;
+  if (!*f.scratch) YKD_HIP(hipMalloc(f.scratch, bytes));  // (a film's tile never changes size)
+  char* const base = (char*)*f.scratch;
+  double* const d_mv = (double*)base;
+  double* const d_out = (double*)(base + off_out);
+  uint8_t* const d_rgb = (uint8_t*)(base + off_rgb);
+  unsigned long long* const d_low = (unsigned long long*)(base + off_low);
+
+  // (per call: the attribute belongs to the current device)
+  YKD_HIP(hipFuncSetAttribute((const void*)yk_film_nlm, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)nlm_lds_bytes(kMaxRadius, kMaxPatch)));
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 3 && stats && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
+  const auto record = [&](int k) {
+    if (stats && e == hipSuccess) e = hipEventRecord(ev[k], f.stream);
+  };
+  unsigned long long low = 0;
+  if (e == hipSuccess) e = hipMemsetAsync(d_low, 0, sizeof low, f.stream);
+  record(0);
+  if (e == hipSuccess) {
+    const uint32_t blocks = std::max(1u, std::min((f.nps + 255) / 256, 2048u));
+    hipLaunchKernelGGL(yk_film_moments, dim3(blocks), dim3(256), 0, f.stream, f.plane, f.order, f.count, d_mv, d_low,
+                       f.nps, (uint32_t)npix, f.done);
+    e = hipGetLastError();
+  }
+  record(1);
+  // (the filter does not depend on the verdict: it is enqueued behind the moments, and its result
+  // is dropped if a count turns out to be below 2)
+  if (e == hipSuccess) {
+    NlmArgs a{};
+    a.mv = d_mv;
+    a.out = d_out;
+    a.rows = f.rows;
+    a.wt = f.wt;
+    a.npix = (uint32_t)npix;
+    a.radius = dp.radius;
+    a.patch = dp.patch;
+    a.k2 = dp.k2;
+    a.alpha = dp.alpha;
+    a.eps = dp.eps;
+    a.npatch = (double)(3 * (2 * dp.patch + 1) * (2 * dp.patch + 1));
+    const dim3 grid((f.wt + kBlockW - 1) / kBlockW, (f.rows + kBlockH - 1) / kBlockH);
+    hipLaunchKernelGGL(yk_film_nlm, grid, dim3(kThreads), nlm_lds_bytes(dp.radius, dp.patch), f.stream, a);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && rgb_host) {
+    const uint32_t blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>((3 * npix + 255) / 256, 2048));
+    hipLaunchKernelGGL(yk_film_rgb8, dim3(blocks), dim3(256), 0, f.stream, d_out, d_rgb, (uint64_t)(3 * npix));
+    e = hipGetLastError();
+  }
+  record(2);
+  if (e == hipSuccess) e = hipMemcpyAsync(&low, d_low, sizeof low, hipMemcpyDeviceToHost, f.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(f.stream);
+  // (the outputs are written only once the call is known to succeed)
+  if (e == hipSuccess && low == 0) {
+    if (mean_host) e = hipMemcpyAsync(mean_host, d_out, 3 * npix * sizeof(double), hipMemcpyDeviceToHost, f.stream);
+    if (e == hipSuccess && rgb_host) e = hipMemcpyAsync(rgb_host, d_rgb, 3 * npix, hipMemcpyDeviceToHost, f.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(f.stream);
+  }
+  float ms_m = 0, ms_f = 0;
+  if (stats && e == hipSuccess) e = hipEventElapsedTime(&ms_m, ev[0], ev[1]);
+  if (stats && e == hipSuccess) e = hipEventElapsedTime(&ms_f, ev[1], ev[2]);
+  for (hipEvent_t v : ev)
+    if (v) (void)hipEventDestroy(v);
+  if (e != hipSuccess)
+    return yk_film_fail(e == hipErrorOutOfMemory ? YK_ERR_NOMEM : YK_ERR_DEVICE,
+                        (std::string("ykgpu_film_denoise: ") + hipGetErrorString(e)).c_str());
+  if (low) return yk_film_fail(YK_ERR_INVALID, "denoise needs at least two samples in every pixel");
+  if (stats) {
+    stats->moments_ms = ms_m;
+    stats->filter_ms = ms_f;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return YK_OK;
+}
+
+}  // extern "C"

@@ -46,6 +46,7 @@
 #include "yk_bvh.hpp"
 #include "yk_device.hpp"
 #include "yk_device_f32.hpp"
+#include "yk_film_internal.hpp"
 #include "yk_stamps.hpp"
 
 using ykd::v3;
@@ -877,24 +878,8 @@ __global__ __launch_bounds__(256) void yk_reduce_samples(ReduceArgs ra) {
 // order the launches' colours arrive in, so every access of the fold below is coalesced like
 // yk_reduce_samples' — and its own copy of the slot → pixel order, so that neither the planes nor
 // their meaning depend on what the context renders between two chunks.
-// The arithmetic the host tests restate in numpy: each operation rounded on its own, never fused.
-// (the unit is built with -ffp-contract=off; the pragma says so for these four whatever the flags)
-__device__ __forceinline__ double film_add(double a, double b) {
-#pragma clang fp contract(off)
-  return __dadd_rn(a, b);
-}
-__device__ __forceinline__ double film_sub(double a, double b) {
-#pragma clang fp contract(off)
-  return __dsub_rn(a, b);
-}
-__device__ __forceinline__ double film_mul(double a, double b) {
-#pragma clang fp contract(off)
-  return __dmul_rn(a, b);
-}
-__device__ __forceinline__ double film_div(double a, double b) {
-#pragma clang fp contract(off)
-  return __ddiv_rn(a, b);
-}
+// The arithmetic the host tests restate in numpy (film_add, film_sub, film_mul, film_div: each
+// operation rounded on its own, never fused) is in yk_film_internal.hpp, shared with yk_denoise.hip.
 
 // A launch's sample colours folded into a film: s = s + c (the reference's left fold, continued
 // from the film's sums: carry-in and carry-out are the planes) and q = q + (c * c), per sample in
@@ -2886,6 +2871,8 @@ struct ykgpu_film {
   uint32_t* d_gmap = nullptr;    // ... and its slots' film slots
   unsigned long long* d_hist = nullptr;  // kFilmVals words
   uint32_t g_slots = 0;  // != 0: launch() renders the group (d_gorder, d_gmap) instead of the film's order
+  // ykgpu_film_denoise's buffers (yk_denoise.hip), allocated at the film's first denoise
+  void* d_denoise = nullptr;
   bool uniform() const { return hist.size() <= 1; }
 };
 
@@ -4440,7 +4427,7 @@ int ykgpu_film_destroy(ykgpu_film* film) {
   (void)hipFree(film->d_order);
   (void)hipFree(film->d_result);
   for (void* q : {(void*)film->d_count, (void*)film->d_take, (void*)film->d_blocks, (void*)film->d_gorder,
-                  (void*)film->d_gmap, (void*)film->d_hist})
+                  (void*)film->d_gmap, (void*)film->d_hist, film->d_denoise})
     (void)hipFree(q);
   delete film;
   return YK_OK;
@@ -4909,4 +4896,26 @@ int ykgpu_render_devices(const int* devices, uint32_t n_devices, const yk_sphere
 }
 
 }  // extern "C"
+
+// ---- film denoise (yk_denoise.hip): that unit's view of a film, and this unit's error slot ------
+int yk_film_fail(int code, const char* msg) { return fail(code, msg); }
+
+int yk_film_view_of(ykgpu_film* film, yk_film_view* out) {
+  if (int rc = film_ready(film)) return rc;
+  const yk_render_params& p = film->p;
+  out->device = film->device;
+  out->stream = film->ctx->stream;
+  out->plane = film->d_plane;
+  out->order = film->d_order;
+  out->count = film->uniform() ? nullptr : film->d_count;
+  out->nps = film->nps;
+  out->done = film->done;
+  out->rows = p.row_count;
+  out->wt = tile_width(&p);
+  // (both maps increase strictly, so the last entry tells whether any step was larger than one)
+  out->consecutive = host_row_y(&p, p.row_count - 1) == (uint64_t)p.row_begin + p.row_count - 1 &&
+                     host_col_x(&p, out->wt - 1) == (uint64_t)p.col_begin + out->wt - 1;
+  out->scratch = &film->d_denoise;
+  return YK_OK;
+}
 #endif  // YK_SPLIT != 2

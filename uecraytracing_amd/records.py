@@ -164,7 +164,35 @@ class FilmPass(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class DenoiseParams(ctypes.Structure):
+    """yk_denoise_params (include/ykgpu.h): the non-local-means filter's window, patch and scales."""
+    _fields_ = [
+        ("radius", ctypes.c_uint32),  # R, 0..10
+        ("patch", ctypes.c_uint32),  # F, 0..3
+        ("k2", ctypes.c_double),
+        ("alpha", ctypes.c_double),
+        ("eps", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class DenoiseStats(ctypes.Structure):
+    """yk_denoise_stats (include/ykgpu.h): where one ykgpu_film_denoise call spent its time."""
+    _fields_ = [
+        ("moments_ms", ctypes.c_double),
+        ("filter_ms", ctypes.c_double),
+        ("total_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 assert ctypes.sizeof(Sphere) == 80
+assert ctypes.sizeof(DenoiseParams) == 32
+assert ctypes.sizeof(DenoiseStats) == 24
 assert ctypes.sizeof(FilmPass) == 32
 assert ctypes.sizeof(FilmStats) == 32
 assert ctypes.sizeof(Camera) == 19 * 8
