@@ -286,6 +286,20 @@ class film {
     check(ykgpu_film_denoise(f_, &dp, nullptr, img.data(), stats), "ykgpu_film_denoise");
     return img;
   }
+  // the first-hit albedo, normal and depth of the tile (include/ykgpu.h "film features"): 7 doubles
+  // per pixel, pixel order; computed once per (film, grid)
+  std::vector<double> features(uint32_t grid) {
+    std::vector<double> mean(pixels() * 7);
+    check(ykgpu_film_features(f_, grid, mean.data(), nullptr, nullptr), "ykgpu_film_features");
+    return mean;
+  }
+  // the RGB8 image of the filter guided by those features; the same preconditions as denoise()
+  std::vector<uint8_t> denoise_guided(const yk_denoise_params& dp, const yk_feature_params& fp,
+                                      yk_guided_stats* stats = nullptr) {
+    std::vector<uint8_t> img(pixels() * 3);
+    check(ykgpu_film_denoise_guided(f_, &dp, &fp, nullptr, img.data(), stats), "ykgpu_film_denoise_guided");
+    return img;
+  }
   yk_film_stats error_stats(double threshold2) {
     yk_film_stats st;
     check(ykgpu_film_error(f_, threshold2, nullptr, &st), "ykgpu_film_error");

@@ -492,6 +492,90 @@ int yk_denoise_defaults(yk_denoise_params* out);
 int ykgpu_film_denoise(ykgpu_film* film, const yk_denoise_params* params, double* mean_host, uint8_t* rgb_host,
                        yk_denoise_stats* stats);
 
+/* ---- film features: first-hit albedo, normal and depth, and a filter guided by them ----------
+ * (Added under ABI 11 like the film: nothing that existed changed size or meaning.)
+ *
+ * The feature pass makes seven channels per pixel of the film's tile from the scene and camera the
+ * film was created with.  It is deterministic and draws no random numbers.  For image pixel (x, y)
+ * (the tile's row and column sets map tile to image exactly as the render does) and a grid g in 1..4,
+ * the sub-rays (i, j) run row-major, i = 0..g-1 outside and j inside:
+ *   a = ((double)j + 0.5) / (double)g          b = ((double)i + 0.5) / (double)g
+ *   u = ((double)x + a) / (double)W            v = ((double)(H - y - 1) + b) / (double)H
+ *   o = origin,  d = ((lower_left_corner + horizontal*u) + vertical*v) - origin
+ * That is the camera's pinhole ray: THE LENS IS IGNORED even when lens_radius > 0, so the features
+ * are sharp where the colour is defocused (a guided filter keeps edges the defocus has blurred).
+ * The closest hit is the reference's ordered scan over the spheres in tuple order, always in
+ * double whatever the film's precision (features are guides, not the reference's arithmetic), with
+ * t_min = params.t_min and t_max = +inf.  Per sphere (centre c, radius r), closest = t_max at first:
+ *   oc = o - c;  a = (d.x*d.x + d.y*d.y) + d.z*d.z;  half_b = (oc.x*d.x + oc.y*d.y) + oc.z*d.z
+ *   cc = ((oc.x*oc.x + oc.y*oc.y) + oc.z*oc.z) - r*r;  disc = half_b*half_b - a*cc;  disc < 0: no hit
+ *   sq = math::sqrt(disc);  root = (-half_b - sq) / a
+ *   if (root < t_min || closest < root) { root = (-half_b + sq) / a;  the same test: no hit }
+ *   closest = root, the sphere is the hit (so of equal roots the later index wins)
+ * and of the last accepted sphere k:  p = o + d*t,  outward = (p - c) / r,
+ * normal = dot(d, outward) < 0 ? outward : -outward.  The channels of a sub-ray:
+ *   f0..f2  the sphere's albedo (lambertian, metal) or (1, 1, 1) (dielectric);  a miss: (1, 1, 1)
+ *   f3..f5  normal;                                                             a miss: (0, 0, 0)
+ *   f6      t;                                                                  a miss: 0
+ * Per channel, left folds over the sub-rays: s = s + f, q = q + (f*f).  With G = (double)(g*g):
+ *   F = s / G                                                     the mean
+ *   U = max(0, (q - (s*s)/G) / (G*(G - 1)))   (g = 1: U = 0)      the variance of the mean
+ * Every + - * / is one IEEE double operation, rounded on its own and never fused, in that order.
+ *
+ * ykgpu_film_features computes the pass once per (film, grid) into planes the film owns (17 doubles
+ * per pixel: F, U and three sums of U; allocated at first use, freed with the film; a later call
+ * with the same grid reuses them and reports ms = 0, another grid replaces them) and copies out
+ *   mean_host, var_host   row_count * Wt * 7 doubles each, pixel order (either may be NULL; both
+ *                         NULL: compute and cache only);  ms may be NULL.
+ * It works on any tile, strided ones included, and changes nothing of the film's state.
+ *   YK_ERR_INVALID   grid outside 1..4; the context's scene was set after the film was created
+ *
+ * The guided filter is "film denoise" above with the weight w = min(wf, wc): wc is exactly that
+ * section's w for the given yk_denoise_params, and for the same window offset and in-tile neighbour
+ * q the feature weight is pointwise (no patch), over the groups A = channels 0..2, N = 3..5, Z = 6:
+ *   V_k(x) = U(x) summed over the group's channels, left to right
+ *   E_k    = (dF*dF) summed over the group's channels, left to right,   dF = F(p) - F(q)
+ *   Phi_k  = (E_k - alpha_f*(V_k(p) + min(V_k(q), V_k(p)))) / (tau_k + k2_f*(V_k(p) + V_k(q)))
+ *   DF     = max(max(max(0, Phi_A), Phi_N), Phi_Z)                 (x > y ? x : y; min: q < p ? q : p)
+ *   tf = 1 - 0.25*DF;  tf = tf > 0 ? tf : 0;  wf = (tf*tf)*(tf*tf)
+ *   w  = wf < wc ? wf : wc
+ * then acc_c = acc_c + (w * m_c(q)), wsum = wsum + w and out_c = acc_c / wsum as before.  The centre
+ * has Phi <= 0, so wf = 1 and wsum >= 1.  tau_k = +inf switches a group off; with all three infinite
+ * the result is ykgpu_film_denoise's bit for bit.  ykgpu_film_denoise_guided is synchronous and only
+ * reads the film; it computes the feature pass at feat->grid first unless the film holds it.
+ * Errors, with nothing written to mean_host / rgb_host / stats:
+ *   YK_ERR_INVALID      a colour parameter out of "film denoise"'s ranges; grid outside 1..4,
+ *                       reserved != 0, k2_f <= 0 or not finite, alpha_f < 0 or not finite, a tau <= 0
+ *                       or NaN; a stale scene; any pixel's count below 2; both outputs NULL
+ *   YK_ERR_UNSUPPORTED  the tile is not consecutive image rows and consecutive image columns
+ *
+ * raytrace --aov writes F as three PNGs, each step one IEEE double operation:
+ *   albedo  trunc(clamp(F_c, 0, 0.999) * 256), c = 0..2
+ *   normal  trunc(clamp(0.5*F_c + 0.5, 0, 0.999) * 256), c = 3..5
+ *   depth   trunc(clamp(F_6 / (1 + F_6), 0, 0.999) * 256), grey */
+typedef struct yk_feature_params { /* 48 bytes */
+  uint32_t grid;                   /* g, 1..4                                        */
+  uint32_t reserved;               /* 0                                              */
+  double k2, alpha;                /* k2_f > 0, alpha_f >= 0                         */
+  double tau_albedo, tau_normal, tau_depth; /* > 0, +inf allowed                     */
+} yk_feature_params;
+
+typedef struct yk_guided_stats {   /* 32 bytes */
+  double features_ms;              /* the feature pass (device); 0 when the cached pass was reused */
+  double moments_ms;               /* the gather of m and v (device)                 */
+  double filter_ms;                /* the filter and the RGB8 conversion (device)    */
+  double total_ms;                 /* the call's host wall clock, copies included    */
+} yk_guided_stats;
+
+/* The pair tuned together (host only): colour radius 5, patch 1, k2 2.0, alpha 1.0,
+ * eps 1e-10; features grid 2, k2 2.0, alpha 1.0, tau_albedo 1e-2, tau_normal 1e-1, tau_depth 1e-2.
+ * Either pointer may be NULL, not both. */
+int yk_guided_defaults(yk_denoise_params* colour, yk_feature_params* feat);
+int ykgpu_film_features(ykgpu_film* film, uint32_t grid, double* mean_host, double* var_host, double* ms);
+/* colour / feat NULL: that side of yk_guided_defaults.  Outputs as ykgpu_film_denoise's. */
+int ykgpu_film_denoise_guided(ykgpu_film* film, const yk_denoise_params* colour, const yk_feature_params* feat,
+                              double* mean_host, uint8_t* rgb_host, yk_guided_stats* stats);
+
 /* ---- host-side scene helpers (no device needed) ---------------------------------------- */
 
 /* camera<double>{} of camera.hpp:16-27 (16:9, viewport height 2, focal length 1, origin 0). */

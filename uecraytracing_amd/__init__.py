@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 from . import records
-from .records import Camera, DenoiseParams, DenoiseStats, FilmPass, FilmStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
+from .records import Camera, DenoiseParams, DenoiseStats, FeatureParams, FilmPass, GuidedStats, FilmStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(PKG_DIR, "lib")
@@ -37,6 +37,7 @@ EXPORTS = (
     "ykgpu_film_accumulate_adaptive", "ykgpu_film_counts", "ykgpu_film_write_counts",
     "yk_film_save_counts", "yk_film_load_counts",
     "yk_denoise_defaults", "ykgpu_film_denoise",
+    "yk_guided_defaults", "ykgpu_film_features", "ykgpu_film_denoise_guided",
 )
 ABI_VERSION = 11
 SCENE_DIR = os.path.join(PKG_DIR, "scenes")  # committed scene files of the BASELINE configs
@@ -120,6 +121,10 @@ def load_library():
                                  c.c_void_p, c.c_uint64], c.c_int),
         "yk_denoise_defaults": ([P(DenoiseParams)], c.c_int),
         "ykgpu_film_denoise": ([c.c_void_p, P(DenoiseParams), c.c_void_p, c.c_void_p, P(DenoiseStats)], c.c_int),
+        "yk_guided_defaults": ([P(DenoiseParams), P(FeatureParams)], c.c_int),
+        "ykgpu_film_features": ([c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, P(c.c_double)], c.c_int),
+        "ykgpu_film_denoise_guided": ([c.c_void_p, P(DenoiseParams), P(FeatureParams), c.c_void_p, c.c_void_p,
+                                       P(GuidedStats)], c.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
@@ -248,6 +253,14 @@ def denoise_defaults() -> DenoiseParams:
     return dp
 
 
+def guided_defaults():
+    """yk_guided_defaults (host only): the (DenoiseParams, FeatureParams) pair tuned together
+    (DESIGN.md §6.4)."""
+    dp, fp = DenoiseParams(), FeatureParams()
+    _check(load_library().yk_guided_defaults(ctypes.byref(dp), ctypes.byref(fp)))
+    return dp, fp
+
+
 class Film:
     """A progressive film (ykgpu_film, include/ykgpu.h): the resumable accumulation state of one
     tile.  Made by Renderer.film(params); any chunking of the samples yields the one-shot render's
@@ -364,6 +377,31 @@ class Film:
         dp, st = DenoiseParams(radius, patch, k2, alpha, eps), DenoiseStats()
         _check(self._lib.ykgpu_film_denoise(self._f, ctypes.byref(dp), mean.ctypes.data if want_mean else None,
                                             rgb.ctypes.data if want_rgb else None, ctypes.byref(st)))
+        return mean, rgb, st.as_dict()
+
+    def features(self, grid: int = 2):
+        """(mean float64[row_count, tile width, 7], var float64[row_count, tile width, 7], ms): the
+        first-hit albedo (0..2), normal (3..5) and depth (6) of include/ykgpu.h "film features" on
+        the film's tile, and the variances of those means over the grid x grid sub-rays.  Computed
+        once per (film, grid): ms is 0 when the film's cached pass was reused."""
+        mean = np.empty(self._shape + (7,), np.float64)
+        var = np.empty(self._shape + (7,), np.float64)
+        ms = ctypes.c_double(0.0)
+        _check(self._lib.ykgpu_film_features(self._f, grid, mean.ctypes.data, var.ctypes.data, ctypes.byref(ms)))
+        return mean, var, ms.value
+
+    def denoise_guided(self, colour: DenoiseParams = None, feat: FeatureParams = None, want_mean: bool = True,
+                       want_rgb: bool = True):
+        """(mean | None, rgb | None, stats dict) like denoise(): the filter of include/ykgpu.h "film
+        features", its weight bounded by the feature planes' distance.  colour / feat None: that side
+        of guided_defaults()."""
+        mean = np.empty(self._shape + (3,), np.float64) if want_mean else None
+        rgb = np.empty(self._shape + (3,), np.uint8) if want_rgb else None
+        st = GuidedStats()
+        _check(self._lib.ykgpu_film_denoise_guided(
+            self._f, ctypes.byref(colour) if colour is not None else None,
+            ctypes.byref(feat) if feat is not None else None, mean.ctypes.data if want_mean else None,
+            rgb.ctypes.data if want_rgb else None, ctypes.byref(st)))
         return mean, rgb, st.as_dict()
 
     def render_until(self, threshold: float, chunk: int) -> dict:
@@ -567,5 +605,5 @@ def render_devices(devices, spheres, camera: Camera, params: RenderParams) -> np
     return out
 
 
-__all__ = ["Renderer", "Film", "FilmPass", "DenoiseParams", "DenoiseStats", "denoise_defaults", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
+__all__ = ["Renderer", "Film", "FilmPass", "DenoiseParams", "DenoiseStats", "denoise_defaults", "FeatureParams", "GuidedStats", "guided_defaults", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
            "make_params", "load_library", "records", "EXPORTS", "LIB_PATH", "CLI_PATH"]

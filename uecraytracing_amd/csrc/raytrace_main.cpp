@@ -21,7 +21,9 @@
 // --device, --stats, the progressive film's --progressive, --until, --checkpoint, --stop-after
 // (include/ykgpu.h "progressive film": the image in chunks of samples, the same bytes as in one
 // call), and --denoise with --denoise-radius, --denoise-patch, --denoise-k2 (include/ykgpu.h "film
-// denoise": the final image and every preview through the film's variance-guided filter).  --seed0 fixes the per-sample seed base (seed0 + (y*W+x)*spp + s, the constexpr
+// denoise": the final image and every preview through the film's variance-guided filter),
+// --denoise-features, --feature-grid and --aov (include/ykgpu.h "film features": the filter guided
+// by first-hit albedo, normal and depth, and those three as images).  --seed0 fixes the per-sample seed base (seed0 + (y*W+x)*spp + s, the constexpr
 // build's formula, source.cpp:154-158); without it every sample gets its own seed from a
 // per-call std::random_device key (YK_SEED_RANDOM_DEVICE), like the reference's runtime build
 // (source.cpp:159).  --precision fp32 renders render<float> (T = float, source.cpp:98);
@@ -96,7 +98,15 @@ const char* kHelp =
     "                            of the raw mean; needs at least 2 samples per pixel\n"
     "      --denoise-radius arg  the filter's window radius, 0..10 (default: 5)\n"
     "      --denoise-patch arg   the filter's patch radius, 0..3 (default: 1)\n"
-    "      --denoise-k2 arg      the filter's variance scale, > 0 (default: 0.5)\n";
+    "      --denoise-k2 arg      the filter's variance scale, > 0 (default: 0.5)\n"
+    "      --denoise-features    --denoise with the filter's weight bounded by first-hit albedo,\n"
+    "                            normal and depth (pinhole rays: sharp where a lens defocuses),\n"
+    "                            at the pair of defaults tuned together (k2 2, grid 2); the\n"
+    "                            --denoise-* options still set the colour side\n"
+    "      --feature-grid arg    sub-rays per pixel side of the feature pass, 1..4 (default: 2)\n"
+    "      --aov arg             also write the feature means F as arg.albedo.png, arg.normal.png\n"
+    "                            and arg.depth.png: trunc(clamp(x, 0, 0.999) * 256) of F0..F2, of\n"
+    "                            0.5 * F + 0.5 for F3..F5, and of F6 / (1 + F6) (grey: r = g = b)\n";
 
 struct args {
   bool help = false, verbose_flag = false, stats = false;
@@ -120,7 +130,11 @@ struct args {
   // the film's denoise filter (the options other than --denoise only set its parameters)
   bool denoise = false, have_denoise_params = false;
   yk_denoise_params dn{};
-  bool film() const { return denoise || adaptive || have_progressive || have_until || have_stop_after || !checkpoint.empty(); }
+  // the guided filter and the feature images (--feature-grid alone sets the grid of either)
+  bool denoise_features = false, have_feature_grid = false;
+  yk_feature_params fp{};
+  std::string aov;
+  bool film() const { return denoise || !aov.empty() || adaptive || have_progressive || have_until || have_stop_after || !checkpoint.empty(); }
 };
 
 uint32_t to_u32(const std::string& opt, const std::string& v) {
@@ -154,6 +168,8 @@ uint32_t to_count(const std::string& opt, const std::string& v) {
 args parse(int argc, char** argv) {
   args a;
   yk_denoise_defaults(&a.dn);
+  yk_guided_defaults(nullptr, &a.fp);
+  bool have_k2 = false;
   int positional = 0;
   auto value = [&](int& i, const std::string& name, const std::string& inl) -> std::string {
     if (!inl.empty()) return inl;
@@ -200,7 +216,13 @@ args parse(int argc, char** argv) {
       else if (n == "denoise") { a.denoise = true; }
       else if (n == "denoise-radius") { a.dn.radius = to_u32(n, value(i, n, inl)); a.have_denoise_params = true; }
       else if (n == "denoise-patch") { a.dn.patch = to_u32(n, value(i, n, inl)); a.have_denoise_params = true; }
-      else if (n == "denoise-k2") { a.dn.k2 = to_positive(n, value(i, n, inl)); a.have_denoise_params = true; }
+      else if (n == "denoise-k2") { a.dn.k2 = to_positive(n, value(i, n, inl)); a.have_denoise_params = true; have_k2 = true; }
+      else if (n == "denoise-features") { a.denoise = a.denoise_features = true; }
+      else if (n == "feature-grid") { a.fp.grid = to_u32(n, value(i, n, inl)); a.have_feature_grid = true; }
+      else if (n == "aov") {
+        a.aov = value(i, n, inl);
+        if (a.aov.empty()) throw option_error{"Option 'aov' needs a file name prefix"};
+      }
       else if (n == "checkpoint") {
         a.checkpoint = value(i, n, inl);
         if (a.checkpoint.empty()) throw option_error{"Option 'checkpoint' needs a file name"};
@@ -228,6 +250,14 @@ args parse(int argc, char** argv) {
   }
   if (a.adaptive && !a.have_until) throw option_error{"Option 'adaptive' needs --until"};
   if (a.have_denoise_params && !a.denoise) throw option_error{"The denoise parameters need --denoise"};
+  if (a.have_feature_grid && !a.denoise_features && a.aov.empty())
+    throw option_error{"Option 'feature-grid' needs --denoise-features or --aov"};
+  if (a.fp.grid < 1 || a.fp.grid > 4) throw option_error{"Option 'feature-grid' must be 1..4"};
+  if (a.denoise_features && !have_k2) {  // the colour side of the pair, unless the option set it
+    yk_denoise_params pair;
+    yk_guided_defaults(&pair, nullptr);
+    a.dn.k2 = pair.k2;
+  }
   if (a.dn.radius > 10) throw option_error{"Option 'denoise-radius' must be at most 10"};
   if (a.dn.patch > 3) throw option_error{"Option 'denoise-patch' must be at most 3"};
   return a;
@@ -352,7 +382,8 @@ int main(int argc, char* argv[]) {
       // of a film that still has a pixel below two samples stays the raw mean; the final image
       // does not: the filter's error is the run's)
       auto picture = [&](bool preview) {
-        return a.denoise && !(preview && film.count_range().first < 2) ? film.denoise(a.dn) : film.resolve();
+        if (!a.denoise || (preview && film.count_range().first < 2)) return film.resolve();
+        return a.denoise_features ? film.denoise_guided(a.dn, a.fp) : film.denoise(a.dn);
       };
       uint32_t chunks = 0;
       if (a.adaptive) {
@@ -398,6 +429,28 @@ int main(int argc, char* argv[]) {
           std::cout << "stopped at " << film.done() << " of " << a.spp << " samples" << std::endl;
       }
       st.seed_key = film.params().seed_key;
+      if (!a.aov.empty()) {
+        // the feature means as images (include/ykgpu.h "film features"): one operation per step
+        const std::vector<double> F = film.features(a.fp.grid);
+        const auto enc = [](double x) {
+          x = (x < 0.0) ? 0.0 : (0.999 < x) ? 0.999 : x;
+          return (uint8_t)(uint32_t)(x * 256);
+        };
+        std::vector<uint8_t> albedo((size_t)W * H * 3), normal(albedo.size()), depth(albedo.size());
+        for (size_t px = 0; px < (size_t)W * H; ++px) {
+          const double* f = &F[px * 7];
+          for (int c = 0; c < 3; ++c) {
+            albedo[px * 3 + c] = enc(f[c]);
+            normal[px * 3 + c] = enc(0.5 * f[3 + c] + 0.5);
+            depth[px * 3 + c] = enc(f[6] / (1.0 + f[6]));
+          }
+        }
+        for (const auto& [name, img] : {std::pair<const char*, const std::vector<uint8_t>*>{"albedo", &albedo},
+                                        {"normal", &normal}, {"depth", &depth}}) {
+          const std::string path = a.aov + "." + name + ".png";
+          if (!ykpng::write_rgb(path.c_str(), W, H, img->data())) throw ykgpu::error(YK_ERR_INVALID, "cannot write " + path);
+        }
+      }
     }
     if (verbose) {
       ykgpu::render_options vo = ro;

@@ -8,12 +8,15 @@
 //   yk_film_nlm      the filter, one workgroup per 32 x 8 pixels, m and v of the block and its
 //                    halo in LDS
 //   yk_film_rgb8     to_color3b's steps after its division on the filtered mean
+// and, for ykgpu_film_denoise_guided ("film features"), yk_film_nlm_guided in
+// yk_film_nlm's place: the same filter with the weight bounded by the feature planes' distance.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
+#include <initializer_list>
 #include <string>
 
 #include "../../include/ykgpu.h"
@@ -168,6 +171,132 @@ __global__ __launch_bounds__(kThreads) void yk_film_nlm(NlmArgs a) {
   }
 }
 
+struct GuidedArgs {
+  NlmArgs c;           // the colour side, exactly yk_film_nlm's
+  const double* feat;  // kYkFeatPlanes planes of npix doubles (yk_features.hip)
+  double k2, alpha, tau[3];
+};
+
+// yk_film_nlm with w = min(wf, wc) (include/ykgpu.h "film features"): the colour weight wc is
+// computed by the same statements in the same order; the feature weight is pointwise, between p and
+// q = p + d.  The feature planes stay in global memory: the ten planes the weight reads (F0..F6, V_A,
+// V_N, V_Z) grown by R would take 60 KiB of LDS beside the colour planes' 46.6 KiB at the defaults,
+// and at R = 10, F = 3 the colour planes alone take 101 KiB of the CU's 160 KiB, so one layout that
+// holds for every (R, F) reads them through L2: at a fixed offset the 32 lanes of a row read 32
+// consecutive doubles of each plane, and neighbouring offsets read the same lines again.  A thread
+// keeps its own pixel's ten values in registers.  Where wc is 0 the weight is 0 whatever wf is
+// (wf >= 0 is never below it), so those neighbours' planes are not read.
+__global__ __launch_bounds__(kThreads) void yk_film_nlm_guided(GuidedArgs ga) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const NlmArgs& a = ga.c;
+  const int R = (int)a.radius, F = (int)a.patch, H = R + F;
+  const int pw = (int)kBlockW + 2 * H, ph = (int)kBlockH + 2 * H;  // the six m / v planes
+  const int tw = (int)kBlockW + 2 * F, th = (int)kBlockH + 2 * F;  // the term planes
+  const int plane = pw * ph;
+  double* const term = lds + 6 * plane;
+  const int rows = (int)a.rows, wt = (int)a.wt;
+  const int x0 = (int)(blockIdx.x * kBlockW), y0 = (int)(blockIdx.y * kBlockH);
+  const int tid = (int)threadIdx.x;
+
+  for (int i = tid; i < plane; i += (int)kThreads) {
+    const int ly = i / pw, lx = i - ly * pw;
+    int gy = y0 - H + ly, gx = x0 - H + lx;
+    gy = gy < 0 ? 0 : gy > rows - 1 ? rows - 1 : gy;
+    gx = gx < 0 ? 0 : gx > wt - 1 ? wt - 1 : gx;
+    const size_t g = (size_t)gy * a.wt + gx;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) lds[c * plane + i] = a.mv[(size_t)c * a.npix + g];
+  }
+  __syncthreads();
+
+  const int tx = tid & (int)(kBlockW - 1), ty = tid / (int)kBlockW;
+  const int py = y0 + ty, px = x0 + tx;
+  const bool mine = py < rows && px < wt;
+  const int by1 = (y0 + (int)kBlockH < rows ? y0 + (int)kBlockH : rows) - 1;
+  const int bx1 = (x0 + (int)kBlockW < wt ? x0 + (int)kBlockW : wt) - 1;
+  // this pixel's features: F0..F6 and the three group variances (planes 14..16)
+  double fp[kYkFeatChannels], vp[3];
+  {
+    const size_t g = mine ? (size_t)py * a.wt + px : 0;
+#pragma unroll
+    for (uint32_t c = 0; c < kYkFeatChannels; ++c) fp[c] = ga.feat[(size_t)c * a.npix + g];
+#pragma unroll
+    for (uint32_t k = 0; k < 3; ++k) vp[k] = ga.feat[(size_t)(14 + k) * a.npix + g];
+  }
+  double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, wsum = 0.0;
+  int buf = 0;
+  for (int dy = -R; dy <= R; ++dy) {
+    if (by1 + dy < 0 || y0 + dy > rows - 1) continue;  // (uniform over the workgroup)
+    for (int dx = -R; dx <= R; ++dx) {
+      if (bx1 + dx < 0 || x0 + dx > wt - 1) continue;  // (uniform over the workgroup)
+      double* const t = term + buf * (tw * th);
+      for (int i = tid; i < tw * th; i += (int)kThreads) {
+        const int uy = i / tw, ux = i - uy * tw;
+        const int ip = (uy + R) * pw + (ux + R);
+        const int iq = ip + dy * pw + dx;
+        double s3[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const double mp = lds[c * plane + ip], mq = lds[c * plane + iq];
+          const double vpc = lds[(3 + c) * plane + ip], vq = lds[(3 + c) * plane + iq];
+          const double d = film_sub(mp, mq);
+          const double num = film_sub(film_mul(d, d), film_mul(a.alpha, film_add(vpc, vq < vpc ? vq : vpc)));
+          const double den = film_add(a.eps, film_mul(a.k2, film_add(vpc, vq)));
+          s3[c] = film_div(num, den);
+        }
+        t[i] = film_add(film_add(s3[0], s3[1]), s3[2]);
+      }
+      __syncthreads();
+      if (mine && py + dy >= 0 && py + dy < rows && px + dx >= 0 && px + dx < wt) {
+        double S = 0.0;
+        for (int oy = 0; oy <= 2 * F; ++oy)
+          for (int ox = 0; ox <= 2 * F; ++ox) S = film_add(S, t[(ty + oy) * tw + tx + ox]);
+        double D = film_div(S, a.npatch);
+        D = D > 0.0 ? D : 0.0;
+        double wc = film_sub(1.0, film_mul(0.25, D));
+        wc = wc > 0.0 ? wc : 0.0;
+        wc = film_mul(film_mul(wc, wc), film_mul(wc, wc));
+        double w = wc;
+        if (wc > 0.0) {
+          const size_t gq = (size_t)(py + dy) * a.wt + (size_t)(px + dx);
+          double e[kYkFeatChannels];
+#pragma unroll
+          for (uint32_t c = 0; c < kYkFeatChannels; ++c) {
+            const double dF = film_sub(fp[c], ga.feat[(size_t)c * a.npix + gq]);
+            e[c] = film_mul(dF, dF);
+          }
+          const double E[3] = {film_add(film_add(e[0], e[1]), e[2]), film_add(film_add(e[3], e[4]), e[5]), e[6]};
+          double DF = 0.0;
+#pragma unroll
+          for (uint32_t k = 0; k < 3; ++k) {
+            const double vq = ga.feat[(size_t)(14 + k) * a.npix + gq];
+            const double num = film_sub(E[k], film_mul(ga.alpha, film_add(vp[k], vq < vp[k] ? vq : vp[k])));
+            const double den = film_add(ga.tau[k], film_mul(ga.k2, film_add(vp[k], vq)));
+            const double phi = film_div(num, den);
+            DF = DF > phi ? DF : phi;
+          }
+          double wf = film_sub(1.0, film_mul(0.25, DF));
+          wf = wf > 0.0 ? wf : 0.0;
+          wf = film_mul(film_mul(wf, wf), film_mul(wf, wf));
+          w = wf < wc ? wf : wc;
+        }
+        const int iq = (ty + H + dy) * pw + tx + H + dx;
+        acc0 = film_add(acc0, film_mul(w, lds[iq]));
+        acc1 = film_add(acc1, film_mul(w, lds[plane + iq]));
+        acc2 = film_add(acc2, film_mul(w, lds[2 * plane + iq]));
+        wsum = film_add(wsum, w);
+      }
+      buf ^= 1;
+    }
+  }
+  if (mine) {
+    double* o = a.out + ((size_t)py * a.wt + px) * 3;
+    o[0] = film_div(acc0, wsum);
+    o[1] = film_div(acc1, wsum);
+    o[2] = film_div(acc2, wsum);
+  }
+}
+
 // ykgpu_film_resolve's steps after its division on n values: math::sqrt, clamp to [0, 0.999],
 // * 256, truncate
 __global__ __launch_bounds__(256) void yk_film_rgb8(const double* mean, uint8_t* rgb, uint64_t n) {
@@ -291,6 +420,139 @@ int ykgpu_film_denoise(ykgpu_film* film, const yk_denoise_params* params, double
                         (std::string("ykgpu_film_denoise: ") + hipGetErrorString(e)).c_str());
   if (low) return yk_film_fail(YK_ERR_INVALID, "denoise needs at least two samples in every pixel");
   if (stats) {
+    stats->moments_ms = ms_m;
+    stats->filter_ms = ms_f;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return YK_OK;
+}
+
+int yk_guided_defaults(yk_denoise_params* colour, yk_feature_params* feat) {
+  if (!colour && !feat) return yk_film_fail(YK_ERR_INVALID, "null out");
+  if (colour) {
+    yk_denoise_defaults(colour);
+    colour->k2 = 2.0;  // the pair of DESIGN.md §6.4 (tools/features_tune.py)
+  }
+  if (feat) {
+    feat->grid = 2;
+    feat->reserved = 0;
+    feat->k2 = 2.0;
+    feat->alpha = 1.0;
+    feat->tau_albedo = 1e-2;
+    feat->tau_normal = 1e-1;
+    feat->tau_depth = 1e-2;
+  }
+  return YK_OK;
+}
+
+int ykgpu_film_denoise_guided(ykgpu_film* film, const yk_denoise_params* params, const yk_feature_params* fparams,
+                              double* mean_host, uint8_t* rgb_host, yk_guided_stats* stats) {
+  const auto t0 = std::chrono::steady_clock::now();
+  yk_film_view f{};
+  if (int rc = yk_film_view_of(film, &f)) return rc;
+  yk_denoise_params dp;
+  yk_feature_params fp;
+  yk_guided_defaults(&dp, &fp);
+  if (params) dp = *params;
+  if (fparams) fp = *fparams;
+  if (dp.radius > kMaxRadius) return yk_film_fail(YK_ERR_INVALID, "denoise: radius must be <= 10");
+  if (dp.patch > kMaxPatch) return yk_film_fail(YK_ERR_INVALID, "denoise: patch must be <= 3");
+  if (!(dp.k2 > 0) || !std::isfinite(dp.k2)) return yk_film_fail(YK_ERR_INVALID, "denoise: k2 must be finite and > 0");
+  if (!(dp.alpha >= 0) || !std::isfinite(dp.alpha)) return yk_film_fail(YK_ERR_INVALID, "denoise: alpha must be finite and >= 0");
+  if (!(dp.eps > 0) || !std::isfinite(dp.eps)) return yk_film_fail(YK_ERR_INVALID, "denoise: eps must be finite and > 0");
+  if (fp.grid < 1 || fp.grid > 4) return yk_film_fail(YK_ERR_INVALID, "features: grid must be 1..4");
+  if (fp.reserved) return yk_film_fail(YK_ERR_INVALID, "features: reserved must be 0");
+  if (!(fp.k2 > 0) || !std::isfinite(fp.k2)) return yk_film_fail(YK_ERR_INVALID, "features: k2 must be finite and > 0");
+  if (!(fp.alpha >= 0) || !std::isfinite(fp.alpha)) return yk_film_fail(YK_ERR_INVALID, "features: alpha must be finite and >= 0");
+  for (double tau : {fp.tau_albedo, fp.tau_normal, fp.tau_depth})
+    if (!(tau > 0)) return yk_film_fail(YK_ERR_INVALID, "features: tau must be > 0 (+inf switches a group off)");
+  if (f.stale) return yk_film_fail(YK_ERR_INVALID, "the context's scene was set after the film was created");
+  if (!mean_host && !rgb_host) return yk_film_fail(YK_ERR_INVALID, "denoise: mean_host and rgb_host are both null");
+  if (!f.consecutive)
+    return yk_film_fail(YK_ERR_UNSUPPORTED, "denoise: the film's tile is not consecutive image rows and columns");
+  if (!f.count && f.done < 2) return yk_film_fail(YK_ERR_INVALID, "denoise needs at least two samples in every pixel");
+
+  const double* d_feat = nullptr;
+  double ms_feat = 0;
+  if (int rc = yk_film_features_ensure(f, fp.grid, &d_feat, &ms_feat)) return rc;
+  const size_t npix = (size_t)f.rows * f.wt;
+  // the film's denoise buffers, ykgpu_film_denoise's
+  const size_t off_out = align256(6 * npix * sizeof(double)), off_rgb = off_out + align256(3 * npix * sizeof(double));
+  const size_t off_low = off_rgb + align256(3 * npix), bytes = off_low + 256;
+  if (!*f.scratch) YKD_HIP(hipMalloc(f.scratch, bytes));
+  char* const base = (char*)*f.scratch;
+  double* const d_mv = (double*)base;
+  double* const d_out = (double*)(base + off_out);
+  uint8_t* const d_rgb = (uint8_t*)(base + off_rgb);
+  unsigned long long* const d_low = (unsigned long long*)(base + off_low);
+
+  YKD_HIP(hipFuncSetAttribute((const void*)yk_film_nlm_guided, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)nlm_lds_bytes(kMaxRadius, kMaxPatch)));
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 3 && stats && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
+  const auto record = [&](int k) {
+    if (stats && e == hipSuccess) e = hipEventRecord(ev[k], f.stream);
+  };
+  unsigned long long low = 0;
+  if (e == hipSuccess) e = hipMemsetAsync(d_low, 0, sizeof low, f.stream);
+  record(0);
+  if (e == hipSuccess) {
+    const uint32_t blocks = std::max(1u, std::min((f.nps + 255) / 256, 2048u));
+    hipLaunchKernelGGL(yk_film_moments, dim3(blocks), dim3(256), 0, f.stream, f.plane, f.order, f.count, d_mv, d_low,
+                       f.nps, (uint32_t)npix, f.done);
+    e = hipGetLastError();
+  }
+  record(1);
+  if (e == hipSuccess) {
+    GuidedArgs g{};
+    NlmArgs& a = g.c;
+    a.mv = d_mv;
+    a.out = d_out;
+    a.rows = f.rows;
+    a.wt = f.wt;
+    a.npix = (uint32_t)npix;
+    a.radius = dp.radius;
+    a.patch = dp.patch;
+    a.k2 = dp.k2;
+    a.alpha = dp.alpha;
+    a.eps = dp.eps;
+    a.npatch = (double)(3 * (2 * dp.patch + 1) * (2 * dp.patch + 1));
+    g.feat = d_feat;
+    g.k2 = fp.k2;
+    g.alpha = fp.alpha;
+    g.tau[0] = fp.tau_albedo;
+    g.tau[1] = fp.tau_normal;
+    g.tau[2] = fp.tau_depth;
+    const dim3 grid((f.wt + kBlockW - 1) / kBlockW, (f.rows + kBlockH - 1) / kBlockH);
+    hipLaunchKernelGGL(yk_film_nlm_guided, grid, dim3(kThreads), nlm_lds_bytes(dp.radius, dp.patch), f.stream, g);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && rgb_host) {
+    const uint32_t blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>((3 * npix + 255) / 256, 2048));
+    hipLaunchKernelGGL(yk_film_rgb8, dim3(blocks), dim3(256), 0, f.stream, d_out, d_rgb, (uint64_t)(3 * npix));
+    e = hipGetLastError();
+  }
+  record(2);
+  if (e == hipSuccess) e = hipMemcpyAsync(&low, d_low, sizeof low, hipMemcpyDeviceToHost, f.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(f.stream);
+  // (the outputs are written only once the call is known to succeed)
+  if (e == hipSuccess && low == 0) {
+    if (mean_host) e = hipMemcpyAsync(mean_host, d_out, 3 * npix * sizeof(double), hipMemcpyDeviceToHost, f.stream);
+    if (e == hipSuccess && rgb_host) e = hipMemcpyAsync(rgb_host, d_rgb, 3 * npix, hipMemcpyDeviceToHost, f.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(f.stream);
+  }
+  float ms_m = 0, ms_f = 0;
+  if (stats && e == hipSuccess) e = hipEventElapsedTime(&ms_m, ev[0], ev[1]);
+  if (stats && e == hipSuccess) e = hipEventElapsedTime(&ms_f, ev[1], ev[2]);
+  for (hipEvent_t v : ev)
+    if (v) (void)hipEventDestroy(v);
+  if (e != hipSuccess)
+    return yk_film_fail(e == hipErrorOutOfMemory ? YK_ERR_NOMEM : YK_ERR_DEVICE,
+                        (std::string("ykgpu_film_denoise_guided: ") + hipGetErrorString(e)).c_str());
+  if (low) return yk_film_fail(YK_ERR_INVALID, "denoise needs at least two samples in every pixel");
+  if (stats) {
+    stats->features_ms = ms_feat;
     stats->moments_ms = ms_m;
     stats->filter_ms = ms_f;
     stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -2873,6 +2873,9 @@ struct ykgpu_film {
   uint32_t g_slots = 0;  // != 0: launch() renders the group (d_gorder, d_gmap) instead of the film's order
   // ykgpu_film_denoise's buffers (yk_denoise.hip), allocated at the film's first denoise
   void* d_denoise = nullptr;
+  // ykgpu_film_features' planes (yk_features.hip), allocated at the first pass, and their grid
+  void* d_features = nullptr;
+  uint32_t feature_grid = 0;
   bool uniform() const { return hist.size() <= 1; }
 };
 
@@ -4427,7 +4430,7 @@ int ykgpu_film_destroy(ykgpu_film* film) {
   (void)hipFree(film->d_order);
   (void)hipFree(film->d_result);
   for (void* q : {(void*)film->d_count, (void*)film->d_take, (void*)film->d_blocks, (void*)film->d_gorder,
-                  (void*)film->d_gmap, (void*)film->d_hist, film->d_denoise})
+                  (void*)film->d_gmap, (void*)film->d_hist, film->d_denoise, film->d_features})
     (void)hipFree(q);
   delete film;
   return YK_OK;
@@ -4897,7 +4900,8 @@ int ykgpu_render_devices(const int* devices, uint32_t n_devices, const yk_sphere
 
 }  // extern "C"
 
-// ---- film denoise (yk_denoise.hip): that unit's view of a film, and this unit's error slot ------
+// ---- film denoise and features (yk_denoise.hip, yk_features.hip): those units' view of a film, and
+// this unit's error slot
 int yk_film_fail(int code, const char* msg) { return fail(code, msg); }
 
 int yk_film_view_of(ykgpu_film* film, yk_film_view* out) {
@@ -4916,6 +4920,27 @@ int yk_film_view_of(ykgpu_film* film, yk_film_view* out) {
   out->consecutive = host_row_y(&p, p.row_count - 1) == (uint64_t)p.row_begin + p.row_count - 1 &&
                      host_col_x(&p, out->wt - 1) == (uint64_t)p.col_begin + out->wt - 1;
   out->scratch = &film->d_denoise;
+  static_assert(sizeof(SphereGeo) == 4 * sizeof(double) && offsetof(SphereGeo, rr) == 3 * sizeof(double), "yk_film_view::geo");
+  static_assert(sizeof(SphereMat) == kYkMatStride && offsetof(SphereMat, ar) == kYkMatAlbedo &&
+                    offsetof(SphereMat, ab) == kYkMatAlbedo + 16 && offsetof(SphereMat, radius) == kYkMatRadius &&
+                    offsetof(SphereMat, kind) == kYkMatKind, "yk_film_view::mat");
+  const ykgpu_context* ctx = film->ctx;
+  out->W = p.image_width;
+  out->H = p.image_height;
+  out->row_begin = p.row_begin;
+  out->row_stride = p.row_stride;
+  out->row_band = p.row_band_log2;
+  out->col_begin = p.col_count ? p.col_begin : 0;
+  out->col_stride = p.col_count ? p.col_stride : 1;
+  out->col_band = p.col_count ? p.col_band_log2 : 0;
+  out->t_min = p.t_min;
+  out->stale = film->scene_gen != ctx->scene_gen;
+  out->geo = (const double*)ctx->d_geo;
+  out->mat = (const unsigned char*)ctx->d_mat;
+  out->nspheres = ctx->nspheres;
+  out->cam = ctx->cam;
+  out->features = &film->d_features;
+  out->feature_grid = &film->feature_grid;
   return YK_OK;
 }
 #endif  // YK_SPLIT != 2

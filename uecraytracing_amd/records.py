@@ -190,7 +190,39 @@ class DenoiseStats(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class FeatureParams(ctypes.Structure):
+    """yk_feature_params (include/ykgpu.h "film features"): the feature pass's grid and the guided
+    filter's feature scales."""
+    _fields_ = [
+        ("grid", ctypes.c_uint32),  # g, 1..4
+        ("reserved", ctypes.c_uint32),  # 0
+        ("k2", ctypes.c_double),
+        ("alpha", ctypes.c_double),
+        ("tau_albedo", ctypes.c_double),  # > 0, +inf switches the group off
+        ("tau_normal", ctypes.c_double),
+        ("tau_depth", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved"}
+
+
+class GuidedStats(ctypes.Structure):
+    """yk_guided_stats (include/ykgpu.h): where one ykgpu_film_denoise_guided call spent its time."""
+    _fields_ = [
+        ("features_ms", ctypes.c_double),  # 0 when the cached pass was reused
+        ("moments_ms", ctypes.c_double),
+        ("filter_ms", ctypes.c_double),
+        ("total_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 assert ctypes.sizeof(Sphere) == 80
+assert ctypes.sizeof(FeatureParams) == 48
+assert ctypes.sizeof(GuidedStats) == 32
 assert ctypes.sizeof(DenoiseParams) == 32
 assert ctypes.sizeof(DenoiseStats) == 24
 assert ctypes.sizeof(FilmPass) == 32
