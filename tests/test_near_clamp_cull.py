@@ -1,5 +1,5 @@
 """The FP64 visit's culling test with distances measured from t_min and clamped near FMAs
-(`YK_NEAR_CLAMP`) keeps every box the culling contract requires (CPU).
+(the clamped near distances) keeps every box the culling contract requires (CPU).
 
 The kernel keeps a wide-node slot when max(near, tmin_lo) <= min(far * c, U*(1 + 2^-18)) (round 5,
 `old` below); round 6 computes the same test in distances from tmin_lo scaled by s = 2^-24, the

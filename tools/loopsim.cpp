@@ -819,7 +819,7 @@ int main(int argc, char** argv) {
            "per lane: visits %.2f leaf tests %.2f | cost %.0f\n",
            name[variant], trips / nw, wv / nw, wl / nw, wd2 / nw, lv / (64.0 * nw), ll / (64.0 * nw), cost / nw);
   }
-  // ---- round 6: the branch-free visit's while-while loop (YK_NODE_BF: an inner visit loop until
+  // ---- round 6: the branch-free visit's while-while loop (an inner visit loop until
   // every lane holds a leaf, then one leaf block, then the pops) and its speculative form (a visit
   // whose last entered child is a leaf parks it and goes on with the entry below the new top, known
   // in registers; the leaf block tests the parked leaf, else the lane's current leaf)

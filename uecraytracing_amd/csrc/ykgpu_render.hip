@@ -83,6 +83,9 @@ struct alignas(16) SphereMat {
 };
 static_assert(sizeof(SphereMat) == 64, "SphereMat layout");
 
+// ---- Kernel-side tuning constants (each overridable with -DYK_...: `make variants`,
+// tools/build_def_variant.sh).  The host's are gathered at the top of the host half. ----
+//
 // One 768-thread workgroup per CU (12 waves, 3 per SIMD): the scene is copied into LDS once per
 // CU instead of once per 256-thread block, which leaves room for the shading tables (sphere
 // geometry and materials in tuple order) beside the BVH and the traversal stacks.  The fourth
@@ -93,119 +96,11 @@ static_assert(sizeof(SphereMat) == 64, "SphereMat layout");
 #ifndef YK_BLOCK
 #define YK_BLOCK 768
 #endif
-#ifndef YK_WAVES_PER_EU
-#define YK_WAVES_PER_EU 0
-#endif
-constexpr int kBlock = YK_BLOCK;
 // The xor128 instances draw no seed walks, so nothing needs the fourth wave slot of a SIMD: they
 // run 1024-thread workgroups (4 render waves per SIMD; the node loop is bound by LDS latency, so
 // the fourth wave pays)
 #ifndef YK_BLOCK_X128
 #define YK_BLOCK_X128 1024
-#endif
-constexpr int kBlockX128 = YK_BLOCK_X128;
-template <int kMode>
-constexpr int mode_block() {
-  return (kMode & 4) ? kBlockX128 : kBlock;
-}
-constexpr int block_of(bool x128) { return x128 ? kBlockX128 : kBlock; }
-#ifndef YK_RENDER_PRIO
-#define YK_RENDER_PRIO 1
-#endif
-// the visit's slab constants as one op_sel-read register pair per axis and bound (yk_slab.hpp):
-// round 4: FP64 123 -> 115 VGPRs and no faster (512 spp 173.9 -> 174.2 ms), FP32 125 -> 111 VGPRs
-// and faster (195.3 -> 190.1 ms, profiles/r04_ab/f32/).  Round 6, on the branch-free visit: FP64
-// 128 -> 114 VGPRs, bench -0.7% (the SIMD's spare registers take a third warm-up wave,
-// profiles/r06_ab/vgpr/), so both kernels now read slab pairs.
-// YK_SLAB_PAIRS sets both (A/B).  (Round 4's two-paths-per-lane kernel, which lost its A/B, is
-// kept as a patch beside its evidence: profiles/r04_ab/dual/yk_dual.patch.)
-#ifdef YK_SLAB_PAIRS
-#define YK_SLAB_PAIRS_F64 YK_SLAB_PAIRS
-#define YK_SLAB_PAIRS_F32 YK_SLAB_PAIRS
-#endif
-#ifndef YK_SLAB_PAIRS_F64
-#define YK_SLAB_PAIRS_F64 1
-#endif
-#ifndef YK_SLAB_PAIRS_F32
-#define YK_SLAB_PAIRS_F32 1
-#endif
-// (Tried and removed in round 4, DESIGN.md §4.1: the FP32 slow-axis bound folded into the slow
-// axis' far-plane FMA, +2.3%; the slow-axis read skipped in waves without a slow-axis ray, +3.8%.)
-using DevNode = ykbvh::WideNode;  // 4-wide BVH nodes (yk_bvh.hpp)
-constexpr int kCounters = 32;  // [16..18]: timeline, [19..22]: diag (stamp builds), [24..31]: work
-// Spheres per BVH leaf the kernels' leaf code handles: the FP64 leaf test is loop-free for one
-// sphere, the FP32 leaf loop is unrolled for two.  ykgpu_set_scene builds the trees with these
-// as ykbvh::Options::max_leaf and upload_tree rejects a tree with a larger leaf (its extra spheres
-// would be skipped silently).
-constexpr uint32_t kLeafCapF64 = 1, kLeafCapF32 = 2;
-constexpr uint32_t kStackRegs = 8;  // attenuation ids kept in registers (4 x 2 x u16)
-// FP64 node visit without a branch (round 6): the stack's bottom entry holds the empty leaf (a
-// sentinel), so "no slot entered" pops unconditionally and every lane of the visit runs the same
-// instructions; a lane's run of interior nodes is a loop of its own (while-while), the entry below
-// the top read with the planes.  2: the loop variable is the address of that entry (constant DS
-// offsets for it and the pushes).  0: the round-5 visit with its push / pop branches (A/B).
-// 512 spp, same box (profiles/r06_ab/nodebf/): 0 -> 1: bench 163.0 -> 159.5 ms; 2 = 1.
-#ifndef YK_NODE_BF
-#define YK_NODE_BF 2
-#endif
-// the FP64 stack sized to the tree's proven depth (3 x wide depth + 1 entries) where LDS allows,
-// its overflow check then skipped (a scalar branch on KernelArgs::stack_check): bench 159.0 ->
-// 156.2 ms on top of YK_NODE_BF (0: always checked, A/B)
-// the FP64 candidate list's ids as 16-bit halves of two registers (written for the YK_CAND_HD /
-// YK_NEAR_CLAMP kernel): the shift-in is one alignbit and one lshl_or instead of four moves, two
-// VGPRs freed; bench -0.3...-0.6%, synced -0.4...-0.8%, image hash unchanged (r06_ab/shade/r06ax_*)
-#ifndef YK_CAND_PACK
-#define YK_CAND_PACK 1
-#endif
-// ... and its v_rsq_f64, which math::sqrt's start repeats (A/B; 2 VGPRs more)
-#ifndef YK_CAND_RSQ
-#define YK_CAND_RSQ 0
-#endif
-// the candidates' refined 1/a from the bounds' 1/a (one Newton step instead of rcp + two; A/B)
-#ifndef YK_RA_FROM_IA
-#define YK_RA_FROM_IA 0
-#endif
-// the newest candidate's hb and disc kept from its leaf test, so its exact root skips the second
-// discriminant (17 FP64 operations): bench -0.4...-0.6%, synced -0.6%, the headline image's hash
-// unchanged, no spill at 112 VGPRs (profiles/r06_ab/shade/r06ar_*)
-#ifndef YK_CAND_HD
-#define YK_CAND_HD 1
-#endif
-// the FP64 visit's loop in two copies, with and without the stack check (A/B)
-#ifndef YK_VISIT_UNSWITCH
-#define YK_VISIT_UNSWITCH 0
-#endif
-// the FP64 visit's distances from tmin_lo, scaled by kClampScale, the near FMAs clamping to [0, 1]
-// in place of the max with tmin_lo: 4 VALU fewer per visit, bench 150.0 -> 147.0 ms, node visits
-// unchanged, bit-exact (profiles/r06_ab/shade/r06ai_*)
-#ifndef YK_NEAR_CLAMP
-#define YK_NEAR_CLAMP 1
-#endif
-constexpr float kClampScale = 0x1p-24f;
-// the FP64 visit's slab min / max two slots per asm block (yk_slab.hpp slab_cull2): one hazard
-// pad per visit instead of eight, bench -0.2% (four of four same-box pairs, image hashes equal,
-// profiles/r06_ab/shade/r06ag_*)
-#ifndef YK_CULL_BLOCK
-#define YK_CULL_BLOCK 1
-#endif
-#ifndef YK_STACK_EXACT
-#define YK_STACK_EXACT 1
-#endif
-
-// the FP64 dielectric's 1/ior and Schlick r0 (both sides) precomputed on the host: two FP64
-// divisions fewer per trip with a glass hit (bench -0.6%, profiles/r06_ab/shade/; 0: A/B)
-#ifndef YK_DIEL_PRE
-#define YK_DIEL_PRE 1
-#endif
-// the FP64 unwind without the spill check when no ending lane of the wave spilled, two ids per
-// round (bench 156.6 -> 156.0 ms, profiles/r06_ab/unwind/; 0: the round-5 unwind, A/B)
-#ifndef YK_UNWIND_FAST
-#define YK_UNWIND_FAST 1
-#endif
-// slot claims: the tail size from a kernel argument and the leader's counter by v_readlane (the
-// claim's bookkeeping becomes scalar: 2 VGPRs fewer; 0: A/B)
-#ifndef YK_CLAIM_ARGS
-#define YK_CLAIM_ARGS 1
 #endif
 // VGPRs of the production FP64 render instances: 3 render waves x 112 of a SIMD's 512 leave 176, three
 // 48-VGPR warm-up waves and a reduce wave (bench -0.4% against the natural 114 -> 120; 104 spills
@@ -213,10 +108,10 @@ constexpr float kClampScale = 0x1p-24f;
 #ifndef YK_RENDER_VGPRS
 #define YK_RENDER_VGPRS 112
 #endif
+// sample slots a wave claims per atomic ...
 #ifndef YK_CLAIM
 #define YK_CLAIM 512
 #endif
-constexpr uint32_t kClaim = YK_CLAIM;  // sample slots a wave claims per atomic
 // ... and near the end of a launch's slots: when fewer than kClaimTailFactor x kClaim slots per
 // wave of the grid remain (as the wave last saw the counter), a wave claims kClaimTail slots at a
 // time.  A wave's reserve holds up to kClaim slots (8 samples per lane) when the counter runs
@@ -228,21 +123,87 @@ constexpr uint32_t kClaim = YK_CLAIM;  // sample slots a wave claims per atomic
 #ifndef YK_CLAIM_TAIL_FACTOR
 #define YK_CLAIM_TAIL_FACTOR 2
 #endif
-constexpr uint32_t kClaimTail = YK_CLAIM_TAIL, kClaimTailFactor = YK_CLAIM_TAIL_FACTOR;
-static_assert(kClaimTail == 0 || (kClaimTail >= 64 && kClaimTail <= YK_CLAIM), "a tail claim serves a whole wave");
-#ifndef YK_WG_HOLD
-#define YK_WG_HOLD 0
-#endif
-// the FP64 lens warm-up's retries drawn after its walks (yk_mt_warmup_defer) for launches of at
-// most YK_DEFER_SLOTS slots per warm-up wave (0: the rejection loop in line everywhere)
-#ifndef YK_LENS_DEFER
-#define YK_LENS_DEFER 1
-#endif
+// the FP64 lens warm-up's retries are drawn after its walks (yk_mt_warmup_defer) for launches of at
+// most YK_DEFER_SLOTS slots per warm-up wave; larger launches run the rejection loop in line
 #ifndef YK_DEFER_SLOTS
 #define YK_DEFER_SLOTS 4096
 #endif
-constexpr bool kLensDefer = YK_LENS_DEFER != 0;
+// Walks per lane: the deferred FP64 lens warm-up (the headline frame's) walks four slots at once at
+// 48 VGPRs, so two of its waves share a SIMD with the three render waves (eight walk chains per
+// SIMD instead of four: bench -0.9%, r05_ab/walk/); the other warm-ups walk one
+#ifndef YK_WALK_ILP
+#define YK_WALK_ILP 4
+#endif
+// VGPRs of yk_mt_warmup_defer (the attribute counts gfx950's unified register file: twice)
+#ifndef YK_DEFER_VGPRS
+#define YK_DEFER_VGPRS 48
+#endif
+constexpr int kBlock = YK_BLOCK, kBlockX128 = YK_BLOCK_X128;
+constexpr uint32_t kClaim = YK_CLAIM;
+constexpr uint32_t kClaimTail = YK_CLAIM_TAIL, kClaimTailFactor = YK_CLAIM_TAIL_FACTOR;
+static_assert(kClaimTail == 0 || (kClaimTail >= 64 && kClaimTail <= YK_CLAIM), "a tail claim serves a whole wave");
 constexpr uint64_t kDeferSlots = YK_DEFER_SLOTS;
+constexpr uint32_t kWalkIlp = YK_WALK_ILP;
+
+template <int kMode>
+constexpr int mode_block() {
+  return (kMode & 4) ? kBlockX128 : kBlock;
+}
+constexpr int block_of(bool x128) { return x128 ? kBlockX128 : kBlock; }
+
+// ---- The variants the kernels are built from.  Each was one side of a compile-time A/B; the losing
+// sides are gone from the source (profiles/r11_knobs/README.md says where each one went). ----
+//
+// Both render kernels read the visit's slab constants as one op_sel-read register pair per axis and
+// bound (yk_slab.hpp).  Round 4: FP64 123 -> 115 VGPRs and no faster (512 spp 173.9 -> 174.2 ms),
+// FP32 125 -> 111 VGPRs and faster (195.3 -> 190.1 ms, profiles/r04_ab/f32/).  Round 6, on the
+// branch-free visit: FP64 128 -> 114 VGPRs, bench -0.7% (the SIMD's spare registers take a third
+// warm-up wave, profiles/r06_ab/vgpr/).  (Round 4's two-paths-per-lane kernel, which lost its A/B,
+// is kept as a patch beside its evidence: profiles/r04_ab/dual/yk_dual.patch.)
+// (Tried and removed in round 4, DESIGN.md §4.1: the FP32 slow-axis bound folded into the slow
+// axis' far-plane FMA, +2.3%; the slow-axis read skipped in waves without a slow-axis ray, +3.8%.)
+//
+// The FP64 node visit has no branch (round 6): the stack's bottom entry holds the empty leaf (a
+// sentinel), so "no slot entered" pops unconditionally and every lane of the visit runs the same
+// instructions; a lane's run of interior nodes is a loop of its own (while-while), the entry below
+// the top read with the planes.  The loop variable is the address of that entry (constant DS
+// offsets for it and the pushes).  512 spp, same box (profiles/r06_ab/nodebf/): round 5's visit
+// with its push / pop branches -> this one: bench 163.0 -> 159.5 ms.
+// The visit's loop exists once, its stack check a uniform branch inside it (two copies, with and
+// without the check: +0.4%, profiles/r06_ab/shade/r06an_*).
+// The FP64 stack is sized to the tree's proven depth (3 x wide depth + 1 entries) where LDS allows,
+// its overflow check then skipped (a scalar branch on KernelArgs::stack_check): bench 159.0 ->
+// 156.2 ms on top of the branch-free visit.
+// The visit's distances are measured from tmin_lo and scaled by kClampScale, the near FMAs clamp to
+// [0, 1] in place of the max with tmin_lo: 4 VALU fewer per visit, bench 150.0 -> 147.0 ms, node
+// visits unchanged, bit-exact (profiles/r06_ab/shade/r06ai_*).
+// The visit's slab min / max run two slots per asm block (yk_slab.hpp slab_cull2c): one hazard
+// pad per visit instead of eight, bench -0.2% (four of four same-box pairs, image hashes equal,
+// profiles/r06_ab/shade/r06ag_*).
+// The FP64 candidate list keeps its ids as 16-bit halves of two registers: the shift-in is one
+// alignbit and one lshl_or instead of four moves, two VGPRs freed; bench -0.3...-0.6%, synced
+// -0.4...-0.8%, image hash unchanged (r06_ab/shade/r06ax_*).
+// The newest candidate's hb and disc are kept from its leaf test, so its exact root skips the second
+// discriminant (17 FP64 operations): bench -0.4...-0.6%, synced -0.6%, the headline image's hash
+// unchanged, no spill at 112 VGPRs (profiles/r06_ab/shade/r06ar_*).  Its v_rsq_f64, which
+// math::sqrt's start repeats, is not kept (2 VGPRs more: three spills at 112), and the candidates'
+// refined 1/a is computed on its own, not from the bounds' 1/a (one Newton step instead of rcp +
+// two: neutral, profiles/r06_ab/shade/r06au_*).
+// The FP64 dielectric's 1/ior and Schlick r0 (both sides) are precomputed on the host: two FP64
+// divisions fewer per trip with a glass hit (bench -0.6%, profiles/r06_ab/shade/).
+// The FP64 unwind skips the spill check when no ending lane of the wave spilled, two ids per
+// round (bench 156.6 -> 156.0 ms, profiles/r06_ab/unwind/).
+// Slot claims take the tail size from a kernel argument and the leader's counter by v_readlane (the
+// claim's bookkeeping becomes scalar: 2 VGPRs fewer, profiles/r06_ab/vgpr/r06t_*).
+constexpr float kClampScale = 0x1p-24f;
+using DevNode = ykbvh::WideNode;  // 4-wide BVH nodes (yk_bvh.hpp)
+constexpr int kCounters = 32;  // [16..18]: timeline, [19..22]: diag (stamp builds), [24..31]: work
+// Spheres per BVH leaf the kernels' leaf code handles: the FP64 leaf test is loop-free for one
+// sphere, the FP32 leaf loop is unrolled for two.  ykgpu_set_scene builds the trees with these
+// as ykbvh::Options::max_leaf and upload_tree rejects a tree with a larger leaf (its extra spheres
+// would be skipped silently).
+constexpr uint32_t kLeafCapF64 = 1, kLeafCapF32 = 2;
+constexpr uint32_t kStackRegs = 8;  // attenuation ids kept in registers (4 x 2 x u16)
 constexpr uint32_t kFlagLinearScan = YK_FLAG_LINEAR_SCAN;
 constexpr uint32_t kFlagOneLane = YK_FLAG_ONE_LANE;
 constexpr uint32_t kFlagTrace = YK_FLAG_TRACE_RAYS;
@@ -424,8 +385,6 @@ __device__ __forceinline__ float safe_rcp(float x) {
     else { c3 = ID; l3 = LB; }                \
   } while (0)
 
-// Exact value of sphere i's root under the reference's acceptance rule, ignoring t_max
-// (sphere.hpp:35-39): root1 if root1 >= t_min, else root2 if root2 >= t_min, else none.
 // n / a for a root (sphere.hpp:36-38), a's refined reciprocal shared by all candidates; a wave
 // with any lane out of range takes the full division (divs_fast's rule)
 __device__ __forceinline__ double root_div(double n, double a, double ra, bool a_ok) {
@@ -433,25 +392,14 @@ __device__ __forceinline__ double root_div(double n, double a, double ra, bool a
   if (__builtin_expect(__ballot(!(a_ok && ykd::num_range(n))) != 0, 0)) q = n / a;
   return q;
 }
+// Exact value of sphere i's root under the reference's acceptance rule, ignoring t_max
+// (sphere.hpp:35-39): root1 if root1 >= t_min, else root2 if root2 >= t_min, else none — from the
+// candidate's hb and disc (the reference's, bit for bit)
 __device__ __forceinline__ void exact_root(uint32_t i, double hb, double disc, double a, double ra, bool a_ok,
-                                           double tmin, Hit& best, const double* rsq = nullptr);
-__device__ __forceinline__ void exact_candidate(const SphereGeo* __restrict__ geo, uint32_t i,
-                                                v3 o, v3 d, double a, double ra, bool a_ok,
-                                                double tmin, Hit& best) {
-  const SphereGeo sg = geo[i];
-  const v3 oc = {o.x - sg.cx, o.y - sg.cy, o.z - sg.cz};
-  const double hb = ykd::dot(oc, d);
-  const double c = ykd::len2(oc) - sg.rr;
-  const double disc = hb * hb - a * c;
-  exact_root(i, hb, disc, a, ra, a_ok, tmin, best);
-}
-// the root of a candidate whose hb and disc (the reference's, bit for bit) are already known
-__device__ __forceinline__ void exact_root(uint32_t i, double hb, double disc, double a, double ra, bool a_ok,
-                                           double tmin, Hit& best, const double* rsq) {
+                                           double tmin, Hit& best) {
   if (disc < 0) return;  // never taken: the candidate passed the same test
   ++best.sqrts;
-  // (rsq: v_rsq_f64 of this disc from the leaf test, the instruction math::sqrt's start would repeat)
-  const double sq = rsq ? ykd::nsqrt_c_r(disc, *rsq, best.ncalls, best.nits) : ykd::nsqrt_c(disc, best.ncalls, best.nits);
+  const double sq = ykd::nsqrt_c(disc, best.ncalls, best.nits);
   double r = root_div(-hb - sq, a, ra, a_ok);
   if (r < tmin) {
     r = root_div(-hb + sq, a, ra, a_ok);
@@ -462,6 +410,17 @@ __device__ __forceinline__ void exact_root(uint32_t i, double hb, double disc, d
     best.T = r;
     best.hid = (int)i;
   }
+}
+// ... of a candidate whose hb and disc were not kept from its leaf test
+__device__ __forceinline__ void exact_candidate(const SphereGeo* __restrict__ geo, uint32_t i,
+                                                v3 o, v3 d, double a, double ra, bool a_ok,
+                                                double tmin, Hit& best) {
+  const SphereGeo sg = geo[i];
+  const v3 oc = {o.x - sg.cx, o.y - sg.cy, o.z - sg.cz};
+  const double hb = ykd::dot(oc, d);
+  const double c = ykd::len2(oc) - sg.rr;
+  const double disc = hb * hb - a * c;
+  exact_root(i, hb, disc, a, ra, a_ok, tmin, best);
 }
 
 __device__ __forceinline__ v3 ld3(const double* p) { return {p[0], p[1], p[2]}; }
@@ -723,15 +682,6 @@ __device__ __forceinline__ void mt_warmup_body(const WarmArgs& wa) {
       const uint32_t seed = slot_seed(i, xx, y);
       uint32_t x[1] = {seed};
       ykd::mt_walk397xn<1>(x);
-#ifdef YK_WALK_SENS
-      // (sensitivity probe, never in the product: YK_WALK_SENS more walks of a perturbed seed, their
-      // result folded in as a no-op the compiler cannot prove)
-      for (int r_ = 0; r_ < YK_WALK_SENS; ++r_) {
-        uint32_t z[1] = {seed ^ (0x9e3779b9u + (uint32_t)r_)};
-        ykd::mt_walk397xn<1>(z);
-        x[0] ^= (z[0] == 0x12345678u && seed == 0x9abcdef0u) ? 1u : 0u;
-      }
-#endif
       start_slot(i, xx, y, seed, x[0]);
     }
   }
@@ -789,25 +739,13 @@ __device__ __forceinline__ void mt_warmup_body(const WarmArgs& wa) {
   }
 }
 
-// Walks per lane: the deferred FP64 lens warm-up (the headline frame's) walks four slots at once at
-// 48 VGPRs, so two of its waves share a SIMD with the three render waves (eight walk chains per
-// SIMD instead of four: bench -0.9%, r05_ab/walk/); the other warm-ups walk one
-#ifndef YK_WALK_ILP
-#define YK_WALK_ILP 4
-#endif
-#ifndef YK_WALK_ILP_INLINE
-#define YK_WALK_ILP_INLINE 1
-#endif
-constexpr uint32_t kWalkIlp = YK_WALK_ILP, kWalkIlpInline = YK_WALK_ILP_INLINE;
+// one walk per lane (the deferred FP64 lens warm-up below walks kWalkIlp slots at once)
 template <bool kLens, bool kF32>
 __global__ __launch_bounds__(256) void yk_mt_warmup(WarmArgs wa) {
-  mt_warmup_body<kLens, kF32, false, kWalkIlpInline>(wa);
+  mt_warmup_body<kLens, kF32, false, 1>(wa);
 }
 // the FP64 lens warm-up with its retries deferred, at 48 VGPRs: two of its waves beside the three
 // 128-VGPR render waves of a SIMD (the attribute counts gfx950's unified register file: twice)
-#ifndef YK_DEFER_VGPRS
-#define YK_DEFER_VGPRS 48
-#endif
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(YK_DEFER_VGPRS / 2))) void yk_mt_warmup_defer(WarmArgs wa) {
   mt_warmup_body<true, false, true, kWalkIlp>(wa);
 }
@@ -1198,20 +1136,12 @@ __device__ __forceinline__ bool claim_slots(const KernelArgs& ka, bool in_path, 
       if (kClaimTail) {
         // res_base + res_left: where the counter stood after this wave's last claim
         const uint32_t seen = res_base + res_left;
-#if YK_CLAIM_ARGS
         const uint32_t tail = ka.claim_tail;  // (the host's: no dispatch-packet load, no vmcnt wait)
-#else
-        const uint32_t tail = gridDim.x * (blockDim.x >> 6) * kClaim * kClaimTailFactor;
-#endif
         if (seen >= ka.nsl || ka.nsl - seen < tail) csize = kClaimTail;
       }
       const int leader = __ffsll((long long)m) - 1;
       if ((int)lane == leader) fresh = atomicAdd(ka.pixel_counter, csize);
-#if YK_CLAIM_ARGS
       fresh = __builtin_amdgcn_readlane(fresh, leader);  // (the leader is wave-uniform)
-#else
-      fresh = __shfl(fresh, leader);
-#endif
     }
     if (!in_path) {
       const uint32_t r = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
@@ -1271,10 +1201,8 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
     }
     __syncthreads();
     nodes = smem;
-#if YK_NODE_BF
     // the child-code reads address the LDS copy from 0: the dynamic region must start there
     if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem != 0u) __builtin_trap();
-#endif
     leaf_geo = (const SphereGeo*)(smem + ka.lds_geo_off);
     leaf_ids = (const uint32_t*)(smem + ka.lds_ids_off);
     geo = (const SphereGeo*)(smem + ka.lds_tgeo_off);
@@ -1285,13 +1213,9 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
   // barrier, so every wave-instruction below is one lane's (the profiler's per-wave FP64 counters
   // then count that lane's executed operations exactly: DESIGN.md §5)
   if (kCount && (ka.flags & kFlagOneLane) && lane != 0) return;
-#if YK_NODE_BF
   stk[0] = ykbvh::kEmptyLeaf;  // the sentinel below every traversal's entries
-#endif
-#if YK_RENDER_PRIO
   // the warm-up waves sharing the SIMDs (priority 0) get only the issue slots the render leaves
-  __builtin_amdgcn_s_setprio(YK_RENDER_PRIO);
-#endif
+  __builtin_amdgcn_s_setprio(1);
   YK_CLOCK_BEGIN(ka);
   YK_WAVE_STAMP(ka, 0);
 
@@ -1455,7 +1379,6 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
         const float ixs = ix * kFar, iys = iy * kFar, izs = iz * kFar;
         const float ox_f = (float)o.x, oy_f = (float)o.y, oz_f = (float)o.z;
         const float tmin_lo = __double2float_rd(ka.t_min) * (1.0f - 0x1p-17f);
-#if YK_SLAB_PAIRS_F64 && YK_NEAR_CLAMP
         // Distances measured from tmin_lo and scaled by kClampScale = 2^-24: per
         // axis (s/d, s(-o/d - tmin_lo)) (near) and (sc/d, s(-oc/d - tmin_lo)) (far).  The near
         // FMAs clamp to [0, 1], which IS the max with tmin_lo (distances below 2^24 + tmin_lo
@@ -1468,42 +1391,17 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
                  szp = {iz * kS, (-oiz - tmin_lo) * kS};
         const f2 fxp = {ixs * kS, (-(ox_f * ixs) - tmin_lo) * kS}, fyp = {iys * kS, (-(oy_f * iys) - tmin_lo) * kS},
                  fzp = {izs * kS, (-(oz_f * izs) - tmin_lo) * kS};
-#elif YK_SLAB_PAIRS_F64
-        // per axis ONE register pair (1/d, -o/d) (near) and (c/d, -o c/d) (far), read by op_sel
-        // (yk_slab.hpp): 12 VGPRs instead of 24
-        const f2 sxp = {ix, -oix}, syp = {iy, -oiy}, szp = {iz, -oiz};
-        const f2 fxp = {ixs, -(ox_f * ixs)}, fyp = {iys, -(oy_f * iys)}, fzp = {izs, -(oz_f * izs)};
-#else
-        const f2 ixv = {ix, ix}, iyv = {iy, iy}, izv = {iz, iz};
-        const f2 noix = {-oix, -oix}, noiy = {-oiy, -oiy}, noiz = {-oiz, -oiz};
-        const f2 ixc = {ixs, ixs}, iyc = {iys, iys}, izc = {izs, izs};
-        const f2 noixc = {-(ox_f * ixs), -(ox_f * ixs)}, noiyc = {-(oy_f * iys), -(oy_f * iys)},
-                 noizc = {-(oz_f * izs), -(oz_f * izs)};
-#endif
         const double ia = ykd::rcp_bound(a);  // bounds only: relative error < 2^-44
         double ustar = INFINITY;  // proven upper bound of the minimum exact root
-        float ustar_f = INFINITY;  // >= ustar * (1 + 2^-18) (YK_NEAR_CLAMP: >= s (that - tmin_lo))
-#if YK_SLAB_PAIRS_F64 && YK_NEAR_CLAMP
+        float ustar_f = INFINITY;  // >= ustar * (1 + 2^-18) (clamped distances: >= s (that - tmin_lo))
         // a lane whose 1/d could leave float's normal range once scaled (|d| >= 1e30, never seen)
         // is marked for the exact linear scan from the start (nc = 5, as an overflow)
-#if YK_CAND_PACK
         // the candidates' tuple ids as 16-bit halves (ids are < 2^16: ykgpu_set_scene's limit),
         // entry 0 in cp01's low half
         uint32_t nc = dmax < 1e30f ? 0u : 5u, cp01 = 0, cp23 = 0;
-#else
-        uint32_t nc = dmax < 1e30f ? 0u : 5u, c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-#endif
-#if YK_CAND_HD
         // hb and disc of entry 0 (always the newest candidate: a compaction is followed by the
         // insertion that caused it), so its exact root needs no second discriminant
         double hb0 = 0, disc0 = 0;
-#if YK_CAND_RSQ
-        double rsq0 = 0;  // ... and its v_rsq_f64
-#endif
-#endif
-#else
-        uint32_t nc = 0, c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-#endif
         // candidate lower bounds kept as floats RN(L), compared with ustar_f >= RN(U*): by
         // monotone rounding (all bounds >= 0) L <= U* implies RN(L) <= ustar_f, so the float
         // comparison only ever keeps MORE candidates than the double comparison would
@@ -1513,44 +1411,31 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
         // divergent exit has to merge (-3.4% as a bool), an integer flag is one more loop-carried
         // register (nc = 5 instead: -0.8%)
         int32_t node = ka.bvh_root;
-#if YK_NODE_BF
-        // this lane's traversal stack top as an LDS byte address (entries kBlk words apart), above
-        // the sentinel
-        // (YK_NODE_BF 2: the variable holds the address of the entry BELOW the top, kTopOff less,
-        // so the visit's read of that entry and the pushes at the top take constant DS offsets)
-        constexpr uint32_t kTopOff = YK_NODE_BF == 2 ? kBlk * 4u : 0u;
+        // this lane's traversal stack as LDS byte addresses (entries kBlk words apart).  `top` holds
+        // the address of the entry BELOW the top, kTopOff less than the top's (at the start: the
+        // sentinel's), so the visit's read of that entry and the pushes at the top take constant
+        // DS offsets.  (The expressions below spell the top's address less kTopOff out: the
+        // compiler schedules two instances differently when they are folded by hand.)
+        constexpr uint32_t kTopOff = kBlk * 4u;
         const uint32_t stk_b = (uint32_t)(uintptr_t)stk;
         uint32_t top = stk_b + kBlk * 4u - kTopOff;
         const uint32_t stk_cap = stk_b + ka.stack_cap * kBlk * 4u - kTopOff;
 #define YK_STK(a) (*(__attribute__((address_space(3))) int32_t*)(uintptr_t)(a))
-#else
-        int32_t* top = stk;  // this lane's traversal stack top (entries kBlk words apart)
-        const int32_t* const stk_cap = stk + ka.stack_cap * kBlk;
-#endif
         for (;;) {
           if (node >= 0) {
-#if YK_NODE_BF
            // the lane's run of interior nodes as a loop of its own tested at the bottom: its exit
            // value is the visit's own result, so the compiler keeps node / top / nc in place
-#if YK_VISIT_UNSWITCH
-           // (two copies of the loop, with and without the stack check: no uniform branch inside)
-           auto visit_run = [&](auto chk) __attribute__((always_inline)) {
-#endif
            do {
-#endif
             if (kCount) ++n_node;
             YK_STAMP_NODE_ITERATION(lane);
-#if YK_NODE_BF
             // the entry below the top (the sentinel when the stack holds nothing), read with the
             // planes: the pushes below write at and above the top, never here
             const int32_t popped = YK_STK(top + kTopOff - kBlk * 4u);
-#endif
             // near / far distances of the 4 slots per axis, one packed FMA per pair of slots:
             // t = plane*(1/d) - o*(1/d), the binary node's arithmetic per slot
             const f4 qnx = *(const f4*)(px + node), qfx = *(const f4*)(px + node + 16);
             const f4 qny = *(const f4*)(py + node), qfy = *(const f4*)(py + node + 16);
             const f4 qnz = *(const f4*)(pz + node), qfz = *(const f4*)(pz + node + 16);
-#if YK_NODE_BF
             // the scene's LDS copy starts at LDS address 0 (the kernel's only LDS is the dynamic
             // region, checked at the kernel's start), so the child codes of node n sit at n + 144
             int4 ch;
@@ -1561,11 +1446,7 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
             } else {
               ch = *(const int4*)(nodes + node + 144);
             }
-#else
-            const int4 ch = *(const int4*)(nodes + node + 144);
-#endif
             bool hk[4];
-#if YK_SLAB_PAIRS_F64 && YK_NEAR_CLAMP
             const f2 nx[2] = {slab_fma_clamp(qnx.xy, sxp), slab_fma_clamp(qnx.zw, sxp)};
             const f2 fx[2] = {slab_fma(qfx.xy, fxp), slab_fma(qfx.zw, fxp)};
             const f2 ny[2] = {slab_fma_clamp(qny.xy, syp), slab_fma_clamp(qny.zw, syp)};
@@ -1580,49 +1461,9 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
               hk[2 * h] = tna <= tfa;
               hk[2 * h + 1] = tnb <= tfb;
             }
-#elif YK_SLAB_PAIRS_F64
-            const f2 nx[2] = {slab_fma(qnx.xy, sxp), slab_fma(qnx.zw, sxp)};
-            const f2 fx[2] = {slab_fma(qfx.xy, fxp), slab_fma(qfx.zw, fxp)};
-            const f2 ny[2] = {slab_fma(qny.xy, syp), slab_fma(qny.zw, syp)};
-            const f2 fy[2] = {slab_fma(qfy.xy, fyp), slab_fma(qfy.zw, fyp)};
-            const f2 nz[2] = {slab_fma(qnz.xy, szp), slab_fma(qnz.zw, szp)};
-            const f2 fz[2] = {slab_fma(qfz.xy, fzp), slab_fma(qfz.zw, fzp)};
-#if YK_CULL_BLOCK
-            // two slots per asm block (yk_slab.hpp slab_cull2): the same instructions, fewer edges
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-              float tna, tfa, tnb, tfb;
-              slab_cull2(nx[h][0], ny[h][0], nz[h][0], fx[h][0], fy[h][0], fz[h][0], nx[h][1], ny[h][1], nz[h][1],
-                         fx[h][1], fy[h][1], fz[h][1], tmin_lo, ustar_f, tna, tfa, tnb, tfb);
-              hk[2 * h] = tna <= tfa;
-              hk[2 * h + 1] = tnb <= tfb;
-            }
-#else
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              const float tn = slab_max(slab_max3(nx[k >> 1][k & 1], ny[k >> 1][k & 1], nz[k >> 1][k & 1]), tmin_lo);
-              const float tf = slab_min(slab_min3(fx[k >> 1][k & 1], fy[k >> 1][k & 1], fz[k >> 1][k & 1]), ustar_f);
-              hk[k] = tn <= tf;
-            }
-#endif
-#else
-            const f2 nx[2] = {__builtin_elementwise_fma(qnx.xy, ixv, noix), __builtin_elementwise_fma(qnx.zw, ixv, noix)};
-            const f2 fx[2] = {__builtin_elementwise_fma(qfx.xy, ixc, noixc), __builtin_elementwise_fma(qfx.zw, ixc, noixc)};
-            const f2 ny[2] = {__builtin_elementwise_fma(qny.xy, iyv, noiy), __builtin_elementwise_fma(qny.zw, iyv, noiy)};
-            const f2 fy[2] = {__builtin_elementwise_fma(qfy.xy, iyc, noiyc), __builtin_elementwise_fma(qfy.zw, iyc, noiyc)};
-            const f2 nz[2] = {__builtin_elementwise_fma(qnz.xy, izv, noiz), __builtin_elementwise_fma(qnz.zw, izv, noiz)};
-            const f2 fz[2] = {__builtin_elementwise_fma(qfz.xy, izc, noizc), __builtin_elementwise_fma(qfz.zw, izc, noizc)};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              const float tn = fmaxf(fmaxf(fmaxf(nx[k >> 1][k & 1], ny[k >> 1][k & 1]), nz[k >> 1][k & 1]), tmin_lo);
-              const float tf = fminf(fminf(fminf(fx[k >> 1][k & 1], fy[k >> 1][k & 1]), fz[k >> 1][k & 1]), ustar_f);
-              hk[k] = tn <= tf;
-            }
-#endif
             // keep the child-code read in this block, issued with the plane reads (the compiler
             // would otherwise sink it into the branch below and wait for it there)
             asm volatile("" ::"v"(ch.x), "v"(ch.y), "v"(ch.z), "v"(ch.w));
-#if YK_NODE_BF
             {
               // the last slot entered is visited next, the others entered are pushed in slot
               // order; none entered: the popped entry is next and the top moves down one
@@ -1636,13 +1477,9 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
               top += (hk[2] && hk[3]) ? kBlk * 4u : (any ? 0u : 0u - kBlk * 4u);
               // stack full: the top stays at the capacity and nc = 5 sends the lane to the scan
               // (only where the plan could not give the stack its proven depth: ka.stack_check)
-#if YK_VISIT_UNSWITCH
-              if (decltype(chk)::value) {
-#else
               if (ka.stack_check) {
-#endif
                 asm volatile("");  // (a scalar branch: no selects on the uniform flag)
-                // signed: with YK_NODE_BF 2 the pop of the sentinel leaves `top` one entry below the
+                // signed: the pop of the sentinel leaves `top` (the entry below the top) one entry below the
                 // stack's base, below LDS address 0 for the low lanes of a scene with a small LDS
                 // copy (unsigned, that wrapped past the capacity and the lane never left the loop)
                 nc = (int32_t)top > (int32_t)stk_cap ? 5u : nc;
@@ -1650,49 +1487,8 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
               }
             }
            } while (node >= 0);
-#if YK_VISIT_UNSWITCH
-           };
-           if (ka.stack_check) visit_run(std::true_type{}); else visit_run(std::false_type{});
-#endif
-#else
-            if (hk[0] || hk[1] || hk[2] || hk[3]) {
-              // the last slot entered is visited next and the others entered are pushed, in slot
-              // order: no distance sort (visit order only affects how fast U* shrinks, never the
-              // result; modelled by tools/bvhsim, it costs ~1% more leaf tests and no node
-              // visits).  Each write lands at the current top, which moves only for a push.
-              node = hk[3] ? ch.w : (hk[2] ? ch.z : (hk[1] ? ch.y : ch.x));
-              *top = ch.x;
-              top += (hk[0] && (hk[1] || hk[2] || hk[3])) ? kBlk : 0;
-              *top = ch.y;
-              top += (hk[1] && (hk[2] || hk[3])) ? kBlk : 0;
-              *top = ch.z;
-              top += (hk[2] && hk[3]) ? kBlk : 0;
-              // stack full: the top stays at the capacity (the pushes above it are lost and the
-              // rest of this traversal is void) and nc = 5 marks the lane for the exact linear scan
-              if (top > stk_cap) {
-                top = stk + ka.stack_cap * kBlk;
-                nc = 5;
-              }
-              continue;
-            }
-            // no slot entered: pop here, inside the visit branch, so the lane goes on with the
-            // popped node in the next trip instead of waiting for every other lane of the wave to
-            // stop descending (512 spp: 180.8 -> 178.4 ms); an empty stack ends the traversal as
-            // the empty leaf (~0: no spheres)
-            if (top == stk) {
-              node = ykbvh::kEmptyLeaf;
-            } else {
-              top -= kBlk;
-              node = *top;
-            }
-            continue;
-#endif
-#if YK_NODE_BF
           }
           {
-#else
-          } else {
-#endif
             YK_STAMP(2);  // interior nodes since the last stamp
             const uint32_t v = ~(uint32_t)node, first = v >> 4, cnt = v & 15u;
             // the FP64 tree has one sphere per leaf (max_leaf = 1: the builder's median fallback
@@ -1716,12 +1512,7 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
               if (kCount) ++n_dpos;
               YK_STAMP_DISC_POS();
               // bounds of the exact root: |approx - exact| <= m (256x the error bound, §4)
-#if YK_CAND_HD && YK_CAND_RSQ
-              const double rq = __builtin_amdgcn_rsq(disc);
-              const double sq = ykd::sqrt_bound_r(disc, rq);
-#else
               const double sq = ykd::sqrt_bound(disc);
-#endif
               const double r1 = (-hb - sq) * ia, r2 = (-hb + sq) * ia;
               const double m = (fabs(hb) + sq) * ia * 0x1p-34 + 0x1p-1000;
               if (r2 + m < ka.t_min) continue;  // both roots certainly behind t_min
@@ -1730,32 +1521,22 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
               if (!(lb <= ustar)) continue;
               if (ub < ustar) {
                 ustar = ub;
-#if YK_SLAB_PAIRS_F64 && YK_NEAR_CLAMP
                 // s (RN(ub)(1 + 2^-18) - tmin_lo), rounded up by the factor 1 + 2^-22: >= s (the
                 // unshifted bound - tmin_lo), positive (ub >= t_min > tmin_lo)
                 ustar_f = ((float)ub * (1.0f + 0x1p-18f) - tmin_lo) * ((1.0f + 0x1p-22f) * kClampScale);
-#else
-                ustar_f = (float)ub * (1.0f + 0x1p-18f);
-#endif
               }
               if (nc == 4) {  // compact: drop entries the new bound has excluded
                 uint32_t m2 = 0;
-#if YK_CAND_PACK
                 uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
                 const uint32_t d0 = cp01 & 0xffffu, d1 = cp01 >> 16, d2 = cp23 & 0xffffu, d3 = cp23 >> 16;
-#else
-                uint32_t d0 = c0, d1 = c1, d2 = c2, d3 = c3;
-#endif
                 float e0 = l0, e1 = l1, e2 = l2, e3 = l3;
                 if (e0 <= ustar_f) { YK_CAND_SET(m2, d0, e0); ++m2; }
                 if (e1 <= ustar_f) { YK_CAND_SET(m2, d1, e1); ++m2; }
                 if (e2 <= ustar_f) { YK_CAND_SET(m2, d2, e2); ++m2; }
                 if (e3 <= ustar_f) { YK_CAND_SET(m2, d3, e3); ++m2; }
                 nc = m2;
-#if YK_CAND_PACK
                 cp01 = c0 | (c1 << 16);
                 cp23 = c2 | (c3 << 16);
-#endif
               }
               if (nc < 4) {
                 // shifted in at entry 0 — straight-line moves instead of a branch per list
@@ -1763,30 +1544,13 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
                 // RN(lb), not rounded down: t_min >= 0 (checked by the host) makes every lb and
                 // U* >= 0, and lb <= U* implies RN(lb) <= RN(U*) <= ustar_f (monotone rounding),
                 // so the list still keeps every sphere that can be the minimum
-#if YK_CAND_PACK
                 cp23 = __builtin_amdgcn_alignbit(cp23, cp01, 16u);  // (cp23 << 16) | (cp01 >> 16)
                 cp01 = (cp01 << 16) | id;
                 l3 = l2, l2 = l1, l1 = l0;
-#else
-                c3 = c2, l3 = l2, c2 = c1, l2 = l1, c1 = c0, l1 = l0;
-#endif
-#if YK_CAND_HD
                 hb0 = hb, disc0 = disc;
-#if YK_CAND_RSQ
-                rsq0 = rq;
-#endif
-#endif
-#if YK_SLAB_PAIRS_F64 && YK_NEAR_CLAMP
                 // the same monotone map as ustar_f's: s RN(RN(lb) - tmin_lo) (one FMA, s a power of
                 // two), so lb <= U* still implies l0 <= ustar_f
-#if YK_CAND_PACK
                 l0 = __builtin_fmaf((float)lb, kClampScale, -tmin_lo * kClampScale);
-#else
-                c0 = id, l0 = __builtin_fmaf((float)lb, kClampScale, -tmin_lo * kClampScale);
-#endif
-#else
-                c0 = id, l0 = (float)lb;
-#endif
                 ++nc;
               } else {
                 nc = 5;  // the list is full: overflow (the exact linear scan decides)
@@ -1794,16 +1558,10 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
             } while (0);
             YK_STAMP(6);  // this leaf
           }
-#if YK_NODE_BF
           if (top + kTopOff <= stk_b + kBlk * 4u) break;  // only the sentinel left, or the sentinel just visited
           top -= kBlk * 4u;
           node = YK_STK(top + kTopOff);
 #undef YK_STK
-#else
-          if (top == stk) break;
-          top -= kBlk;
-          node = *top;
-#endif
         }
         YK_STAMP(2);
         if (nc > 4) {
@@ -1812,25 +1570,9 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
           // exact evaluation of the survivors; the roots' divisor a is the same for every
           // candidate of a ray, so its refined reciprocal is computed once
           const bool a_ok = ykd::div_range(a);
-#if YK_RA_FROM_IA
-          // rcp_refined(a)'s first Newton step is rcp_bound(a) = ia, bit for bit (the same rcp and
-          // fmas): the second step alone (YK_RA_FROM_IA)
-          const double ra = (nc > 0 && a_ok) ? __builtin_fma(ia, __builtin_fma(-a, ia, 1.0), ia) : 0.0;
-#else
           const double ra = (nc > 0 && a_ok) ? ykd::rcp_refined(a) : 0.0;
-#endif
-#if YK_CAND_HD
-#if YK_CAND_PACK
           const uint32_t c0 = cp01 & 0xffffu, c1 = cp01 >> 16, c2 = cp23 & 0xffffu, c3 = cp23 >> 16;
-#endif
-#if YK_CAND_RSQ
-          if (nc > 0 && l0 <= ustar_f) exact_root(c0, hb0, disc0, a, ra, a_ok, ka.t_min, hit, &rsq0);
-#else
           if (nc > 0 && l0 <= ustar_f) exact_root(c0, hb0, disc0, a, ra, a_ok, ka.t_min, hit);
-#endif
-#else
-          if (nc > 0 && l0 <= ustar_f) exact_candidate(geo, c0, o, d, a, ra, a_ok, ka.t_min, hit);
-#endif
           if (nc > 1 && l1 <= ustar_f) exact_candidate(geo, c1, o, d, a, ra, a_ok, ka.t_min, hit);
           if (nc > 2 && l2 <= ustar_f) exact_candidate(geo, c2, o, d, a, ra, a_ok, ka.t_min, hit);
           if (nc > 3 && l3 <= ustar_f) exact_candidate(geo, c3, o, d, a, ra, a_ok, ka.t_min, hit);
@@ -1939,14 +1681,10 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
         } else {  // dielectric extension (attenuation (1,1,1): multiplying by 1.0 is exact)
           if (kCount) ++n_diel;
           push = false;
-#if YK_DIEL_PRE
           // 1/ior and Schlick's r0 of both sides precomputed on the host with the same IEEE
           // operations (ykgpu_set_scene: the dielectric's unused fuzz / albedo fields)
           const double ratio = front ? m.fuzz : m.ior;
           const double r0 = front ? m.ar : m.ag;
-#else
-          const double ratio = front ? (1.0 / m.ior) : m.ior;
-#endif
           const v3 unit = un;
           const double sn = sq2;
           const bool cannot = ratio * sn > 1.0;
@@ -1956,11 +1694,7 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
           } else {
             u = spec ? ykd::uniform_of(c0, 0, 1) : ykd::uniform(g, 0, 1);
           }
-#if YK_DIEL_PRE
           if (cannot || ykd::reflectance_r0(ct, r0) > u) {
-#else
-          if (cannot || ykd::reflectance(ct, ratio) > u) {
-#endif
             nd = ykd::reflect(unit, nrm);
           } else {
             const v3 perp = ykd::mul(ykd::add(unit, ykd::mul(nrm, ct)), ratio);
@@ -1998,7 +1732,6 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
         --nstk;
         return id;
       };
-#if YK_UNWIND_FAST
       if (__ballot(nstk > kStackRegs) == 0) {
         // no ending lane of the wave holds spilled ids: the register window alone, two ids per
         // round (the window moves by a whole register)
@@ -2016,13 +1749,13 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
           st0 = st1, st1 = st2, st2 = st3;
           nstk = nstk > 1 ? nstk - 2 : 0;
         }
-      } else
-#endif
-      while (nstk > 0) {
-        const SphereMat m = mat[pop()];
-        L_r = m.ar * L_r;
-        L_g = m.ag * L_g;
-        L_b = m.ab * L_b;
+      } else {
+        while (nstk > 0) {
+          const SphereMat m = mat[pop()];
+          L_r = m.ar * L_r;
+          L_g = m.ag * L_g;
+          L_b = m.ab * L_b;
+        }
       }
       if (ykd::mt_used_fallback(g)) ++n_fb;
       if (kCount) n_words += ykd::rng_words(g), n_twist += ykd::rng_twists(g);
@@ -2054,29 +1787,14 @@ __device__ __forceinline__ void render_body(KernelArgs ka) {
     atomicAdd(&ka.counters[31], (unsigned long long)n_twist);
   }
   if (n_fb) atomicAdd(&ka.counters[3], (unsigned long long)n_fb);
-#if YK_WG_HOLD
-  // (A/B) the workgroup's waves leave together: a wave without work keeps its registers until the
-  // last one is done, so the CU frees whole and the next launch's workgroup is not starved by the
-  // warm-up's small workgroups taking the registers piecemeal
-  if constexpr (kMode == 0) __syncthreads();
-#endif
 }
-
 
 // The kernels.  Production instances at <= YK_RENDER_VGPRS (gfx950's amdgpu_num_vgpr counts the
 // unified file, so the attribute takes half).
 template <bool kSceneInLds, int kMode>
 __global__ __launch_bounds__(mode_block<kMode>())
-#if YK_WAVES_PER_EU
-__attribute__((amdgpu_waves_per_eu(YK_WAVES_PER_EU, YK_WAVES_PER_EU)))
-#else
 __attribute__((amdgpu_waves_per_eu(4, 8)))
-#endif
-#ifdef YK_SINGLE_VGPRS
-__attribute__((amdgpu_num_vgpr(YK_SINGLE_VGPRS / 2)))  // (A/B)
-#else
 __attribute__((amdgpu_num_vgpr(YK_RENDER_VGPRS / 2)))
-#endif
 void yk_render_persistent(KernelArgs ka) {
   render_body<kSceneInLds, kMode>(ka);
 }
@@ -2176,17 +1894,11 @@ __device__ __forceinline__ void cone_axis(float dk, float ok, float s, f2& in2, 
   const bool far = fabsf(dk) >= kF32FarAt * s;
   const float jf = far ? __builtin_amdgcn_rcpf(dk - sg) * (1.0f + 0x1p-17f) : 0.0f;
   const float nc = -(ok * in), fc = far ? -(ok * jf) : INFINITY;
-#if YK_SLAB_PAIRS_F32
-  // the pairs (in, nc) and (jf, fc), read by op_sel (yk_slab.hpp); nc2 / fc2 unused
+  // the pairs (in, nc) and (jf, fc), read by op_sel (yk_slab.hpp); nc2 / fc2 are unused (dropping
+  // the two dead parameters changes the FP32 kernels' schedule)
   in2 = f2{in, nc};
   jf2 = f2{jf, fc};
   nc2 = fc2 = f2{0.0f, 0.0f};
-#else
-  in2 = f2{in, in};
-  nc2 = f2{nc, nc};
-  jf2 = f2{jf, jf};
-  fc2 = f2{fc, fc};
-#endif
 }
 
 // kSceneInLds: the FP32 tree, its float4 leaf geometry and its leaf ids copied into LDS per
@@ -2226,9 +1938,7 @@ void yk_render_f32(KernelArgs ka) {
     mat = (const SphereMat*)(smem + ka.lds_mat_off);
   }
   int32_t* const stk = (int32_t*)(smem + ka.lds_stack_off) + threadIdx.x;  // [sp * kBlk]
-#if YK_RENDER_PRIO
-  __builtin_amdgcn_s_setprio(YK_RENDER_PRIO);  // over the co-resident warm-up waves, as in FP64
-#endif
+  __builtin_amdgcn_s_setprio(1);  // over the co-resident warm-up waves, as in FP64
   YK_CLOCK_BEGIN(ka);
   Gen g;
   rng_init(g, ka, gid);
@@ -2349,11 +2059,7 @@ void yk_render_f32(KernelArgs ka) {
         // bound like a near distance (same FMA form and error).  Without it, a
         // ray grazing a field of boxes enters every box under its path.  One slow axis per ray
         // gets the bound (y, then x, then z); the others keep L = -inf.
-#if YK_SLAB_PAIRS_F32
         f2 jl2 = {0.0f, -INFINITY};  // the (jl, cl) pair
-#else
-        f2 jl2 = {0.0f, 0.0f}, cl2 = {-INFINITY, -INFINITY};
-#endif
         const char* pl = px + 16;
         {
           const float slow = s * kF32SlowAt;
@@ -2363,12 +2069,7 @@ void yk_render_f32(KernelArgs ka) {
           for (int k = 0; k < 3; ++k) {
             if (fabsf(dk[k]) < slow) {
               const float jl = __builtin_amdgcn_rcpf(dk[k] - (dk[k] < 0.0f ? -s : s));
-#if YK_SLAB_PAIRS_F32
               jl2 = f2{jl, -(ok[k] * jl)};  // (jl, cl), read by op_sel
-#else
-              jl2 = f2{jl, jl};
-              cl2 = f2{-(ok[k] * jl), -(ok[k] * jl)};
-#endif
               pl = pk[k] + 16;
             }
           }
@@ -2393,7 +2094,6 @@ void yk_render_f32(KernelArgs ka) {
             const f4 qnz = *(const f4*)(pz + node), qfz = *(const f4*)(pz + node + 16);
             const int4 ch = *(const int4*)(nodes + node + 144);
             bool hk[4];
-#if YK_SLAB_PAIRS_F32
             const f2 nx[2] = {slab_fma(qnx.xy, inx), slab_fma(qnx.zw, inx)};
             const f2 fx[2] = {slab_fma(qfx.xy, jfx), slab_fma(qfx.zw, jfx)};
             const f2 ny[2] = {slab_fma(qny.xy, iny), slab_fma(qny.zw, iny)};
@@ -2409,24 +2109,6 @@ void yk_render_f32(KernelArgs ka) {
               const float tf = slab_min(slab_min3(fx[k >> 1][k & 1], fy[k >> 1][k & 1], fz[k >> 1][k & 1]), ustar_f);
               hk[k] = tn <= tf;
             }
-#else
-            const f4 qsl = *(const f4*)(pl + node);
-            const f2 nx[2] = {__builtin_elementwise_fma(qnx.xy, inx, ncx), __builtin_elementwise_fma(qnx.zw, inx, ncx)};
-            const f2 fx[2] = {__builtin_elementwise_fma(qfx.xy, jfx, fcx), __builtin_elementwise_fma(qfx.zw, jfx, fcx)};
-            const f2 ny[2] = {__builtin_elementwise_fma(qny.xy, iny, ncy), __builtin_elementwise_fma(qny.zw, iny, ncy)};
-            const f2 fy[2] = {__builtin_elementwise_fma(qfy.xy, jfy, fcy), __builtin_elementwise_fma(qfy.zw, jfy, fcy)};
-            const f2 nz[2] = {__builtin_elementwise_fma(qnz.xy, inz, ncz), __builtin_elementwise_fma(qnz.zw, inz, ncz)};
-            const f2 fz[2] = {__builtin_elementwise_fma(qfz.xy, jfz, fcz), __builtin_elementwise_fma(qfz.zw, jfz, fcz)};
-            const f2 sl[2] = {__builtin_elementwise_fma(qsl.xy, jl2, cl2), __builtin_elementwise_fma(qsl.zw, jl2, cl2)};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              // (a chain: two v_max3)
-              const float tn = fmaxf(fmaxf(fmaxf(fmaxf(nx[k >> 1][k & 1], ny[k >> 1][k & 1]), nz[k >> 1][k & 1]),
-                                           sl[k >> 1][k & 1]), tmin_lo);
-              const float tf = fminf(fminf(fminf(fx[k >> 1][k & 1], fy[k >> 1][k & 1]), fz[k >> 1][k & 1]), ustar_f);
-              hk[k] = tn <= tf;
-            }
-#endif
             asm volatile("" ::"v"(ch.x), "v"(ch.y), "v"(ch.z), "v"(ch.w));
             if (hk[0] || hk[1] || hk[2] || hk[3]) {
               node = hk[3] ? ch.w : (hk[2] ? ch.z : (hk[1] ? ch.y : ch.x));
@@ -2734,6 +2416,114 @@ RenderKernel f32_kernel(bool lds, int mode) { return (RenderKernel)yk_split_f32_
 // =========================================================================================
 // C-ABI
 // =========================================================================================
+// ---- Host-side tuning constants (each overridable with -DYK_...; the kernels' are at the top of
+// the file) ----
+#ifndef YK_LAUNCH_MB
+#define YK_LAUNCH_MB 8192
+#endif
+// colour records of one launch at most: bounds a launch's slots for very large tiles (kmax in
+// launch())
+constexpr uint64_t kLaunchBytes = (uint64_t)YK_LAUNCH_MB << 20;
+// the render kernel addresses a slot's start record as 4 * slot uint4s (FP32: 3) in 32-bit
+// arithmetic
+static_assert(kLaunchBytes / (8 * kColStride) * 4 < (1ull << 32), "4 * slot must fit 32 bits");
+// samples per pixel per launch at most: many mid-sized launches beat a few big ones, because the
+// launches alternate between two streams and each one's drain overlaps the next one's start
+// (DESIGN.md §8: round 1, 1920x1080x512 259.5 -> 254.0 ms at 64 spp/launch; with the render
+// streams at top priority, bench 205.5 ms at 64, 199.6 at 32, 199.8 at 24, 206.3 at 16)
+#ifndef YK_LAUNCH_SPP
+#define YK_LAUNCH_SPP 32
+#endif
+constexpr uint32_t kLaunchSpp = YK_LAUNCH_SPP;
+// ... and for a call enqueued while the previous one still runs (launch() `inflight`): its launches
+// need no ramp and overlap the calls around them, so the per-launch handover is what is left, and
+// half as many launches pay it (frame: 8 of 64 instead of 16 of 32: bench -1.7%); a synced call
+// keeps kLaunchSpp (64 there cost it 2%: the 64-spp warm-up under the ramp's 32-spp render and a
+// longer last launch alone on the device, profiles/r06_ab/shade/).  The rings hold the larger
+// launch in both, so a synced call and the in-flight calls after it share one ring geometry.
+#ifndef YK_LAUNCH_SPP_OV
+#define YK_LAUNCH_SPP_OV 64
+#endif
+constexpr uint32_t kLaunchSppOv = YK_LAUNCH_SPP_OV;
+// ... or spp / kLaunchesPerCall when that is more (a long call: launch())
+#ifndef YK_LAUNCHES_PER_CALL
+#define YK_LAUNCHES_PER_CALL 32
+#endif
+constexpr uint32_t kLaunchesPerCall = YK_LAUNCHES_PER_CALL;
+// ... and launches of about kLaunchSlots sample slots when the tile is small: a launch has a fixed
+// cost (the handover of every CU from its render workgroup to the next launch's, filled by seed
+// walks: ~0.2 ms per launch, DESIGN.md §3), so a call is split into round(slots / kLaunchSlots)
+// launches — the frame's 32-spp launches are 66M slots, and a tile's launches are as large (the
+// 8-way tile of 1920x1080x512: 2 launches of 256 spp; with 2^25-slot launches, 4 of 128, its
+// back-to-back calls cost 2% more per sample than the frame's, profiles/r06_ab/tiles/)
+#ifndef YK_LAUNCH_SLOTS
+#define YK_LAUNCH_SLOTS (1u << 26)
+#endif
+constexpr uint64_t kLaunchSlots = YK_LAUNCH_SLOTS;
+// ... and of about kLaunchSlotsOv for an in-flight call (as kLaunchSppOv for the frame), never
+// fewer than two launches where a synced call has two: the 4-way tile 38.73 -> 38.59 ms, the 2-way
+// 76.73 -> 76.18, config 4's 8-way 153.78 -> 153.10, the 8-way unchanged (profiles/r06_ab/tiles/r06ae_*)
+#ifndef YK_LAUNCH_SLOTS_OV
+#define YK_LAUNCH_SLOTS_OV (1u << 27)
+#endif
+constexpr uint64_t kLaunchSlotsOv = YK_LAUNCH_SLOTS_OV;
+// global launch numbers whose dependency events (ykgpu_context::gev) are kept: more than any ring
+// is deep
+constexpr uint32_t kDepRing = 16;
+// Under memory pressure (launch()): launches shrink down to this many sample slots before a call
+// fails with YK_ERR_NOMEM, and the rings leave kMemReserve of the device free
+constexpr uint64_t kMemFloorSlots = 1ull << 24;
+constexpr size_t kMemReserve = (size_t)512 << 20;
+// Start-record ring: the warm-ups run on ctx->aux, beside the render launches (their wave slots
+// and VGPRs fit next to the render kernel's, and the render leaves most VALU issue slots idle),
+// into a ring of min(launches, kWarmRingDepth) launch buffers (YKGPU_WARM_RING overrides); warm-up
+// c waits for the render of launch c - ring.  Sized to the call: ring x slots x record (1920x1080
+// at 32 spp per launch: 66M slots x 64 B = 4.2 GB per launch buffer).
+#ifndef YK_WARM_RING
+#define YK_WARM_RING 3
+#endif
+constexpr uint32_t kWarmRingDepth = YK_WARM_RING;
+#ifndef YK_FIRST_LAUNCH
+#define YK_FIRST_LAUNCH 4
+#endif
+constexpr uint32_t kFirstLaunch = YK_FIRST_LAUNCH;  // samples per pixel in the first launch
+// ... and each next launch grows by this factor until kmax: 4, 8, 16, 32, 32, ... (1920x1080x512:
+// 4 + 8 + 16 + 14 x 32 + 18 + 18 = 512 spp in 19 launches).  Before round 4: 8, 32, 32, ...; its second
+// warm-up (32 spp of walks beside the first render) sometimes finished late and delayed every
+// launch after it: 20 synced calls on one box spread 173.6-177.4 ms (max/min 1.022), against
+// 173.6-174.6 (1.0059) with 4, 8, 16 (tools/variance_ab.py, profiles/r04_ab/variance/)
+#ifndef YK_SCHED_GROW
+#define YK_SCHED_GROW 2
+#endif
+constexpr uint32_t kSchedGrow = YK_SCHED_GROW;
+// ... and for a call enqueued while the previous one still runs (launch(): `inflight`): every
+// launch at kmax (YK_FIRST_LAUNCH_OV 0; else that many samples per pixel first, growing by
+// YK_SCHED_GROW_OV)
+#ifndef YK_FIRST_LAUNCH_OV
+#define YK_FIRST_LAUNCH_OV 0
+#endif
+#ifndef YK_SCHED_GROW_OV
+#define YK_SCHED_GROW_OV 4
+#endif
+constexpr uint32_t kFirstLaunchOv = YK_FIRST_LAUNCH_OV, kSchedGrowOv = YK_SCHED_GROW_OV;
+static_assert(YK_FIRST_LAUNCH >= 1 && YK_LAUNCH_SPP >= 1, "launch sizes must be >= 1 sample per pixel");
+#ifndef YK_TILE
+#define YK_TILE 8
+#endif
+constexpr uint32_t kTile = YK_TILE;  // processing blocks of kTile x kTile pixels (0: row-major)
+// colour buffers in flight (col_ring())
+#ifndef YK_COL_RING
+#define YK_COL_RING 2
+#endif
+// FP64 warm-up grid: blocks per CU (warm_per_cu(); each thread walks n / grid slots, at least kWarmSlots)
+#ifndef YK_WARM_PER_CU
+#define YK_WARM_PER_CU 32
+#endif
+#ifndef YK_WARM_SLOTS
+#define YK_WARM_SLOTS 4
+#endif
+constexpr uint32_t kWarmSlots = YK_WARM_SLOTS;
+
 // A BVH on the device: the FP64 kernel's (boxes grown for the exact test's rounding, DESIGN.md
 // §4) or the FP32 kernel's (grown for render<float>'s sphere test, §4.1), with its LDS layout
 // [nodes][leaf geometry][leaf ids][traversal stacks] and the persistent grid it leaves room for.
@@ -2986,111 +2776,6 @@ int ensure_scratch(ykgpu_context* ctx, uint32_t max_depth, size_t lanes, bool ne
   return YK_OK;
 }
 
-#ifndef YK_LAUNCH_MB
-#define YK_LAUNCH_MB 8192
-#endif
-// colour records of one launch at most: bounds a launch's slots for very large tiles (kmax in
-// launch())
-constexpr uint64_t kLaunchBytes = (uint64_t)YK_LAUNCH_MB << 20;
-// the render kernel addresses a slot's start record as 4 * slot uint4s (FP32: 3) in 32-bit
-// arithmetic
-static_assert(kLaunchBytes / (8 * kColStride) * 4 < (1ull << 32), "4 * slot must fit 32 bits");
-// samples per pixel per launch at most: many mid-sized launches beat a few big ones, because the
-// launches alternate between two streams and each one's drain overlaps the next one's start
-// (DESIGN.md §8: round 1, 1920x1080x512 259.5 -> 254.0 ms at 64 spp/launch; with the render
-// streams at top priority, bench 205.5 ms at 64, 199.6 at 32, 199.8 at 24, 206.3 at 16)
-#ifndef YK_LAUNCH_SPP
-#define YK_LAUNCH_SPP 32
-#endif
-constexpr uint32_t kLaunchSpp = YK_LAUNCH_SPP;
-// ... and for a call enqueued while the previous one still runs (launch() `inflight`): its launches
-// need no ramp and overlap the calls around them, so the per-launch handover is what is left, and
-// half as many launches pay it (frame: 8 of 64 instead of 16 of 32: bench -1.7%); a synced call
-// keeps kLaunchSpp (64 there cost it 2%: the 64-spp warm-up under the ramp's 32-spp render and a
-// longer last launch alone on the device, profiles/r06_ab/shade/).  The rings hold the larger
-// launch in both, so a synced call and the in-flight calls after it share one ring geometry.
-#ifndef YK_LAUNCH_SPP_OV
-#define YK_LAUNCH_SPP_OV 64
-#endif
-constexpr uint32_t kLaunchSppOv = YK_LAUNCH_SPP_OV;
-// ... or spp / kLaunchesPerCall when that is more (a long call: launch())
-#ifndef YK_LAUNCHES_PER_CALL
-#define YK_LAUNCHES_PER_CALL 32
-#endif
-constexpr uint32_t kLaunchesPerCall = YK_LAUNCHES_PER_CALL;
-// ... and launches of about kLaunchSlots sample slots when the tile is small: a launch has a fixed
-// cost (the handover of every CU from its render workgroup to the next launch's, filled by seed
-// walks: ~0.2 ms per launch, DESIGN.md §3), so a call is split into round(slots / kLaunchSlots)
-// launches — the frame's 32-spp launches are 66M slots, and a tile's launches are as large (the
-// 8-way tile of 1920x1080x512: 2 launches of 256 spp; with 2^25-slot launches, 4 of 128, its
-// back-to-back calls cost 2% more per sample than the frame's, profiles/r06_ab/tiles/)
-#ifndef YK_LAUNCH_SLOTS
-#define YK_LAUNCH_SLOTS (1u << 26)
-#endif
-constexpr uint64_t kLaunchSlots = YK_LAUNCH_SLOTS;
-// ... and of about kLaunchSlotsOv for an in-flight call (as kLaunchSppOv for the frame), never
-// fewer than two launches where a synced call has two: the 4-way tile 38.73 -> 38.59 ms, the 2-way
-// 76.73 -> 76.18, config 4's 8-way 153.78 -> 153.10, the 8-way unchanged (profiles/r06_ab/tiles/r06ae_*)
-#ifndef YK_LAUNCH_SLOTS_OV
-#define YK_LAUNCH_SLOTS_OV (1u << 27)
-#endif
-constexpr uint64_t kLaunchSlotsOv = YK_LAUNCH_SLOTS_OV;
-// (A/B) an in-flight call of one launch keeps the rings' full depth, so consecutive one-launch calls
-// overlap like the launches of one call, and the floor of two launches goes
-#ifndef YK_INFLIGHT_DEEP
-#define YK_INFLIGHT_DEEP 0
-#endif
-constexpr bool kInflightDeep = YK_INFLIGHT_DEEP != 0;
-// global launch numbers whose dependency events (ykgpu_context::gev) are kept: more than any ring
-// is deep
-constexpr uint32_t kDepRing = 16;
-// Under memory pressure (launch()): launches shrink down to this many sample slots before a call
-// fails with YK_ERR_NOMEM, and the rings leave kMemReserve of the device free
-constexpr uint64_t kMemFloorSlots = 1ull << 24;
-constexpr size_t kMemReserve = (size_t)512 << 20;
-// Start-record ring: the warm-ups run on ctx->aux, beside the render launches (their wave slots
-// and VGPRs fit next to the render kernel's, and the render leaves most VALU issue slots idle),
-// into a ring of min(launches, kWarmRingDepth) launch buffers (YKGPU_WARM_RING overrides); warm-up
-// c waits for the render of launch c - ring.  Sized to the call: ring x slots x record (1920x1080
-// at 32 spp per launch: 66M slots x 64 B = 4.2 GB per launch buffer).
-#ifndef YK_WARM_RING
-#define YK_WARM_RING 3
-#endif
-constexpr uint32_t kWarmRingDepth = YK_WARM_RING;
-#ifndef YK_FIRST_LAUNCH
-#define YK_FIRST_LAUNCH 4
-#endif
-constexpr uint32_t kFirstLaunch = YK_FIRST_LAUNCH;  // samples per pixel in the first launch
-// ... and each next launch grows by this factor until kmax: 4, 8, 16, 32, 32, ... (1920x1080x512:
-// 4 + 8 + 16 + 14 x 32 + 18 + 18 = 512 spp in 19 launches).  Before round 4: 8, 32, 32, ...; its second
-// warm-up (32 spp of walks beside the first render) sometimes finished late and delayed every
-// launch after it: 20 synced calls on one box spread 173.6-177.4 ms (max/min 1.022), against
-// 173.6-174.6 (1.0059) with 4, 8, 16 (tools/variance_ab.py, profiles/r04_ab/variance/)
-#ifndef YK_SCHED_GROW
-#define YK_SCHED_GROW 2
-#endif
-constexpr uint32_t kSchedGrow = YK_SCHED_GROW;
-// ... and by half from this many samples per pixel on (0: kSchedGrow throughout)
-#ifndef YK_SCHED_SLOW
-#define YK_SCHED_SLOW 0
-#endif
-constexpr uint32_t kSchedSlow = YK_SCHED_SLOW;
-// ... and for a call enqueued while the previous one still runs (launch(): `inflight`): every
-// launch at kmax (YK_FIRST_LAUNCH_OV 0; else that many samples per pixel first, growing by
-// YK_SCHED_GROW_OV)
-#ifndef YK_FIRST_LAUNCH_OV
-#define YK_FIRST_LAUNCH_OV 0
-#endif
-#ifndef YK_SCHED_GROW_OV
-#define YK_SCHED_GROW_OV 4
-#endif
-constexpr uint32_t kFirstLaunchOv = YK_FIRST_LAUNCH_OV, kSchedGrowOv = YK_SCHED_GROW_OV;
-static_assert(YK_FIRST_LAUNCH >= 1 && YK_LAUNCH_SPP >= 1, "launch sizes must be >= 1 sample per pixel");
-#ifndef YK_TILE
-#define YK_TILE 8
-#endif
-constexpr uint32_t kTile = YK_TILE;  // processing blocks of kTile x kTile pixels (0: row-major)
-
 // The processing order of a tile of W x rows pixels (kernel comment at kNoPixel).  A function of
 // the geometry only, so it is built once per size and kept on the device.  Blocks hold 64 tile
 // pixels; for a tile of every stride-th image row (the N-GPU split) they are widened and
@@ -3164,12 +2849,6 @@ hipError_t create_render_stream(hipStream_t* s) {
 // ends long before the render after next needs its buffer; rings of 2 / 3 / 4 time the same
 // (bench 171.8 / 171.8 / 172.1 ms; config-4 rank tile 174.0 vs 173.6 ms, profiles/r04_ab/rings/)
 // and 2 holds 4.2 GB less at the headline size (call_bytes 22.3 -> 18.1 GB)
-#ifndef YK_COL_RING
-#define YK_COL_RING 2
-#endif
-#ifndef YK_RED_PRIO
-#define YK_RED_PRIO 0
-#endif
 uint32_t col_ring() {
   uint32_t r = YK_COL_RING;
   if (const char* e = ab_knob("YKGPU_COL_RING")) r = (uint32_t)std::max(2, std::min(8, std::atoi(e)));
@@ -3190,14 +2869,6 @@ uint32_t reduce_blocks(const ykgpu_context* ctx, uint32_t nps) {
 // path and takes every idle issue slot it can (32; 16: neutral, 8: +1.8%); the FP32 one has
 // slack, and each resident warm-up wave delays the latency-bound render waves it shares a SIMD
 // with (512-spp FP32 A/B: 32 -> 205.2 ms, 4 -> 202.4, 3 -> 202.4, 2 -> 201.3)
-// FP64 warm-up grid: blocks per CU (each thread walks n / grid slots, at least kWarmSlots)
-#ifndef YK_WARM_PER_CU
-#define YK_WARM_PER_CU 32
-#endif
-#ifndef YK_WARM_SLOTS
-#define YK_WARM_SLOTS 4
-#endif
-constexpr uint32_t kWarmSlots = YK_WARM_SLOTS;
 uint32_t warm_per_cu(bool f32) {
   uint32_t per_cu = f32 ? 2u : (uint32_t)YK_WARM_PER_CU;
   if (const char* e = ab_knob("YKGPU_WARM_PER_CU")) per_cu = (uint32_t)std::max(1, std::atoi(e));
@@ -3206,12 +2877,9 @@ uint32_t warm_per_cu(bool f32) {
 // A warm-up's blocks for n slots, at most cap: each thread walks n / grid slots, at least
 // kWarmSlots; with ilp walks per lane the grid is trimmed so that a thread's slot count is a
 // multiple of ilp (no lane walks a chain for a slot it does not have, but in the last blocks)
-#ifndef YK_WARM_TRIM
-#define YK_WARM_TRIM 1
-#endif
 inline uint32_t warm_blocks_for(uint64_t n, uint64_t cap, uint32_t ilp) {
   uint64_t wb = std::min<uint64_t>((n + 256 * kWarmSlots - 1) / (256 * kWarmSlots), cap);
-  if (YK_WARM_TRIM && ilp > 1 && wb > 0) {
+  if (ilp > 1 && wb > 0) {
     const uint64_t per = 256ull * ilp, it = (n + wb * per - 1) / (wb * per);
     wb = (n + per * it - 1) / (per * it);
   }
@@ -3270,11 +2938,11 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
     return std::max<uint64_t>(1, ((uint64_t)nps * spp + lslots / 2) / lslots);
   };
   // (in flight: never fewer than two launches where a synced call has two — a one-launch call has
-  // rings of one buffer and overlaps nothing: the 8-way tile 19.6 -> 25.5 ms, r06ad)
+  // rings of one buffer and overlaps nothing: the 8-way tile 19.6 -> 25.5 ms, r06ad; one launch
+  // with the rings' full depth kept instead: +1.5%, profiles/r06_ab/tiles/r06al_*)
   const uint64_t call_launches = launches_for(launch_slots);
   const uint64_t call_launches_ov =
-      kInflightDeep ? launches_for(std::max(launch_slots, kLaunchSlotsOv))
-                    : std::max(std::min<uint64_t>(call_launches, 2), launches_for(std::max(launch_slots, kLaunchSlotsOv)));
+      std::max(std::min<uint64_t>(call_launches, 2), launches_for(std::max(launch_slots, kLaunchSlotsOv)));
   const uint64_t slot_spp = (spp + call_launches - 1) / call_launches;
   const uint64_t slot_spp_ov = (spp + call_launches_ov - 1) / call_launches_ov;
   // A long call takes longer launches: every launch pays a drain whose length is the longest path
@@ -3367,10 +3035,9 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
         take = spp - s0 <= kcap ? spp - s0 : (spp - s0 + 1) / 2;
       sched.emplace_back(s_begin + s0, take);
       s0 += take;
-      // past kSchedSlow spp the ramp grows by half: a warm-up twice its render's size no longer
-      // hides under it (64-spp launches: the 64-spp warm-up under the 32-spp render cost the
-      // synced call 2%, profiles/r06_ab/shade/r06z_*)
-      k = std::min(kSchedSlow && k >= kSchedSlow ? k + k / 2 : grow_k * k, kcap);
+      // (a ramp growing by half past 32 or 16 spp did not recover the synced call of 64-spp
+      // launches: profiles/r06_ab/shade/r06z_*, r06aa_*)
+      k = std::min(grow_k * k, kcap);
     }
     // a launch buffer of the rings holds kmax samples per pixel (every launch fits: above)
     K = kmax;
@@ -3378,13 +3045,13 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
     // rings as deep as kWarmRingDepth / col_ring() whatever the call's launch count (a call of two
     // launches reuses the buffers of the call before it, launch() `ov`); one buffer each for a
     // single-launch call
-    kWarmRing = nlaunch > 1 || (kInflightDeep && inflight) ? kWarmRingDepth : 1;
+    kWarmRing = nlaunch > 1 ? kWarmRingDepth : 1;
     if (const char* e = ab_knob("YKGPU_WARM_RING"))  // (A/B) launch buffers in the ring
       kWarmRing = (uint32_t)std::min<uint64_t>(kDepRing - 1, (uint64_t)std::max(2, std::atoi(e)));
     if (warm_first) kWarmRing = nlaunch;
     // colour buffers: render c writes buffer c % ring and waits for the reduce of launch c - ring;
     // reduce c (stream red) overlaps the renders after it
-    kColRing = nlaunch > 1 || (kInflightDeep && inflight) ? std::min(col_ring(), kDepRing - 1) : 1;
+    kColRing = nlaunch > 1 ? std::min(col_ring(), kDepRing - 1) : 1;
     const size_t need_warm = x128 ? 0 : (size_t)kWarmRing * nps * K * welem;
     const size_t need_col = (size_t)kColRing * nps * K * kColStride * sizeof(double);
     if (kmax > kfloor && (need_warm > ctx->warm_cap || need_col > ctx->col_cap * sizeof(double))) {
@@ -3414,7 +3081,7 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
   // such launch (the frame's 32-spp launches: 640 records, 1.0 GB); longer launches run the
   // rejection loop in line (config 5's 121-spp launches: 7600 slots per wave, where the deferral
   // measured 0.7% slower)
-  const bool lens_defer = kLensDefer && !x128 && !f32 && ctx->cam.lens_radius > 0;
+  const bool lens_defer = !x128 && !f32 && ctx->cam.lens_radius > 0;
   auto wave_slots = [&](uint64_t nl) {
     const uint64_t wb = warm_blocks_for(nl, (uint64_t)ctx->cus * warm_per_cu(false), kWalkIlp);
     return (nl + wb * 256 - 1) / (wb * 256) * 64;
@@ -3667,7 +3334,7 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
     wa.out = ctx->d_warm + (size_t)((g0 + c) % kWarmRing) * nps * K * welem;
     wa.counter = ctx->d_counter + (g0 + c) % kWarmRing;
     const bool defer = !x128 && !f32 && wa.lens && wa.retry_cap && wave_slots(wa.n) <= kDeferSlots;
-    const uint32_t wblocks = warm_blocks_for(wa.n, (uint64_t)ctx->cus * warm_per_cu(f32), defer ? kWalkIlp : kWalkIlpInline);
+    const uint32_t wblocks = warm_blocks_for(wa.n, (uint64_t)ctx->cus * warm_per_cu(f32), defer ? kWalkIlp : 1u);
     YK_HIP(hipEventRecord(ev[0], ctx->aux));
     if (!x128) {
       if (f32 && wa.lens)
@@ -4051,11 +3718,7 @@ int ykgpu_context_create(int device, ykgpu_context** out) {
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
       hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking) != hipSuccess ||
-#if YK_RED_PRIO
-      create_render_stream(&ctx->red) != hipSuccess ||  // (A/B: the reduces at the renders' priority)
-#else
       hipStreamCreateWithFlags(&ctx->red, hipStreamNonBlocking) != hipSuccess ||
-#endif
       create_render_stream(&ctx->alt) != hipSuccess || create_render_stream(&ctx->ren) != hipSuccess ||
       hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess ||
       hipMalloc(&ctx->d_stats, kCounters * sizeof(unsigned long long)) != hipSuccess) {
@@ -4116,11 +3779,11 @@ int ykgpu_set_scene(ykgpu_context* ctx, const yk_sphere* spheres, uint32_t count
     const float rf = (float)s.radius;
     geo_f[i] = make_float4((float)s.center[0], (float)s.center[1], (float)s.center[2], rf * rf);
     mat[i] = {s.albedo[0], s.albedo[1], s.albedo[2], s.fuzz, s.radius, s.ior, s.material, 0.0f, 0.0};  // inv_r*: yk_mat_prep
-#if YK_DIEL_PRE
     if (s.material == YK_MATERIAL_DIELECTRIC) {
       // the FP64 kernel's dielectric reads 1/ior and Schlick's r0 for both sides of the surface
       // from its otherwise unused fields (never unwound: its attenuation is 1), computed here
-      // with the operations and order of ykd::reflectance (IEEE double, no contraction)
+      // with the operations and order of Schlick's formula as ykf::reflectance writes it (IEEE
+      // double, no contraction)
       const double inv = 1.0 / s.ior;
       double r0f = (1 - inv) / (1 + inv), r0b = (1 - s.ior) / (1 + s.ior);
       r0f = r0f * r0f;
@@ -4129,7 +3792,6 @@ int ykgpu_set_scene(ykgpu_context* ctx, const yk_sphere* spheres, uint32_t count
       mat[i].ar = r0f;
       mat[i].ag = r0b;
     }
-#endif
   }
   YK_HIP(hipSetDevice(ctx->device));
   // a render enqueued by ykgpu_render_async on the caller's stream (and its launches on the
@@ -4177,7 +3839,7 @@ int ykgpu_set_scene(ykgpu_context* ctx, const yk_sphere* spheres, uint32_t count
   const RenderKernel k64[2][2] = {{fp64_kernel(false, 0), fp64_kernel(true, 0)},
                                   {fp64_kernel(false, 4), fp64_kernel(true, 4)}};
   int rc = upload_tree(ctx, ctx->t64, centers, radii, cam_ext, bopt, kLeafCapF64, geo.data(), sizeof(SphereGeo),
-                       sizeof(SphereGeo), k64, YK_NODE_BF != 0 && YK_STACK_EXACT != 0);
+                       sizeof(SphereGeo), k64, true);
   if (rc) return rc;
   ykbvh::Options fopt = bopt;
   fopt.max_leaf = kLeafCapF32;  // the FP32 kernel's leaf loop is unrolled for two spheres
