@@ -1,9 +1,12 @@
 """The product is built from one version of the kernels: no compile-time A/B switch is left (CPU).
 
-Round 11 removed every structural `YK_*` switch of ykgpu_render.hip, keeping the branch the product
-was built with (profiles/r11_knobs/README.md lists them, the value kept and the evidence).  Two
-things keep that true: the product's Makefile recipes define nothing but `YK_SPLIT`, and none of
-the removed names comes back into the sources.
+Round 11 removed every structural `YK_*` switch of the render kernels, keeping the branch the
+product was built with (profiles/r11_knobs/README.md lists them, the value kept and the evidence).
+Round 12 took the two path kernels out of ykgpu_render.hip into units of their own, each source
+file compiled once (profiles/r12_split/README.md), which removed `YK_SPLIT` too.  Three things keep that true: the
+product's Makefile recipes define no `YK_*` at all, none of the removed names comes back into the
+sources, and a test variant compiles one host-side unit with its switch and links the product's
+other objects.
 """
 import os
 import re
@@ -11,7 +14,12 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "uecraytracing_amd", "csrc")
 
-PRODUCT_TARGETS = ("ykgpu_render.o", "ykgpu_render_f32.o", "yk_denoise.o", "yk_features.o", "libykgpu.so")
+# the library's units: one object each (the Makefile's HIP_UNITS and CXX_UNITS)
+HIP_UNITS = ("yk_render_f64", "yk_render_f32", "ykgpu_render", "yk_denoise", "yk_features")
+CXX_UNITS = ("yk_host", "yk_bvh")
+# the rules that make the product: the two object patterns and the link
+PRODUCT_TARGETS = ("%.o", "libykgpu.so")
+TEST_VARIANTS = {"abl/libykgpu_retry%.so": "YK_RETRY_CAP_FORCE", "abl/libykgpu_stack%.so": "YK_STACK_CAP_FORCE"}
 
 REMOVED = [
     "YK_NODE_BF",
@@ -43,17 +51,26 @@ REMOVED = [
     "kInflightDeep",
     "kSchedSlow",
     "kLensDefer",
+    "YK_SPLIT",
+    "yk_split_f32_kernel",
 ]
 
 
+def makefile():
+    return open(os.path.join(CSRC, "Makefile")).read().split("\n")
+
+
 def recipes():
-    """target file name -> its recipe lines, of every rule of the Makefile"""
+    """target file name -> the recipe lines of its rules (a target-specific variable counts as a
+    line of its target), of every rule of the Makefile for a file under $(LIB)"""
     out, cur = {}, None
-    for line in open(os.path.join(CSRC, "Makefile")).read().split("\n"):
-        m = re.match(r"^\$\(LIB\)/([^\s:]+)\s*:", line)
+    for line in makefile():
+        m = re.match(r"^\$\(LIB\)/([^\s:]+)\s*:(.*)$", line)
         if m:
             cur = m.group(1)
-            out[cur] = []
+            out.setdefault(cur, [])
+            if re.match(r"^\s*\w+\s*[:+?]?=", m.group(2)):
+                out[cur].append(m.group(2))
         elif line.startswith("\t") and cur:
             out[cur].append(line)
         elif line.strip() and not line.startswith("#"):
@@ -61,15 +78,67 @@ def recipes():
     return out
 
 
-def test_product_recipes_define_only_yk_split():
+def variable(name):
+    for line in makefile():
+        m = re.match(r"^%s\s*[:+?]?=(.*)$" % re.escape(name), line)
+        if m:
+            return m.group(1).split("#")[0].split()
+    raise AssertionError(f"the Makefile sets no {name}")
+
+
+def test_units_are_the_makefiles():
+    assert tuple(variable("HIP_UNITS")) == HIP_UNITS and tuple(variable("CXX_UNITS")) == CXX_UNITS
+    for u in HIP_UNITS:
+        assert os.path.exists(os.path.join(CSRC, u + ".hip")), u
+    for u in CXX_UNITS:
+        assert os.path.exists(os.path.join(CSRC, u + ".cpp")), u
+
+
+def test_product_recipes_define_no_yk_switch():
     rules = recipes()
     for target in PRODUCT_TARGETS:
         assert rules.get(target), f"the Makefile has no recipe for {target}"
-        defs = re.findall(r"-DYK_\S*", "\n".join(rules[target]))
-        assert set(defs) <= {"-DYK_SPLIT=1", "-DYK_SPLIT=2"}, (target, defs)
-    # the two render units are the ones YK_SPLIT makes
-    assert re.findall(r"-DYK_\S*", "\n".join(rules["ykgpu_render.o"])) == ["-DYK_SPLIT=1"]
-    assert re.findall(r"-DYK_\S*", "\n".join(rules["ykgpu_render_f32.o"])) == ["-DYK_SPLIT=2"]
+    # no rule for a product file, and no flag variable, defines a YK_* macro
+    for target, lines in rules.items():
+        if target not in TEST_VARIANTS:
+            assert not re.findall(r"-DYK_\S*", "\n".join(lines)), (target, lines)
+    for name in ("CXXFLAGS", "HIPFLAGS", "DEPFLAGS", "DEFS"):
+        assert not [w for w in variable(name) if w.startswith("-D")], name
+    # every unit is compiled by one of the two pattern rules, once: no unit has a rule of its own
+    # with a recipe, and each pattern's recipe is one compile
+    compiles = [l for l in rules["%.o"] if " -c " in l]
+    assert len(compiles) == 2 and len(rules["%.o"]) == 4, rules["%.o"]
+    for u in HIP_UNITS + CXX_UNITS:
+        assert not [l for l in rules.get(u + ".o", []) if l.startswith("\t")], u
+    # the one per-unit flag: the FP32 path kernel's scheduler
+    assert rules["yk_render_f32.o"] == [" UNITFLAGS = -mllvm --amdgpu-sched-strategy=max-ilp"]
+    assert [t for t in rules if t.endswith(".o") and rules[t] and t != "%.o"] == ["yk_render_f32.o"]
+
+
+def test_test_variants_compile_one_host_unit_and_link_the_products_objects():
+    rules = recipes()
+    assert variable("REST") == ["$(filter-out", "$(LIB)/ykgpu_render.o,$(OBJS))"]
+    assert variable("OBJS") == ["$(HIP_UNITS:%=$(LIB)/%.o)", "$(CXX_UNITS:%=$(LIB)/%.o)"]
+    for target, switch in TEST_VARIANTS.items():
+        lines = [l for l in rules[target] if not l.strip().startswith("@")]
+        compiles = [l for l in lines if " -c " in l]
+        links = [l for l in lines if " -shared " in l]
+        assert len(compiles) == 1 and len(links) == 1 and len(lines) == 2, lines
+        # the one compile: ykgpu_render.hip with the variant's switch, and nothing else defined
+        assert re.findall(r"-D\S*", compiles[0]) == [f"-D{switch}=$*"], compiles[0]
+        assert re.fullmatch(r"YK_\w+_FORCE", switch)
+        assert compiles[0].split()[-1] == "ykgpu_render.hip"
+        obj = compiles[0].split()[compiles[0].split().index("-o") + 1]
+        # the link: that object and the product's other objects, unchanged
+        assert links[0].split()[links[0].split().index("$@") + 1:] == [obj, "$(REST)"], links[0]
+    # the switches are host code of ykgpu_render.hip, a unit without a render kernel
+    for f in os.listdir(CSRC):
+        text = open(os.path.join(CSRC, f), errors="replace").read()
+        if f not in ("ykgpu_render.hip", "Makefile"):
+            assert "_CAP_FORCE" not in text, f
+    main = open(os.path.join(CSRC, "ykgpu_render.hip")).read()
+    assert not re.search(r"void\s+yk_render_\w+\s*\(", main)
+    assert "#include \"yk_path.hpp\"" not in main
 
 
 def test_no_removed_switch_in_the_sources():

@@ -2,7 +2,7 @@
 
 Round 5's kernel kept a candidate's lower bound as l = RN_f32(L) and compared it with
 ustar_f = RN_f32(RN_f32(U*) * (1 + 2^-18)); round 6's (the clamped near distances, the leaf block of
-ykgpu_render.hip) measures both from tmin_lo = t_min (1 - 2^-17) in units of s = 2^-24:
+yk_render_f64.hip) measures both from tmin_lo = t_min (1 - 2^-17) in units of s = 2^-24:
 l = fma(RN(L), s, -tmin_lo s) and ustar_f = RN(RN(RN(U*)(1 + 2^-18)) - tmin_lo) RN((1 + 2^-22) s)
 (test_shifted_map_never_drops_a_candidate).  The host rejects
 t_min < 0, so every L and U* is >= 0, and the claim is: L <= U*  implies  l <= ustar_f.  This

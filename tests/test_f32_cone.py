@@ -1,6 +1,6 @@
 """The FP32 kernel's cone slab test never culls a box its cone reaches.
 
-render<float> culls with a per-ray cone of slope s = kF32Cone |d| (ykgpu_render.hip, cone_axis and
+render<float> culls with a per-ray cone of slope s = kF32Cone |d| (yk_render_f32.hip, cone_axis and
 the slow-axis bound): per axis, near planes at (plane - o) / (d + s sign d); far planes at
 (plane - o) / (d - s sign d) scaled by (1 + 2^-17) when |d| >= s (1 + 2^-10); and on ONE slow axis
 (|d| < s (1 - 2^-10), y first, then x, then z) the far-side plane's crossing, a LOWER bound, folded

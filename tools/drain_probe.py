@@ -1,7 +1,7 @@
 """Per-launch drain of the persistent render, measured.
 
 usage: YKGPU_LIB_OVERRIDE=.../libykgpu_drain.so python tools/drain_probe.py [spp] [rows] [out.json]
-(the library built with -DYK_DRAIN_DIAG: tools/build_def_variant.sh drain -DYK_DRAIN_DIAG)
+(the library built with -DYK_DRAIN_DIAG: tools/build_variant.sh drain -DYK_DRAIN_DIAG)
 
 Renders the headline workload (or a row tile "begin:count:stride") once warm, clears the wave
 records, renders it again synced, and reads every FP64 render wave's start and end

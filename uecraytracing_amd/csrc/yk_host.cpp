@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/ykgpu.h"
+#include "yk_schedule.hpp"
 
 namespace {
 
@@ -210,6 +211,25 @@ int yk_scene_build(const char* name, uint32_t seed, yk_sphere* spheres, uint32_t
     std::memcpy(spheres, w.data(), w.size() * sizeof(yk_sphere));
   }
   return YK_OK;
+}
+
+// The launch schedule of a render call (yk_schedule.hpp), for the CPU tests: not part of the C-ABI
+// (include/ykgpu.h does not declare it).  A call of spp samples per pixel from s_begin over nps
+// processing slots on a persistent grid of `lanes` threads, synced or in flight; kmax: the launch
+// buffers' samples per pixel (0: the ideal, no memory pressure).  sizes[3] receives kideal, ksynced,
+// kfloor; s0[i], take[i] the launches (the first `cap` of them).  Returns the number of launches.
+uint32_t yk_schedule_plan(uint32_t nps, uint32_t spp, uint32_t s_begin, uint64_t lanes, int inflight, uint32_t kmax,
+                          uint32_t* sizes, uint32_t* s0, uint32_t* take, uint32_t cap) {
+  if (!nps || !spp) return 0;
+  const yksched::LaunchSizes z = yksched::launch_sizes(nps, spp, lanes);
+  if (sizes) sizes[0] = z.kideal, sizes[1] = z.ksynced, sizes[2] = z.kfloor;
+  std::vector<std::pair<uint32_t, uint32_t>> sched;
+  yksched::launch_schedule(sched, spp, s_begin, kmax ? kmax : z.kideal, z.ksynced, inflight != 0);
+  for (uint32_t i = 0; i < sched.size() && i < cap; ++i) {
+    if (s0) s0[i] = sched[i].first;
+    if (take) take[i] = sched[i].second;
+  }
+  return (uint32_t)sched.size();
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // yk_slab.hpp — the wide-node slab test's arithmetic in the fewest registers (gfx950; included by
-// ykgpu_render.hip inside its anonymous namespace).
+// yk_path.hpp inside its anonymous namespace, for both path kernels).
 //
 // d = plane * p.x + p.y for both slots of a plane pair, the pair (1/d, -o/d) read by op_sel: one
 // v_pk_fma_f32 whose second and third operands are the two halves of ONE register pair (the

@@ -39,17 +39,12 @@
 #include <cstring>
 #include <map>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/ykgpu.h"
-#include "yk_bvh.hpp"
-#include "yk_device.hpp"
-#include "yk_device_f32.hpp"
 #include "yk_film_internal.hpp"
-#include "yk_stamps.hpp"
-
-using ykd::v3;
+#include "yk_render_device.hpp"
+#include "yk_schedule.hpp"
 
 namespace {
 
@@ -67,428 +62,6 @@ int fail(int code, const std::string& msg) {
       return fail(e_ == hipErrorOutOfMemory ? YK_ERR_NOMEM : YK_ERR_DEVICE,               \
                   std::string(#call) + ": " + hipGetErrorString(e_));                     \
   } while (0)
-
-// Geometry of one sphere, as the closest-hit scan reads it (32 B: one scalar x8 load).
-// rr = radius*radius computed on the host with the same IEEE multiply as sphere.hpp:33.
-struct alignas(32) SphereGeo {
-  double cx, cy, cz, rr;
-};
-// Shading data, read once per segment by the lane that hit the sphere.
-struct alignas(16) SphereMat {
-  double ar, ag, ab, fuzz;
-  double radius, ior;
-  uint32_t kind;
-  float inv_rf;  // ykf::rcp_refined((float)radius) (FP32 kernel), computed on the device by yk_mat_prep
-  double inv_r;  // ykd::rcp_refined(radius), computed on the device by yk_mat_prep
-};
-static_assert(sizeof(SphereMat) == 64, "SphereMat layout");
-
-// ---- Kernel-side tuning constants (each overridable with -DYK_...: `make variants`,
-// tools/build_def_variant.sh).  The host's are gathered at the top of the host half. ----
-//
-// One 768-thread workgroup per CU (12 waves, 3 per SIMD): the scene is copied into LDS once per
-// CU instead of once per 256-thread block, which leaves room for the shading tables (sphere
-// geometry and materials in tuple order) beside the BVH and the traversal stacks.  The fourth
-// wave slot of each SIMD (128 of its 512 VGPRs) is left to the yk_mt_warmup waves, which run the
-// next launch's seed walks in the render's idle issue cycles.  (1024 threads, 4 render waves per
-// SIMD: the node loop is bound by LDS latency, so the render alone runs 4% faster — 184 vs 192 ms
-// per 512-spp frame without the walks — but the walks can no longer overlap: 218 vs 215 ms.)
-#ifndef YK_BLOCK
-#define YK_BLOCK 768
-#endif
-// The xor128 instances draw no seed walks, so nothing needs the fourth wave slot of a SIMD: they
-// run 1024-thread workgroups (4 render waves per SIMD; the node loop is bound by LDS latency, so
-// the fourth wave pays)
-#ifndef YK_BLOCK_X128
-#define YK_BLOCK_X128 1024
-#endif
-// VGPRs of the production FP64 render instances: 3 render waves x 112 of a SIMD's 512 leave 176, three
-// 48-VGPR warm-up waves and a reduce wave (bench -0.4% against the natural 114 -> 120; 104 spills
-// and starves the render: +3.4%, profiles/r06_ab/vgpr/); the counting instances keep theirs
-#ifndef YK_RENDER_VGPRS
-#define YK_RENDER_VGPRS 112
-#endif
-// sample slots a wave claims per atomic ...
-#ifndef YK_CLAIM
-#define YK_CLAIM 512
-#endif
-// ... and near the end of a launch's slots: when fewer than kClaimTailFactor x kClaim slots per
-// wave of the grid remain (as the wave last saw the counter), a wave claims kClaimTail slots at a
-// time.  A wave's reserve holds up to kClaim slots (8 samples per lane) when the counter runs
-// out, so with full claims to the end some waves still have ~8 samples per lane of work while
-// others have none, and every launch drains for that long (0: full claims to the end).
-#ifndef YK_CLAIM_TAIL
-#define YK_CLAIM_TAIL 64
-#endif
-#ifndef YK_CLAIM_TAIL_FACTOR
-#define YK_CLAIM_TAIL_FACTOR 2
-#endif
-// the FP64 lens warm-up's retries are drawn after its walks (yk_mt_warmup_defer) for launches of at
-// most YK_DEFER_SLOTS slots per warm-up wave; larger launches run the rejection loop in line
-#ifndef YK_DEFER_SLOTS
-#define YK_DEFER_SLOTS 4096
-#endif
-// Walks per lane: the deferred FP64 lens warm-up (the headline frame's) walks four slots at once at
-// 48 VGPRs, so two of its waves share a SIMD with the three render waves (eight walk chains per
-// SIMD instead of four: bench -0.9%, r05_ab/walk/); the other warm-ups walk one
-#ifndef YK_WALK_ILP
-#define YK_WALK_ILP 4
-#endif
-// VGPRs of yk_mt_warmup_defer (the attribute counts gfx950's unified register file: twice)
-#ifndef YK_DEFER_VGPRS
-#define YK_DEFER_VGPRS 48
-#endif
-constexpr int kBlock = YK_BLOCK, kBlockX128 = YK_BLOCK_X128;
-constexpr uint32_t kClaim = YK_CLAIM;
-constexpr uint32_t kClaimTail = YK_CLAIM_TAIL, kClaimTailFactor = YK_CLAIM_TAIL_FACTOR;
-static_assert(kClaimTail == 0 || (kClaimTail >= 64 && kClaimTail <= YK_CLAIM), "a tail claim serves a whole wave");
-constexpr uint64_t kDeferSlots = YK_DEFER_SLOTS;
-constexpr uint32_t kWalkIlp = YK_WALK_ILP;
-
-template <int kMode>
-constexpr int mode_block() {
-  return (kMode & 4) ? kBlockX128 : kBlock;
-}
-constexpr int block_of(bool x128) { return x128 ? kBlockX128 : kBlock; }
-
-// ---- The variants the kernels are built from.  Each was one side of a compile-time A/B; the losing
-// sides are gone from the source (profiles/r11_knobs/README.md says where each one went). ----
-//
-// Both render kernels read the visit's slab constants as one op_sel-read register pair per axis and
-// bound (yk_slab.hpp).  Round 4: FP64 123 -> 115 VGPRs and no faster (512 spp 173.9 -> 174.2 ms),
-// FP32 125 -> 111 VGPRs and faster (195.3 -> 190.1 ms, profiles/r04_ab/f32/).  Round 6, on the
-// branch-free visit: FP64 128 -> 114 VGPRs, bench -0.7% (the SIMD's spare registers take a third
-// warm-up wave, profiles/r06_ab/vgpr/).  (Round 4's two-paths-per-lane kernel, which lost its A/B,
-// is kept as a patch beside its evidence: profiles/r04_ab/dual/yk_dual.patch.)
-// (Tried and removed in round 4, DESIGN.md §4.1: the FP32 slow-axis bound folded into the slow
-// axis' far-plane FMA, +2.3%; the slow-axis read skipped in waves without a slow-axis ray, +3.8%.)
-//
-// The FP64 node visit has no branch (round 6): the stack's bottom entry holds the empty leaf (a
-// sentinel), so "no slot entered" pops unconditionally and every lane of the visit runs the same
-// instructions; a lane's run of interior nodes is a loop of its own (while-while), the entry below
-// the top read with the planes.  The loop variable is the address of that entry (constant DS
-// offsets for it and the pushes).  512 spp, same box (profiles/r06_ab/nodebf/): round 5's visit
-// with its push / pop branches -> this one: bench 163.0 -> 159.5 ms.
-// The visit's loop exists once, its stack check a uniform branch inside it (two copies, with and
-// without the check: +0.4%, profiles/r06_ab/shade/r06an_*).
-// The FP64 stack is sized to the tree's proven depth (3 x wide depth + 1 entries) where LDS allows,
-// its overflow check then skipped (a scalar branch on KernelArgs::stack_check): bench 159.0 ->
-// 156.2 ms on top of the branch-free visit.
-// The visit's distances are measured from tmin_lo and scaled by kClampScale, the near FMAs clamp to
-// [0, 1] in place of the max with tmin_lo: 4 VALU fewer per visit, bench 150.0 -> 147.0 ms, node
-// visits unchanged, bit-exact (profiles/r06_ab/shade/r06ai_*).
-// The visit's slab min / max run two slots per asm block (yk_slab.hpp slab_cull2c): one hazard
-// pad per visit instead of eight, bench -0.2% (four of four same-box pairs, image hashes equal,
-// profiles/r06_ab/shade/r06ag_*).
-// The FP64 candidate list keeps its ids as 16-bit halves of two registers: the shift-in is one
-// alignbit and one lshl_or instead of four moves, two VGPRs freed; bench -0.3...-0.6%, synced
-// -0.4...-0.8%, image hash unchanged (r06_ab/shade/r06ax_*).
-// The newest candidate's hb and disc are kept from its leaf test, so its exact root skips the second
-// discriminant (17 FP64 operations): bench -0.4...-0.6%, synced -0.6%, the headline image's hash
-// unchanged, no spill at 112 VGPRs (profiles/r06_ab/shade/r06ar_*).  Its v_rsq_f64, which
-// math::sqrt's start repeats, is not kept (2 VGPRs more: three spills at 112), and the candidates'
-// refined 1/a is computed on its own, not from the bounds' 1/a (one Newton step instead of rcp +
-// two: neutral, profiles/r06_ab/shade/r06au_*).
-// The FP64 dielectric's 1/ior and Schlick r0 (both sides) are precomputed on the host: two FP64
-// divisions fewer per trip with a glass hit (bench -0.6%, profiles/r06_ab/shade/).
-// The FP64 unwind skips the spill check when no ending lane of the wave spilled, two ids per
-// round (bench 156.6 -> 156.0 ms, profiles/r06_ab/unwind/).
-// Slot claims take the tail size from a kernel argument and the leader's counter by v_readlane (the
-// claim's bookkeeping becomes scalar: 2 VGPRs fewer, profiles/r06_ab/vgpr/r06t_*).
-constexpr float kClampScale = 0x1p-24f;
-using DevNode = ykbvh::WideNode;  // 4-wide BVH nodes (yk_bvh.hpp)
-constexpr int kCounters = 32;  // [16..18]: timeline, [19..22]: diag (stamp builds), [24..31]: work
-// Spheres per BVH leaf the kernels' leaf code handles: the FP64 leaf test is loop-free for one
-// sphere, the FP32 leaf loop is unrolled for two.  ykgpu_set_scene builds the trees with these
-// as ykbvh::Options::max_leaf and upload_tree rejects a tree with a larger leaf (its extra spheres
-// would be skipped silently).
-constexpr uint32_t kLeafCapF64 = 1, kLeafCapF32 = 2;
-constexpr uint32_t kStackRegs = 8;  // attenuation ids kept in registers (4 x 2 x u16)
-constexpr uint32_t kFlagLinearScan = YK_FLAG_LINEAR_SCAN;
-constexpr uint32_t kFlagOneLane = YK_FLAG_ONE_LANE;
-constexpr uint32_t kFlagTrace = YK_FLAG_TRACE_RAYS;
-
-// the camera rounded to float once on the host (camera<float>'s members, camera.hpp:10-27), and
-// W, H as floats: the FP32 kernel's start converts nothing
-struct CamF {
-  float origin[3], llc[3], horizontal[3], vertical[3], lens_u[3], lens_v[3];
-  float lens_radius, w, h, pad[3];
-};
-struct KernelArgs {
-  yk_camera cam;
-  CamF camf;
-  uint32_t W, H, spp, max_depth;
-  uint32_t seed0, row_begin, row_count, row_stride, band_log2;
-  // stack_check: 0 when the FP64 traversal stack holds 3 x (wide depth) + 1 entries, so the
-  // branch-free visit cannot overflow it and skips the check (upload_tree)
-  uint32_t nspheres, stack_check, flags, id_stride;
-  // A launch renders samples [s0, s0 + nsl / npix_slots) of every pixel: sample slot
-  // i = s_local * npix_slots + p is sample s0 + s_local of tile pixel order[p].
-  uint32_t s0, nsl, npix_slots, seed_mode;  // seed_mode: YK_SEED_*
-  uint32_t nps_m, nps_sh, w_m, w_sh;  // fdiv magic numbers of npix_slots and the tile width Wt
-  uint64_t seed_key;
-  const uint32_t* __restrict__ order;  // p → tile pixel (kNoPixel: empty slot of an edge block)
-  uint64_t pad_a;                      // (keeps the argument layout the kernels were tuned with)
-  const void* __restrict__ start;      // StartRec per sample slot (mt19937 kernels)
-  double t_min;
-  double inv_w, inv_h;  // RN(1/W), RN(1/H) for the camera's exact divisions (div_markstein)
-  double w_d, h_d;      // W, H as doubles (kernel arguments: no loop-hoisted conversion to hold)
-  double origin_bound;  // |o|_inf beyond which the BVH's float culling is not proven sound
-  int32_t bvh_root;
-  uint32_t n_nodes;
-  uint32_t lds_geo_off, lds_ids_off, lds_stack_off, stack_cap;  // stack_cap: entries a lane may hold
-  uint32_t lds_tgeo_off, lds_mat_off;  // FP64 kernel: tuple-order geometry / materials in LDS
-  const DevNode* __restrict__ nodes;  // child links are byte offsets from nodes
-  const SphereGeo* __restrict__ leaf_geo;  // spheres in BVH leaf order
-  const uint32_t* __restrict__ leaf_ids;   // leaf slot → tuple index
-  const SphereGeo* __restrict__ geo;
-  const SphereMat* __restrict__ mat;
-  const float4* __restrict__ geo_f;  // FP32 path: (cx, cy, cz, r*r) rounded to float, tuple order
-  double* col;                       // sample colours: a record per slot (colour_store)
-  uint32_t* pixel_counter;           // sample-slot counter
-  uint32_t* mt_scratch;
-  uint16_t* id_scratch;
-  unsigned long long* counters;  // [segments, sphere_tests, sqrt_calls, mt_fallbacks, nodes]
-  double* trace;                 // YK_FLAG_TRACE_RAYS: rays [(q*spp + s)*trace_cap + k][6]
-  uint32_t* trace_counts;        //   ray_color calls per sample [q*spp + s]
-  uint32_t trace_cap;
-  uint32_t claim_tail;  // slots left below which a wave claims kClaimTail: grid x waves x kClaim x factor
-  unsigned long long* clk;  // this launch's shader-clock probe (YK_CLOCK_*): 4 words
-  // the tile's columns (include/ykgpu.h yk_render_params; the whole width: Wt = W, 0, 1, 0)
-  uint32_t Wt, col_begin, col_stride, col_band;
-#ifdef YK_DRAIN_DIAG
-  uint32_t diag_c, diag_pad;  // the launch's index in its call
-#endif
-};
-
-// Shader-clock probe of a launch: thread 0 of block 0 stores s_memtime (the shader clock) and
-// s_memrealtime (100 MHz) when it starts and when it leaves the loop (vector stores, nothing held
-// in registers across the loop) — the clock the launch ran at (ykgpu_get_stats sclk_mhz; the
-// per-launch timeline).
-#define YK_CLOCK_STAMP(ka, k)                                                              \
-  do {                                                                                     \
-    if (blockIdx.x == 0 && threadIdx.x == 0) {                                             \
-      (ka).clk[(k)] = __builtin_amdgcn_s_memtime();                                        \
-      (ka).clk[(k) + 1] = __builtin_amdgcn_s_memrealtime();                                \
-    }                                                                                      \
-  } while (0)
-#define YK_CLOCK_BEGIN(ka) YK_CLOCK_STAMP(ka, 0)
-#define YK_CLOCK_END(ka) YK_CLOCK_STAMP(ka, 2)
-
-// Diagnostic builds (YK_DRAIN_DIAG, tools/drain_probe.py): every FP64 render wave records when it
-// starts and when it leaves the loop (s_memrealtime, 100 MHz) and where it ran (HW_ID, XCC_ID), per
-// launch of the call: the per-launch drain — waves idle in a workgroup that still holds its CU,
-// CUs between one launch's workgroup and the next — measured, not modelled
-#ifdef YK_DRAIN_DIAG
-constexpr uint32_t kDiagLaunches = 64, kDiagBlocks = 512, kDiagWaves = 16;
-// per wave: {start, end, HW_ID | XCC_ID << 32}
-__device__ unsigned long long yk_wave_times[kDiagLaunches * kDiagBlocks * kDiagWaves * 3];
-#define YK_WAVE_STAMP(ka, k)                                                                          \
-  do {                                                                                                \
-    const uint32_t w_ = threadIdx.x >> 6;                                                             \
-    if ((threadIdx.x & 63u) == 0 && (ka).diag_c < kDiagLaunches && blockIdx.x < kDiagBlocks) {        \
-      unsigned long long* r_ =                                                                        \
-          yk_wave_times + (((size_t)(ka).diag_c * kDiagBlocks + blockIdx.x) * kDiagWaves + w_) * 3;     \
-      r_[(k)] = __builtin_amdgcn_s_memrealtime();                                                     \
-      if ((k) == 0)                                                                                   \
-        r_[2] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |                       \
-                ((unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) << 32);                \
-    }                                                                                                 \
-  } while (0)
-#else
-#define YK_WAVE_STAMP(ka, k) ((void)0)
-#endif
-
-// -l 3 (raytracer.hpp:21-25): ray k of the path of the lane's sample slot (counting instance)
-template <class V>
-__device__ __forceinline__ void trace_ray(const KernelArgs& ka, uint32_t slot, uint32_t k, V o, V d) {
-  const uint32_t sl = slot / ka.npix_slots, q = ka.order[slot - sl * ka.npix_slots];
-  const size_t idx = (size_t)q * ka.spp + ka.s0 + sl;
-  if (k < ka.trace_cap) {
-    double* r = ka.trace + (idx * ka.trace_cap + k) * 6;
-    r[0] = o.x, r[1] = o.y, r[2] = o.z, r[3] = d.x, r[4] = d.y, r[5] = d.z;
-  }
-  ka.trace_counts[idx] = k + 1;
-}
-
-// floor(n / d) for n < 2^31 with the host's magic numbers (fastdiv): ((uint64) n * m) >> sh, where
-// l = ceil(log2 d), sh = 31 + l, m = ceil(2^sh / d) < 2^32 — exact for every 31-bit n (the
-// round-up error n * (m d - 2^sh) / (d 2^sh) < 2^31 d / (d 2^sh) * d / 2^l <= 1/d).  A runtime
-// divisor otherwise costs the ~20-instruction float-reciprocal sequence per division.
-__device__ __forceinline__ uint32_t fdiv(uint32_t n, uint32_t m, uint32_t sh) {
-  return (uint32_t)(((uint64_t)n * m) >> sh);
-}
-
-// Image row of tile row t (include/ykgpu.h yk_render_params: bands of 2^band_log2 rows, every
-// row_stride-th band; band_log2 = 0 is the plain strided row set)
-__device__ __forceinline__ uint32_t tile_row_y(uint32_t row_begin, uint32_t row_stride, uint32_t band_log2,
-                                               uint32_t t) {
-  return row_begin + (((t >> band_log2) * row_stride) << band_log2) + (t & ((1u << band_log2) - 1u));
-}
-// ... and image column of tile column j (bands of 2^col_band columns, every col_stride-th band)
-__device__ __forceinline__ uint32_t tile_col_x(uint32_t col_begin, uint32_t col_stride, uint32_t col_band,
-                                               uint32_t j) {
-  return col_begin + (((j >> col_band) * col_stride) << col_band) + (j & ((1u << col_band) - 1u));
-}
-
-struct Hit {
-  double T;
-  int hid;
-  uint32_t tests, sqrts;
-  uint32_t ncalls, nits;  // math::sqrt calls / loop iterations
-};
-
-// The reference's closest-hit scan verbatim (hittable_list.hpp:32-58 over sphere.hpp:25-48):
-// tuple order, t_max shrinking to the last accepted root.  Used for rays the BVH cannot serve
-// (degenerate direction, origin beyond the proven float range, candidate-list overflow) and,
-// with kFlagLinearScan, as the A/B reference of the BVH path.
-__device__ __noinline__ Hit scan_linear(const SphereGeo* __restrict__ geo, uint32_t n, v3 o, v3 d,
-                                        double tmin) {
-  const double a = ykd::len2(d);
-  Hit h{INFINITY, -1, 0, 0, 0, 0};
-  for (uint32_t i = 0; i < n; ++i) {
-    const SphereGeo sg = geo[i];
-    ++h.tests;
-    const v3 oc = {o.x - sg.cx, o.y - sg.cy, o.z - sg.cz};
-    const double hb = ykd::dot(oc, d);
-    const double c = ykd::len2(oc) - sg.rr;
-    const double disc = hb * hb - a * c;
-    if (disc < 0) continue;
-    ++h.sqrts;
-    const double sq = ykd::nsqrt_c(disc, h.ncalls, h.nits);
-    double root = (-hb - sq) / a;
-    if (root < tmin || h.T < root) {
-      root = (-hb + sq) / a;
-      if (root < tmin || h.T < root) continue;
-    }
-    h.T = root;
-    h.hid = (int)i;
-  }
-  return h;
-}
-
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-#include "yk_slab.hpp"
-
-__device__ __forceinline__ float safe_rcp(float x) {
-  return fabsf(x) > 1e-30f ? 1.0f / x : copysignf(1e30f, x);
-}
-
-// Candidate list entry insertion with static register indexing (no scratch).
-#define YK_CAND_SET(K, ID, LB) \
-  do {                         \
-    if ((K) == 0) { c0 = ID; l0 = LB; }       \
-    else if ((K) == 1) { c1 = ID; l1 = LB; }  \
-    else if ((K) == 2) { c2 = ID; l2 = LB; }  \
-    else { c3 = ID; l3 = LB; }                \
-  } while (0)
-
-// n / a for a root (sphere.hpp:36-38), a's refined reciprocal shared by all candidates; a wave
-// with any lane out of range takes the full division (divs_fast's rule)
-__device__ __forceinline__ double root_div(double n, double a, double ra, bool a_ok) {
-  double q = ykd::div_by(n, a, ra);
-  if (__builtin_expect(__ballot(!(a_ok && ykd::num_range(n))) != 0, 0)) q = n / a;
-  return q;
-}
-// Exact value of sphere i's root under the reference's acceptance rule, ignoring t_max
-// (sphere.hpp:35-39): root1 if root1 >= t_min, else root2 if root2 >= t_min, else none — from the
-// candidate's hb and disc (the reference's, bit for bit)
-__device__ __forceinline__ void exact_root(uint32_t i, double hb, double disc, double a, double ra, bool a_ok,
-                                           double tmin, Hit& best) {
-  if (disc < 0) return;  // never taken: the candidate passed the same test
-  ++best.sqrts;
-  const double sq = ykd::nsqrt_c(disc, best.ncalls, best.nits);
-  double r = root_div(-hb - sq, a, ra, a_ok);
-  if (r < tmin) {
-    r = root_div(-hb + sq, a, ra, a_ok);
-    if (r < tmin) return;
-  }
-  // closest wins; an exact tie goes to the later tuple index (hittable_list.hpp:36-43)
-  if (r < best.T || (r == best.T && (int)i > best.hid)) {
-    best.T = r;
-    best.hid = (int)i;
-  }
-}
-// ... of a candidate whose hb and disc were not kept from its leaf test
-__device__ __forceinline__ void exact_candidate(const SphereGeo* __restrict__ geo, uint32_t i,
-                                                v3 o, v3 d, double a, double ra, bool a_ok,
-                                                double tmin, Hit& best) {
-  const SphereGeo sg = geo[i];
-  const v3 oc = {o.x - sg.cx, o.y - sg.cy, o.z - sg.cz};
-  const double hb = ykd::dot(oc, d);
-  const double c = ykd::len2(oc) - sg.rr;
-  const double disc = hb * hb - a * c;
-  exact_root(i, hb, disc, a, ra, a_ok, tmin, best);
-}
-
-__device__ __forceinline__ v3 ld3(const double* p) { return {p[0], p[1], p[2]}; }
-
-// Processing order: slot p of a call renders tile pixel order[p] (ykgpu_context::order, built on
-// the host for the image geometry): 8x8 pixel blocks, so the lanes a wave refills together take
-// neighbouring pixels in both directions.  Every pixel's samples are independent of the order.
-constexpr uint32_t kNoPixel = 0xffffffffu;
-
-// camera::get_ray (camera.hpp:29-32) for pixel (x, y) from the start's draws: the jitter
-// canonicals uc, vc (source.cpp:162-163, (x + U01) / W correctly rounded by Markstein's form with
-// the host's RN(1/W), yk_device.hpp) and the thin-lens point (px, py) when the camera has a lens.
-// The warm-up and the render kernel's own start (xor128, or a record the warm-up could not
-// complete) both call it, so a record's ray is the ray the render would have computed.
-__device__ __forceinline__ void camera_ray(const yk_camera& cam, double w_d, double inv_w, double h_d,
-                                           double inv_h, uint32_t H, uint32_t x, uint32_t y, double uc,
-                                           double vc, bool lens, double px, double py, v3& o, v3& d) {
-  const double u = ykd::div_markstein((double)x + ykd::uniform_of(uc, 0, 1), w_d, inv_w);
-  const double v = ykd::div_markstein((double)(H - y - 1) + ykd::uniform_of(vc, 0, 1), h_d, inv_h);
-  const v3 cam_o = ld3(cam.origin), cam_llc = ld3(cam.lower_left_corner);
-  const v3 cam_h = ld3(cam.horizontal), cam_v = ld3(cam.vertical);
-  d = ykd::sub(ykd::add(ykd::add(cam_llc, ykd::mul(cam_h, u)), ykd::mul(cam_v, v)), cam_o);
-  o = cam_o;
-  if (lens) {  // thin-lens offset
-    const double rx = px * cam.lens_radius, ry = py * cam.lens_radius;
-    const v3 off = ykd::add(ykd::mul(ld3(cam.lens_u), rx), ykd::mul(ld3(cam.lens_v), ry));
-    o = ykd::add(o, off);
-    d = ykd::sub(d, off);
-  }
-}
-// the same in float (camera<float>, the host-rounded camera CamF; (x + U01) / W a float division)
-__device__ __forceinline__ void camera_ray_f32(const CamF& cam, uint32_t H, uint32_t x, uint32_t y, float uc,
-                                               float vc, bool lens, float px, float py, ykf::v3& o, ykf::v3& d) {
-  const float u = ((float)x + uc) / cam.w;
-  const float v = ((float)(H - y - 1) + vc) / cam.h;
-  const ykf::v3 cam_o = ykf::off(cam.origin), cam_llc = ykf::off(cam.llc);
-  const ykf::v3 cam_h = ykf::off(cam.horizontal), cam_v = ykf::off(cam.vertical);
-  d = ykf::sub(ykf::add(ykf::add(cam_llc, ykf::mul(cam_h, u)), ykf::mul(cam_v, v)), cam_o);
-  o = cam_o;
-  if (lens) {
-    const float rx = px * cam.lens_radius, ry = py * cam.lens_radius;
-    const ykf::v3 off = ykf::add(ykf::mul(ykf::off(cam.lens_u), rx), ykf::mul(ykf::off(cam.lens_v), ry));
-    o = ykf::add(o, off);
-    d = ykf::sub(d, off);
-  }
-}
-
-// A sample's start, precomputed by yk_mt_warmup for the mt19937 kernels: the camera ray of the
-// sample (after the jitter canonicals and the thin-lens rejection loop) and the lazy cursors
-// after those draws (x_j, x_{j+1}, x_{j+397}, j).  j == kNoStart: the lens loop would have
-// reached the scratch engine's words (never seen: ~55 rejections), and the render kernel starts
-// that sample itself.  FP64: 64 bytes (four 16-byte loads); FP32: 48.
-struct alignas(16) StartRec {
-  double ox, oy, oz, dx, dy, dz;
-  uint32_t a0, a1, b, j;
-};
-static_assert(sizeof(StartRec) == 64, "StartRec layout");
-struct alignas(16) StartRecF {
-  float ox, oy, oz, dx, dy, dz;
-  uint32_t pad0, pad1;
-  uint32_t a0, a1, b, j;
-};
-static_assert(sizeof(StartRecF) == 48, "StartRecF layout");
-constexpr uint32_t kNoStart = 0xffffffffu;
-// j == kPadSlot: the slot is an empty slot of an edge block (kNoPixel in the processing order), so
-// the render tells it from its StartRec alone and reads the order only for a start it makes itself
-constexpr uint32_t kPadSlot = 0xfffffffeu;
-constexpr uint32_t kPadX = 0xffffffffu;  // (the warm-up's column of such a slot)
 
 // Seed walk and start of every sample of a launch, fully coherent, one sample per thread
 // (grid-stride): the 397-step walk, then the start's draws with the lazy cursors (yk_device.hpp)
@@ -748,22 +321,6 @@ __global__ __launch_bounds__(256) void yk_mt_warmup(WarmArgs wa) {
 // 128-VGPR render waves of a SIMD (the attribute counts gfx950's unified register file: twice)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(YK_DEFER_VGPRS / 2))) void yk_mt_warmup_defer(WarmArgs wa) {
   mt_warmup_body<true, false, true, kWalkIlp>(wa);
-}
-
-// kSceneInLds: the BVH nodes, the leaf-ordered sphere geometry and the leaf→tuple ids are copied
-// into LDS by each workgroup once (33 KB for the 485-sphere scene), so a node visit is four
-// ds_read_b128 instead of four dependent L2 round trips.  Larger scenes read them from global.
-
-// A sample's colour record: r, g, b as one aligned 32-byte record per sample slot (one 16-byte
-// and one 8-byte store, the whole record in one 32-byte sector), in a colour buffer of the launch.
-// yk_reduce_samples reads the records of consecutive slots, coalesced.  (Round 4 tried writing
-// the colour over the slot's own StartRec instead — no colour buffer at all — and the frame got
-// 3% slower: 174.1 -> 179.5 ms, profiles/r04_ab/; the reduce then reads 24 of every 64 bytes.)
-constexpr size_t kColStride = 4;
-__device__ __forceinline__ void colour_store(double* col, uint32_t slot, double r, double g, double b) {
-  double* rec = col + (size_t)slot * kColStride;
-  *(double2*)rec = make_double2(r, g);
-  rec[2] = b;
 }
 
 // Ordered sum of a launch's sample colours per pixel: pixel_color of source.cpp:137-167 is the
@@ -1109,1290 +666,6 @@ __global__ __launch_bounds__(256) void yk_math_sqrt(const double* in, double* ou
   if (i < n) out[i] = ykd::nsqrt(in[i]);
 }
 
-// Refill of the persistent kernels: lanes without a path take the next sample slots from the
-// wave's reserve, one atomic per kClaim slots.  Every lane runs it, so the reserve (res_base,
-// res_left) stays wave-uniform.  (A pixel is not a lane's unit of work: the samples of a pixel
-// are independent, only their SUM is ordered, and yk_reduce_samples does that.)  Returns true
-// when this lane has no path and the launch has no slots left: the lane exits.
-// The per-sample engine of a kernel instance (YK_RNG_*): lane set-up.
-__device__ __forceinline__ void rng_init(ykd::MtLane& g, const KernelArgs& ka, uint32_t gid) {
-  g.state = ka.mt_scratch + (size_t)gid * ykd::kMtN;
-  g.a0 = g.a1 = g.b = g.j = g.seed = 0;
-}
-__device__ __forceinline__ void rng_init(ykd::X128Lane& g, const KernelArgs&, uint32_t) { g.x = g.y = g.z = g.w = g.n = 0; }
-
-// A sample's engine from its seed alone (xor128, and an mt19937 start no StartRec serves):
-// mt19937 walks its 397 seeding steps here
-__device__ __forceinline__ void rng_start_full(ykd::MtLane& g, uint32_t seed) { ykd::mt_start(g, seed); }
-__device__ __forceinline__ void rng_start_full(ykd::X128Lane& g, uint32_t seed) { ykd::x128_start(g, seed); }
-
-__device__ __forceinline__ bool claim_slots(const KernelArgs& ka, bool in_path, uint32_t lane, uint32_t& slot,
-                                            uint32_t& res_base, uint32_t& res_left) {
-  const unsigned long long m = __ballot(!in_path);
-  if (m) {
-    const uint32_t need = (uint32_t)__popcll(m);
-    uint32_t fresh = 0, csize = kClaim;
-    if (res_left < need) {
-      if (kClaimTail) {
-        // res_base + res_left: where the counter stood after this wave's last claim
-        const uint32_t seen = res_base + res_left;
-        const uint32_t tail = ka.claim_tail;  // (the host's: no dispatch-packet load, no vmcnt wait)
-        if (seen >= ka.nsl || ka.nsl - seen < tail) csize = kClaimTail;
-      }
-      const int leader = __ffsll((long long)m) - 1;
-      if ((int)lane == leader) fresh = atomicAdd(ka.pixel_counter, csize);
-      fresh = __builtin_amdgcn_readlane(fresh, leader);  // (the leader is wave-uniform)
-    }
-    if (!in_path) {
-      const uint32_t r = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      slot = r < res_left ? res_base + r : fresh + (r - res_left);
-    }
-    if (res_left < need) {
-      res_base = fresh + (need - res_left);
-      res_left = csize - (need - res_left);
-    } else {
-      res_base += need;
-      res_left -= need;
-    }
-  }
-  return !in_path && slot >= ka.nsl;
-}
-
-using RenderKernel = void (*)(KernelArgs);
-
-// YK_SPLIT (Makefile): 0 — every kernel in this translation unit (the A/B variants of
-// tools/build_def_variant.sh); 1 — the library's main unit, without the FP32 render kernel; 2 —
-// the FP32 render kernel alone, compiled under LLVM's max-ilp scheduler (FP32 512 spp: -1.3%;
-// the same scheduler costs the FP64 kernel +1.5%)
-#ifndef YK_SPLIT
-#define YK_SPLIT 0
-#endif
-#if YK_SPLIT != 2
-// kCount: the work counters of YK_FLAG_COUNT_WORK (an instance of its own, so the production
-// instance carries neither their registers nor their adds)
-// kMode bit 0: the work counters; bit 1: YK_SEED_RANDOM_DEVICE seeding (an instance of its own:
-// the hash's 64-bit arithmetic and two more kernel arguments cost the counter-seeded production
-// instance 0.6% through SGPR spills); bit 2: the yk::xor128 engine (YK_RNG_XOR128)
-template <bool kSceneInLds, int kMode>
-__device__ __forceinline__ void render_body(KernelArgs ka) {
-  constexpr int kBlk = mode_block<kMode>();
-  constexpr bool kCount = (kMode & 1) != 0;
-  constexpr bool kRandomSeed = (kMode & 2) != 0;
-  using Gen = typename std::conditional<(kMode & 4) != 0, ykd::X128Lane, ykd::MtLane>::type;
-  const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63u;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const char* __restrict__ nodes = (const char*)ka.nodes;
-  const SphereGeo* __restrict__ leaf_geo = ka.leaf_geo;
-  const uint32_t* __restrict__ leaf_ids = ka.leaf_ids;
-  const SphereGeo* __restrict__ geo = ka.geo;  // tuple order: candidates' roots, hit records
-  const SphereMat* __restrict__ mat = ka.mat;  // shading, attenuation unwind
-  if (kSceneInLds) {
-    // the BVH, its leaf geometry and ids, and (tuple order) the geometry and materials
-    const uint4* src[5] = {(const uint4*)ka.nodes, (const uint4*)ka.leaf_geo, (const uint4*)ka.leaf_ids,
-                           (const uint4*)ka.geo, (const uint4*)ka.mat};
-    const uint32_t off[5] = {0u, ka.lds_geo_off, ka.lds_ids_off, ka.lds_tgeo_off, ka.lds_mat_off};
-    const uint32_t n16[5] = {(ka.n_nodes * (uint32_t)sizeof(DevNode) + 15u) / 16u, ka.nspheres * 2u,
-                             (ka.nspheres + 3u) / 4u, ka.nspheres * 2u, ka.nspheres * 4u};
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      uint4* dst = (uint4*)(smem + off[k]);
-      for (uint32_t i = threadIdx.x; i < n16[k]; i += kBlk) dst[i] = src[k][i];
-    }
-    __syncthreads();
-    nodes = smem;
-    // the child-code reads address the LDS copy from 0: the dynamic region must start there
-    if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem != 0u) __builtin_trap();
-    leaf_geo = (const SphereGeo*)(smem + ka.lds_geo_off);
-    leaf_ids = (const uint32_t*)(smem + ka.lds_ids_off);
-    geo = (const SphereGeo*)(smem + ka.lds_tgeo_off);
-    mat = (const SphereMat*)(smem + ka.lds_mat_off);
-  }
-  int32_t* const stk = (int32_t*)(smem + ka.lds_stack_off) + threadIdx.x;  // [sp * kBlk]
-  // YK_FLAG_ONE_LANE (counting instance only): lanes 1..63 leave here, after the block's last
-  // barrier, so every wave-instruction below is one lane's (the profiler's per-wave FP64 counters
-  // then count that lane's executed operations exactly: DESIGN.md §5)
-  if (kCount && (ka.flags & kFlagOneLane) && lane != 0) return;
-  stk[0] = ykbvh::kEmptyLeaf;  // the sentinel below every traversal's entries
-  // the warm-up waves sharing the SIMDs (priority 0) get only the issue slots the render leaves
-  __builtin_amdgcn_s_setprio(1);
-  YK_CLOCK_BEGIN(ka);
-  YK_WAVE_STAMP(ka, 0);
-
-  Gen g;
-  rng_init(g, ka, gid);
-  uint16_t* const id_spill = ka.id_scratch + (size_t)gid * ka.id_stride;
-
-  uint32_t n_seg = 0, n_test = 0, n_sqrt = 0, n_fb = 0, n_node = 0, n_lin = 0, n_ncall = 0, n_nit = 0;
-  uint32_t n_dpos = 0;  // leaf tests with disc >= 0 (their root bounds are computed)
-  uint32_t n_lamb = 0, n_metal = 0, n_fuzz = 0, n_diel = 0;  // hits shaded per material kind
-  // engine words drawn (the warm-up's start words among them) and scratch-engine twists
-  uint32_t n_words = 0, n_swords = 0, n_twist = 0;
-
-  YK_STAMPS_BEGIN(ka.counters, lane);
-  uint32_t slot = 0, depth = 0, nstk = 0;
-  uint32_t st0 = 0, st1 = 0, st2 = 0, st3 = 0;  // newest attenuation id in st0's low half
-  v3 o = {0, 0, 0}, d = {0, 0, 0};
-  bool in_path = false;
-  // wave-level reserve of claimed sample slots (identical in every lane of the wave)
-  uint32_t res_base = 0, res_left = 0;
-
-  for (;;) {
-    // ---- refill (claim_slots): lanes without a path take the next sample slots
-    if (claim_slots(ka, in_path, lane, slot, res_base, res_left)) {
-      YK_STAMPS_EXHAUSTED(ka.counters);
-      break;
-    }
-    YK_STAMP(0);
-
-    // ---- start sample s of the pixel: seed, jitter, camera ray (source.cpp:154-165) ------
-    bool start = !in_path;
-    // mt19937: the slot's StartRec, its four loads issued together and waited for once (every
-    // slot of the launch, empty ones included, has a record, so the read is in bounds); it says
-    // whether the slot is empty (kPadSlot) and holds the whole start, so neither the processing
-    // order nor the pixel's seed is read here — the scratch engine recovers the seed from its
-    // cursor (mt_slow).  xor128: the slot's pixel
-    uint4 rq0 = {0, 0, 0, 0}, rq1 = {0, 0, 0, 0}, rq2 = {0, 0, 0, 0}, rq3 = {0, 0, 0, 0};
-    uint32_t qpix = 0;
-    if (start) {
-      if constexpr (std::is_same<Gen, ykd::MtLane>::value) {
-        const uint4* rp = (const uint4*)ka.start + 4u * slot;
-        rq0 = rp[0];
-        rq1 = rp[1];
-        rq2 = rp[2];
-        rq3 = rp[3];
-        asm volatile("" ::"v"(rq0.x), "v"(rq0.y), "v"(rq0.z), "v"(rq0.w), "v"(rq1.x), "v"(rq1.y),
-                     "v"(rq1.z), "v"(rq1.w), "v"(rq2.x), "v"(rq2.y), "v"(rq2.z), "v"(rq2.w), "v"(rq3.x),
-                     "v"(rq3.y), "v"(rq3.z), "v"(rq3.w));
-        start = rq3.w != kPadSlot;  // an empty slot of an edge block: take another next trip
-      } else {
-        const uint32_t sl = fdiv(slot, ka.nps_m, ka.nps_sh);
-        qpix = ka.order[slot - sl * ka.npix_slots];
-        start = qpix != kNoPixel;
-      }
-    }
-    if (start) {
-      // The start — the jitter canonicals, the lens point and the camera ray — and the engine
-      // after its draws: precomputed for mt19937 by yk_mt_warmup (StartRec), so the divergent
-      // loop only loads them; xor128, and the (never seen) record the warm-up could not
-      // complete, start here
-      bool pre = false;
-      if constexpr (std::is_same<Gen, ykd::MtLane>::value) {
-        StartRec r;  // (loaded above)
-        __builtin_memcpy((char*)&r, &rq0, 16);
-        __builtin_memcpy((char*)&r + 16, &rq1, 16);
-        __builtin_memcpy((char*)&r + 32, &rq2, 16);
-        __builtin_memcpy((char*)&r + 48, &rq3, 16);
-        pre = r.j != kNoStart;
-        if (pre) {
-          if (kCount) n_swords += r.j;
-          g.a0 = r.a0;
-          g.a1 = r.a1;
-          g.b = r.b;
-          g.j = r.j;
-          o = v3{r.ox, r.oy, r.oz};
-          d = v3{r.dx, r.dy, r.dz};
-        }
-      }
-      if (!pre) {
-        // the pixel and its seed (uint32 wrap, source.cpp:154-158)
-        const uint32_t sl = fdiv(slot, ka.nps_m, ka.nps_sh);
-        if constexpr (std::is_same<Gen, ykd::MtLane>::value) qpix = ka.order[slot - sl * ka.npix_slots];
-        const uint32_t s = ka.s0 + sl;
-        const uint32_t tr = fdiv(qpix, ka.w_m, ka.w_sh);
-        const uint32_t x = tile_col_x(ka.col_begin, ka.col_stride, ka.col_band, qpix - tr * ka.Wt);
-        const uint32_t y = tile_row_y(ka.row_begin, ka.row_stride, ka.band_log2, tr);
-        const uint32_t seed = ykd::sample_seed(kRandomSeed ? 1u : 0u, ka.seed_key, ka.seed0, y, x, ka.W, ka.spp, s);
-        const bool lens = ka.cam.lens_radius > 0;
-        rng_start_full(g, seed);
-        const double uc = ykd::canonical<true>(g);  // (a fresh engine: its first words never need the scratch engine)
-        const double vc = ykd::canonical<true>(g);
-        double px = 0, py = 0;
-        if (lens) {  // thin-lens extension: random_in_unit_disk by rejection
-          do {
-            px = ykd::uniform(g, -1, 1);
-            py = ykd::uniform(g, -1, 1);
-          } while (!(px * px + py * py < 1.0));
-        }
-        camera_ray(ka.cam, ka.w_d, ka.inv_w, ka.h_d, ka.inv_h, ka.H, x, y, uc, vc, lens, px, py, o, d);
-      }
-      depth = ka.max_depth;
-      nstk = 0;
-      in_path = true;
-    }
-    YK_STAMP(1);
-    // ray_color prints its ray before the depth test (raytracer.hpp:21-25)
-    if (kCount && (ka.flags & kFlagTrace) && in_path) trace_ray(ka, slot, ka.max_depth - depth, o, d);
-
-    // ---- one segment of ray_color (raytracer.hpp:19-37) ----------------------------------
-    // (a) closest hit: hittable_list::hit_impl (hittable_list.hpp:32-58) over
-    //     sphere::hit_impl (sphere.hpp:25-48): tuple order, t_max shrinking to the last
-    //     accepted root, so the closest hit wins and an exact tie goes to the later sphere.
-    // depth == 0 → black (raytracer.hpp:23); lanes without a path (empty slot) sit this out
-    const bool alive = in_path && depth != 0;
-    Hit hit{INFINITY, -1, 0, 0, 0, 0};
-    if (alive) {
-      ++n_seg;
-      const double a = ykd::len2(d);
-      const double onorm = fmax(fabs(o.x), fmax(fabs(o.y), fabs(o.z)));
-      bool linear = (ka.flags & kFlagLinearScan) || !(a > 0 && a < INFINITY) ||
-                    !(onorm <= ka.origin_bound);
-      if (!linear) {
-        // BVH traversal: cull conservatively, keep every sphere whose exact root could be
-        // the minimum.  Slab distances as one FMA each,
-        // t = lo*(1/d) - o*(1/d): error relative 2^-22 plus an origin perturbation of
-        // 2^-23|o| (< delta/4), inside the culling contract of yk_bvh.hpp.  This is culling
-        // arithmetic only, so explicit FMAs are fine here.
-        // 1/d from v_rcp_f32 (1 ulp): with d's rounding to float and the FMA's rounding the
-        // slab distances stay within the 2^-22 relative error the culling contract assumes
-        // (2^-24 + 2^-23 + 2^-24).  Components outside [1e-30, 1e30] (never seen) take the
-        // correctly rounded division for the whole wave.
-        const float dxf = (float)d.x, dyf = (float)d.y, dzf = (float)d.z;
-        const float dmin = fminf(fminf(fabsf(dxf), fabsf(dyf)), fabsf(dzf));
-        const float dmax = fmaxf(fmaxf(fabsf(dxf), fabsf(dyf)), fabsf(dzf));
-        float ix, iy, iz;
-        if (__ballot(!(dmin > 1e-30f && dmax < 1e30f)) == 0) {
-          ix = __builtin_amdgcn_rcpf(dxf);
-          iy = __builtin_amdgcn_rcpf(dyf);
-          iz = __builtin_amdgcn_rcpf(dzf);
-        } else {
-          ix = safe_rcp(dxf);
-          iy = safe_rcp(dyf);
-          iz = safe_rcp(dzf);
-        }
-        const float oix = (float)o.x * ix, oiy = (float)o.y * iy, oiz = (float)o.z * iz;
-        // this ray's (near x4, far x4) plane quads inside a WideNode (yk_bvh.hpp), as base
-        // pointers: a visit then costs one address add per axis
-        const char* const px = nodes + (ix < 0.0f ? 16u : 0u);
-        const char* const py = nodes + 48u + (iy < 0.0f ? 16u : 0u);
-        const char* const pz = nodes + 96u + (iz < 0.0f ? 16u : 0u);
-        // Conservative interval test without per-visit relaxation: far distances
-        // come out of the FMA already scaled by c = 1 + 2^-17 (scaled 1/d and o/d), near
-        // distances are compared unscaled against tmin_lo = t_min (1 - 2^-17) and against
-        // ustar_f (U* (1 + 2^-18)).  A box passes iff
-        //   max(tn, tmin_lo) <= min(tf * c, ustar_f),
-        // which holds whenever the former test with both distances relaxed by 2^-20 held.
-        constexpr float kFar = 1.0f + 0x1p-17f;
-        // scaled far terms: ONE rounding of the origin product, as for the near terms, so the
-        // origin perturbation stays within delta/4 (yk_bvh.hpp); the rounding of ix*c is a
-        // relative error inside the 2^-17 margin
-        const float ixs = ix * kFar, iys = iy * kFar, izs = iz * kFar;
-        const float ox_f = (float)o.x, oy_f = (float)o.y, oz_f = (float)o.z;
-        const float tmin_lo = __double2float_rd(ka.t_min) * (1.0f - 0x1p-17f);
-        // Distances measured from tmin_lo and scaled by kClampScale = 2^-24: per
-        // axis (s/d, s(-o/d - tmin_lo)) (near) and (sc/d, s(-oc/d - tmin_lo)) (far).  The near
-        // FMAs clamp to [0, 1], which IS the max with tmin_lo (distances below 2^24 + tmin_lo
-        // never reach the clamp's 1; beyond, the clamp only lowers a near distance: more boxes
-        // kept, never fewer), so a slot costs max3 + min3 + min + compare.  s is a power of two
-        // (exact), the constants' subtraction one more rounding of the origin term
-        // (<= 2^-24 (|o/d| + t_min): inside the delta budget with the origin perturbation).
-        constexpr float kS = kClampScale;
-        const f2 sxp = {ix * kS, (-oix - tmin_lo) * kS}, syp = {iy * kS, (-oiy - tmin_lo) * kS},
-                 szp = {iz * kS, (-oiz - tmin_lo) * kS};
-        const f2 fxp = {ixs * kS, (-(ox_f * ixs) - tmin_lo) * kS}, fyp = {iys * kS, (-(oy_f * iys) - tmin_lo) * kS},
-                 fzp = {izs * kS, (-(oz_f * izs) - tmin_lo) * kS};
-        const double ia = ykd::rcp_bound(a);  // bounds only: relative error < 2^-44
-        double ustar = INFINITY;  // proven upper bound of the minimum exact root
-        float ustar_f = INFINITY;  // >= ustar * (1 + 2^-18) (clamped distances: >= s (that - tmin_lo))
-        // a lane whose 1/d could leave float's normal range once scaled (|d| >= 1e30, never seen)
-        // is marked for the exact linear scan from the start (nc = 5, as an overflow)
-        // the candidates' tuple ids as 16-bit halves (ids are < 2^16: ykgpu_set_scene's limit),
-        // entry 0 in cp01's low half
-        uint32_t nc = dmax < 1e30f ? 0u : 5u, cp01 = 0, cp23 = 0;
-        // hb and disc of entry 0 (always the newest candidate: a compaction is followed by the
-        // insertion that caused it), so its exact root needs no second discriminant
-        double hb0 = 0, disc0 = 0;
-        // candidate lower bounds kept as floats RN(L), compared with ustar_f >= RN(U*): by
-        // monotone rounding (all bounds >= 0) L <= U* implies RN(L) <= ustar_f, so the float
-        // comparison only ever keeps MORE candidates than the double comparison would
-        float l0 = 0, l1 = 0, l2 = 0, l3 = 0;
-        // overflow of the stack or of the candidate list is recorded as nc = 5, not as a flag of
-        // its own: a bool carried round the traversal loop lives in a lane mask that every
-        // divergent exit has to merge (-3.4% as a bool), an integer flag is one more loop-carried
-        // register (nc = 5 instead: -0.8%)
-        int32_t node = ka.bvh_root;
-        // this lane's traversal stack as LDS byte addresses (entries kBlk words apart).  `top` holds
-        // the address of the entry BELOW the top, kTopOff less than the top's (at the start: the
-        // sentinel's), so the visit's read of that entry and the pushes at the top take constant
-        // DS offsets.  (The expressions below spell the top's address less kTopOff out: the
-        // compiler schedules two instances differently when they are folded by hand.)
-        constexpr uint32_t kTopOff = kBlk * 4u;
-        const uint32_t stk_b = (uint32_t)(uintptr_t)stk;
-        uint32_t top = stk_b + kBlk * 4u - kTopOff;
-        const uint32_t stk_cap = stk_b + ka.stack_cap * kBlk * 4u - kTopOff;
-#define YK_STK(a) (*(__attribute__((address_space(3))) int32_t*)(uintptr_t)(a))
-        for (;;) {
-          if (node >= 0) {
-           // the lane's run of interior nodes as a loop of its own tested at the bottom: its exit
-           // value is the visit's own result, so the compiler keeps node / top / nc in place
-           do {
-            if (kCount) ++n_node;
-            YK_STAMP_NODE_ITERATION(lane);
-            // the entry below the top (the sentinel when the stack holds nothing), read with the
-            // planes: the pushes below write at and above the top, never here
-            const int32_t popped = YK_STK(top + kTopOff - kBlk * 4u);
-            // near / far distances of the 4 slots per axis, one packed FMA per pair of slots:
-            // t = plane*(1/d) - o*(1/d), the binary node's arithmetic per slot
-            const f4 qnx = *(const f4*)(px + node), qfx = *(const f4*)(px + node + 16);
-            const f4 qny = *(const f4*)(py + node), qfy = *(const f4*)(py + node + 16);
-            const f4 qnz = *(const f4*)(pz + node), qfz = *(const f4*)(pz + node + 16);
-            // the scene's LDS copy starts at LDS address 0 (the kernel's only LDS is the dynamic
-            // region, checked at the kernel's start), so the child codes of node n sit at n + 144
-            int4 ch;
-            if (kSceneInLds) {
-              typedef int i4v __attribute__((ext_vector_type(4)));
-              const i4v c4 = *(__attribute__((address_space(3))) const i4v*)(uintptr_t)((uint32_t)node + 144u);
-              ch = make_int4(c4.x, c4.y, c4.z, c4.w);
-            } else {
-              ch = *(const int4*)(nodes + node + 144);
-            }
-            bool hk[4];
-            const f2 nx[2] = {slab_fma_clamp(qnx.xy, sxp), slab_fma_clamp(qnx.zw, sxp)};
-            const f2 fx[2] = {slab_fma(qfx.xy, fxp), slab_fma(qfx.zw, fxp)};
-            const f2 ny[2] = {slab_fma_clamp(qny.xy, syp), slab_fma_clamp(qny.zw, syp)};
-            const f2 fy[2] = {slab_fma(qfy.xy, fyp), slab_fma(qfy.zw, fyp)};
-            const f2 nz[2] = {slab_fma_clamp(qnz.xy, szp), slab_fma_clamp(qnz.zw, szp)};
-            const f2 fz[2] = {slab_fma(qfz.xy, fzp), slab_fma(qfz.zw, fzp)};
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-              float tna, tfa, tnb, tfb;
-              slab_cull2c(nx[h][0], ny[h][0], nz[h][0], fx[h][0], fy[h][0], fz[h][0], nx[h][1], ny[h][1], nz[h][1],
-                          fx[h][1], fy[h][1], fz[h][1], ustar_f, tna, tfa, tnb, tfb);
-              hk[2 * h] = tna <= tfa;
-              hk[2 * h + 1] = tnb <= tfb;
-            }
-            // keep the child-code read in this block, issued with the plane reads (the compiler
-            // would otherwise sink it into the branch below and wait for it there)
-            asm volatile("" ::"v"(ch.x), "v"(ch.y), "v"(ch.z), "v"(ch.w));
-            {
-              // the last slot entered is visited next, the others entered are pushed in slot
-              // order; none entered: the popped entry is next and the top moves down one
-              const bool any = hk[0] || hk[1] || hk[2] || hk[3];
-              node = hk[3] ? ch.w : (hk[2] ? ch.z : (hk[1] ? ch.y : (hk[0] ? ch.x : popped)));
-              YK_STK(top + kTopOff) = ch.x;
-              top += (hk[0] && (hk[1] || hk[2] || hk[3])) ? kBlk * 4u : 0u;
-              YK_STK(top + kTopOff) = ch.y;
-              top += (hk[1] && (hk[2] || hk[3])) ? kBlk * 4u : 0u;
-              YK_STK(top + kTopOff) = ch.z;
-              top += (hk[2] && hk[3]) ? kBlk * 4u : (any ? 0u : 0u - kBlk * 4u);
-              // stack full: the top stays at the capacity and nc = 5 sends the lane to the scan
-              // (only where the plan could not give the stack its proven depth: ka.stack_check)
-              if (ka.stack_check) {
-                asm volatile("");  // (a scalar branch: no selects on the uniform flag)
-                // signed: the pop of the sentinel leaves `top` (the entry below the top) one entry below the
-                // stack's base, below LDS address 0 for the low lanes of a scene with a small LDS
-                // copy (unsigned, that wrapped past the capacity and the lane never left the loop)
-                nc = (int32_t)top > (int32_t)stk_cap ? 5u : nc;
-                top = (int32_t)top > (int32_t)stk_cap ? stk_cap : top;
-              }
-            }
-           } while (node >= 0);
-          }
-          {
-            YK_STAMP(2);  // interior nodes since the last stamp
-            const uint32_t v = ~(uint32_t)node, first = v >> 4, cnt = v & 15u;
-            // the FP64 tree has one sphere per leaf (max_leaf = 1: the builder's median fallback
-            // never leaves more), so a leaf is tested without a loop (512 spp: -0.9%); the empty
-            // leaf ~0 (cnt 0) tests nothing.  (`continue` inside the do-while(0) leaves the test.)
-            static_assert(kLeafCapF64 == 1, "the FP64 leaf test handles one sphere");
-            if (cnt != 0) do {
-              const uint32_t k = 0;
-              const SphereGeo sg = leaf_geo[first + k];
-              // the tuple index read with the geometry: its latency then hides under the
-              // discriminant instead of following the bounds on the insert path
-              const uint32_t id = leaf_ids[first + k];
-              asm volatile("" ::"v"(id));
-              ++n_test;
-              // the reference's discriminant, bit for bit (sphere.hpp:29-34)
-              const v3 oc = {o.x - sg.cx, o.y - sg.cy, o.z - sg.cz};
-              const double hb = ykd::dot(oc, d);
-              const double c = ykd::len2(oc) - sg.rr;
-              const double disc = hb * hb - a * c;
-              if (disc < 0) continue;
-              if (kCount) ++n_dpos;
-              YK_STAMP_DISC_POS();
-              // bounds of the exact root: |approx - exact| <= m (256x the error bound, §4)
-              const double sq = ykd::sqrt_bound(disc);
-              const double r1 = (-hb - sq) * ia, r2 = (-hb + sq) * ia;
-              const double m = (fabs(hb) + sq) * ia * 0x1p-34 + 0x1p-1000;
-              if (r2 + m < ka.t_min) continue;  // both roots certainly behind t_min
-              const double lb = fmax(ka.t_min, r1 - m);
-              const double ub = (r1 - m >= ka.t_min) ? r1 + m : ((r2 - m >= ka.t_min) ? r2 + m : INFINITY);
-              if (!(lb <= ustar)) continue;
-              if (ub < ustar) {
-                ustar = ub;
-                // s (RN(ub)(1 + 2^-18) - tmin_lo), rounded up by the factor 1 + 2^-22: >= s (the
-                // unshifted bound - tmin_lo), positive (ub >= t_min > tmin_lo)
-                ustar_f = ((float)ub * (1.0f + 0x1p-18f) - tmin_lo) * ((1.0f + 0x1p-22f) * kClampScale);
-              }
-              if (nc == 4) {  // compact: drop entries the new bound has excluded
-                uint32_t m2 = 0;
-                uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-                const uint32_t d0 = cp01 & 0xffffu, d1 = cp01 >> 16, d2 = cp23 & 0xffffu, d3 = cp23 >> 16;
-                float e0 = l0, e1 = l1, e2 = l2, e3 = l3;
-                if (e0 <= ustar_f) { YK_CAND_SET(m2, d0, e0); ++m2; }
-                if (e1 <= ustar_f) { YK_CAND_SET(m2, d1, e1); ++m2; }
-                if (e2 <= ustar_f) { YK_CAND_SET(m2, d2, e2); ++m2; }
-                if (e3 <= ustar_f) { YK_CAND_SET(m2, d3, e3); ++m2; }
-                nc = m2;
-                cp01 = c0 | (c1 << 16);
-                cp23 = c2 | (c3 << 16);
-              }
-              if (nc < 4) {
-                // shifted in at entry 0 — straight-line moves instead of a branch per list
-                // position (evaluation order never matters: min root, later index on ties).
-                // RN(lb), not rounded down: t_min >= 0 (checked by the host) makes every lb and
-                // U* >= 0, and lb <= U* implies RN(lb) <= RN(U*) <= ustar_f (monotone rounding),
-                // so the list still keeps every sphere that can be the minimum
-                cp23 = __builtin_amdgcn_alignbit(cp23, cp01, 16u);  // (cp23 << 16) | (cp01 >> 16)
-                cp01 = (cp01 << 16) | id;
-                l3 = l2, l2 = l1, l1 = l0;
-                hb0 = hb, disc0 = disc;
-                // the same monotone map as ustar_f's: s RN(RN(lb) - tmin_lo) (one FMA, s a power of
-                // two), so lb <= U* still implies l0 <= ustar_f
-                l0 = __builtin_fmaf((float)lb, kClampScale, -tmin_lo * kClampScale);
-                ++nc;
-              } else {
-                nc = 5;  // the list is full: overflow (the exact linear scan decides)
-              }
-            } while (0);
-            YK_STAMP(6);  // this leaf
-          }
-          if (top + kTopOff <= stk_b + kBlk * 4u) break;  // only the sentinel left, or the sentinel just visited
-          top -= kBlk * 4u;
-          node = YK_STK(top + kTopOff);
-#undef YK_STK
-        }
-        YK_STAMP(2);
-        if (nc > 4) {
-          linear = true;
-        } else {
-          // exact evaluation of the survivors; the roots' divisor a is the same for every
-          // candidate of a ray, so its refined reciprocal is computed once
-          const bool a_ok = ykd::div_range(a);
-          const double ra = (nc > 0 && a_ok) ? ykd::rcp_refined(a) : 0.0;
-          const uint32_t c0 = cp01 & 0xffffu, c1 = cp01 >> 16, c2 = cp23 & 0xffffu, c3 = cp23 >> 16;
-          if (nc > 0 && l0 <= ustar_f) exact_root(c0, hb0, disc0, a, ra, a_ok, ka.t_min, hit);
-          if (nc > 1 && l1 <= ustar_f) exact_candidate(geo, c1, o, d, a, ra, a_ok, ka.t_min, hit);
-          if (nc > 2 && l2 <= ustar_f) exact_candidate(geo, c2, o, d, a, ra, a_ok, ka.t_min, hit);
-          if (nc > 3 && l3 <= ustar_f) exact_candidate(geo, c3, o, d, a, ra, a_ok, ka.t_min, hit);
-        }
-      }
-      if (linear) {
-        hit = scan_linear(ka.geo, ka.nspheres, o, d, ka.t_min);
-        n_test += hit.tests;
-        ++n_lin;
-      }
-      n_sqrt += hit.sqrts;
-      n_ncall += hit.ncalls;
-      n_nit += hit.nits;
-    }
-    YK_STAMP(3);
-
-    // (b) shade, material-uniform: every operation more than one material needs runs ONCE for all
-    //     the lanes that need it, instead of once per material branch (a wave holds every kind
-    //     almost every trip, so per-branch copies run one after the other):
-    //   * one block of canonicals: lambertian's vec3::random (3), the fuzzed metal's length factor
-    //     and vector (4), the dielectric's reflect-or-refract uniform (1, drawn speculatively:
-    //     given back when total internal reflection means the reference never draws it);
-    //   * one vector normalisation — the sky's normalized(dir) (raytracer.hpp:35), lambertian's
-    //     random_unit_vector (material.hpp:33-36), metal's / dielectric's normalized(dir);
-    //   * one more Newton square root: the fuzzed metal's |vector| or the dielectric's sin(theta).
-    //   Each lane's own operations and their order are the reference's.
-    bool ended = in_path && !alive;
-    double L_r = 0, L_g = 0, L_b = 0;
-    if (alive) {
-      const int hid = hit.hid;
-      const double T = hit.T;
-      SphereGeo sg{0, 0, 0, 0};
-      SphereMat m{};
-      v3 p{0, 0, 0}, nrm{0, 0, 0};
-      bool front = false;
-      if (hid >= 0) {
-        sg = geo[hid];
-        m = mat[hid];
-        // hit record (sphere.hpp:41-45, hittable.hpp:23-27)
-        p = ykd::add(o, ykd::mul(d, T));
-        const v3 outward = ykd::divs_fast_r(ykd::sub(p, v3{sg.cx, sg.cy, sg.cz}), m.radius, m.inv_r);
-        front = ykd::dot(d, outward) < 0;
-        nrm = front ? outward : ykd::neg(outward);
-      }
-      const bool lamb = hid >= 0 && m.kind == YK_MATERIAL_LAMBERTIAN;
-      const bool fuzzy = hid >= 0 && m.kind == YK_MATERIAL_METAL && m.fuzz > 0;
-      const bool diel = hid >= 0 && m.kind == YK_MATERIAL_DIELECTRIC;
-      const bool spec = diel && ykd::rng_can_speculate(g);
-      const Gen saved = g;  // the dielectric's engine before its speculative draw
-      const uint32_t ncan = lamb ? 3u : (fuzzy ? 4u : (spec ? 1u : 0u));
-      double c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-      if (__ballot(ncan > 0 && !ykd::rng_lazy_ok(g, 2 * ncan)) == 0) {
-        // (almost always) no lane of the wave reaches the scratch engine's words: no checks
-        if (ncan > 0) c0 = ykd::canonical<true>(g);
-        if (ncan > 1) c1 = ykd::canonical<true>(g);
-        if (ncan > 2) c2 = ykd::canonical<true>(g);
-        if (ncan > 3) c3 = ykd::canonical<true>(g);
-      } else {
-        if (ncan > 0) c0 = ykd::canonical(g);
-        if (ncan > 1) c1 = ykd::canonical(g);
-        if (ncan > 2) c2 = ykd::canonical(g);
-        if (ncan > 3) c3 = ykd::canonical(g);
-      }
-      // lambertian: vec3::random(gen, -1, 1), x then y then z (vec3.hpp:134-142); fuzzed metal:
-      // random(-1,1).normalize() * uniform(0.01,0.99) with the factor drawn first — g++, the
-      // reference's compiler, evaluates that product's operands right to left (pinned by the
-      // reference-harness goldens, tests/golden/gen_golden.py)
-      const v3 rv = lamb ? v3{ykd::uniform_of(c0, -1, 1), ykd::uniform_of(c1, -1, 1), ykd::uniform_of(c2, -1, 1)}
-                         : v3{ykd::uniform_of(c1, -1, 1), ykd::uniform_of(c2, -1, 1), ykd::uniform_of(c3, -1, 1)};
-      const v3 vn = lamb ? rv : d;
-      const double len = ykd::nsqrt_c(ykd::len2(vn), n_ncall, n_nit);  // vec3::length(), vec3.hpp:127
-      // vn / len is what every branch below divides (sky: d.y / len; lambertian: the random
-      // vector; metal, dielectric: d), so it is computed once here, not once per branch
-      const v3 un = ykd::divs_fast(vn, len);
-      double ct = 0;  // dielectric: cos(theta) = min(dot(-unit, n), 1)
-      if (diel) {
-        ct = ykd::dot(ykd::neg(un), nrm);
-        if (!(ct < 1.0)) ct = 1.0;
-      }
-      double sq2 = 0;  // fuzzed metal: |random vector|; dielectric: sin(theta)
-      if (fuzzy || diel) sq2 = ykd::nsqrt_c(fuzzy ? ykd::len2(rv) : 1.0 - ct * ct, n_ncall, n_nit);
-      if (hid < 0) {
-        // sky (raytracer.hpp:35-36): t = (normalized(dir).y + 1)/2, lerp white → (.5,.7,1)
-        const double t = (un.y + 1.0) / 2;
-        L_r = (1.0 - t) * 1.0 + t * 0.5;
-        L_g = (1.0 - t) * 1.0 + t * 0.7;
-        L_b = (1.0 - t) * 1.0 + t * 1.0;
-        ended = true;
-      } else {
-        bool scattered = true, push = true;
-        v3 nd;
-        if (m.kind == YK_MATERIAL_LAMBERTIAN) {  // material.hpp:50-59
-          if (kCount) ++n_lamb;
-          nd = ykd::add(nrm, un);
-          if (ykd::near_zero(nd)) nd = nrm;
-        } else if (m.kind == YK_MATERIAL_METAL) {  // material.hpp:67-75 (+ fuzz extension)
-          if (kCount) ++n_metal;
-          nd = ykd::reflect(un, nrm);
-          if (fuzzy) {  // + fuzz * random_in_unit_sphere (material.hpp:27-30)
-            if (kCount) ++n_fuzz;
-            const double k = ykd::uniform_of(c0, 0.01, 0.99);
-            const v3 ru = ykd::divs_fast(rv, sq2);
-            nd = ykd::add(nd, ykd::mul(ykd::mul(ru, k), m.fuzz));
-          }
-          scattered = ykd::dot(nd, nrm) > 0;
-        } else {  // dielectric extension (attenuation (1,1,1): multiplying by 1.0 is exact)
-          if (kCount) ++n_diel;
-          push = false;
-          // 1/ior and Schlick's r0 of both sides precomputed on the host with the same IEEE
-          // operations (ykgpu_set_scene: the dielectric's unused fuzz / albedo fields)
-          const double ratio = front ? m.fuzz : m.ior;
-          const double r0 = front ? m.ar : m.ag;
-          const v3 unit = un;
-          const double sn = sq2;
-          const bool cannot = ratio * sn > 1.0;
-          double u = 0;
-          if (cannot) {
-            if (spec) g = saved;  // `cannot || ...` never draws: give the word pair back
-          } else {
-            u = spec ? ykd::uniform_of(c0, 0, 1) : ykd::uniform(g, 0, 1);
-          }
-          if (cannot || ykd::reflectance_r0(ct, r0) > u) {
-            nd = ykd::reflect(unit, nrm);
-          } else {
-            const v3 perp = ykd::mul(ykd::add(unit, ykd::mul(nrm, ct)), ratio);
-            const double pl = 1.0 - ykd::len2(perp);
-            nd = ykd::add(perp, ykd::mul(nrm, -ykd::nsqrt_c(pl < 0 ? -pl : pl, n_ncall, n_nit)));
-          }
-        }
-        if (!scattered) {
-          ended = true;  // absorbed: black (raytracer.hpp:30)
-        } else {
-          if (push) {
-            if (nstk >= kStackRegs) id_spill[nstk - kStackRegs] = (uint16_t)(st3 >> 16);
-            st3 = (st3 << 16) | (st2 >> 16);
-            st2 = (st2 << 16) | (st1 >> 16);
-            st1 = (st1 << 16) | (st0 >> 16);
-            st0 = (st0 << 16) | (uint32_t)hid;
-            ++nstk;
-          }
-          o = p;
-          d = nd;
-          --depth;
-        }
-      }
-    }
-    YK_STAMP(4);
-
-    if (ended) {
-      // unwind: attenuation_k * (...) from the deepest scatter outwards (raytracer.hpp:31)
-      auto pop = [&]() {
-        const uint32_t id = st0 & 0xffffu;
-        st0 = (st0 >> 16) | (st1 << 16);
-        st1 = (st1 >> 16) | (st2 << 16);
-        st2 = (st2 >> 16) | (st3 << 16);
-        st3 = (st3 >> 16) | (nstk > kStackRegs ? ((uint32_t)id_spill[nstk - kStackRegs - 1] << 16) : 0u);
-        --nstk;
-        return id;
-      };
-      if (__ballot(nstk > kStackRegs) == 0) {
-        // no ending lane of the wave holds spilled ids: the register window alone, two ids per
-        // round (the window moves by a whole register)
-        while (nstk > 0) {
-          const SphereMat m = mat[st0 & 0xffffu];
-          L_r = m.ar * L_r;
-          L_g = m.ag * L_g;
-          L_b = m.ab * L_b;
-          if (nstk > 1) {
-            const SphereMat m2 = mat[st0 >> 16];
-            L_r = m2.ar * L_r;
-            L_g = m2.ag * L_g;
-            L_b = m2.ab * L_b;
-          }
-          st0 = st1, st1 = st2, st2 = st3;
-          nstk = nstk > 1 ? nstk - 2 : 0;
-        }
-      } else {
-        while (nstk > 0) {
-          const SphereMat m = mat[pop()];
-          L_r = m.ar * L_r;
-          L_g = m.ag * L_g;
-          L_b = m.ab * L_b;
-        }
-      }
-      if (ykd::mt_used_fallback(g)) ++n_fb;
-      if (kCount) n_words += ykd::rng_words(g), n_twist += ykd::rng_twists(g);
-      // the sample's colour; yk_reduce_samples adds them in sample order
-      colour_store(ka.col, slot, L_r, L_g, L_b);
-      in_path = false;
-    }
-    YK_STAMP(5);
-  }
-
-  YK_CLOCK_END(ka);
-  YK_WAVE_STAMP(ka, 1);
-  YK_STAMPS_END(ka.counters, lane);
-  if (kCount) {
-    atomicAdd(&ka.counters[0], (unsigned long long)n_seg);
-    atomicAdd(&ka.counters[1], (unsigned long long)n_test);
-    atomicAdd(&ka.counters[2], (unsigned long long)n_sqrt);
-    atomicAdd(&ka.counters[4], (unsigned long long)n_node);
-    atomicAdd(&ka.counters[5], (unsigned long long)n_lin);
-    atomicAdd(&ka.counters[6], (unsigned long long)n_ncall);
-    atomicAdd(&ka.counters[7], (unsigned long long)n_nit);
-    atomicAdd(&ka.counters[24], (unsigned long long)n_dpos);
-    atomicAdd(&ka.counters[25], (unsigned long long)n_lamb);
-    atomicAdd(&ka.counters[26], (unsigned long long)n_metal);
-    atomicAdd(&ka.counters[27], (unsigned long long)n_fuzz);
-    atomicAdd(&ka.counters[28], (unsigned long long)n_diel);
-    atomicAdd(&ka.counters[29], (unsigned long long)n_words);
-    atomicAdd(&ka.counters[30], (unsigned long long)n_swords);
-    atomicAdd(&ka.counters[31], (unsigned long long)n_twist);
-  }
-  if (n_fb) atomicAdd(&ka.counters[3], (unsigned long long)n_fb);
-}
-
-// The kernels.  Production instances at <= YK_RENDER_VGPRS (gfx950's amdgpu_num_vgpr counts the
-// unified file, so the attribute takes half).
-template <bool kSceneInLds, int kMode>
-__global__ __launch_bounds__(mode_block<kMode>())
-__attribute__((amdgpu_waves_per_eu(4, 8)))
-__attribute__((amdgpu_num_vgpr(YK_RENDER_VGPRS / 2)))
-void yk_render_persistent(KernelArgs ka) {
-  render_body<kSceneInLds, kMode>(ka);
-}
-// the counting instances (kMode bit 0: diagnostic builds of the same body, YK_FLAG_COUNT_WORK)
-// under a name of their own, their registers uncapped
-template <bool kSceneInLds, int kMode>
-__global__ __launch_bounds__(mode_block<kMode>()) __attribute__((amdgpu_waves_per_eu(1, 8)))
-void yk_render_counting(KernelArgs ka) {
-  render_body<kSceneInLds, kMode>(ka);
-}
-
-// The FP64 instance for (scene in LDS, kMode)
-RenderKernel fp64_kernel(bool lds, int mode) {
-  static const RenderKernel k[16] = {
-      yk_render_persistent<false, 0>, yk_render_counting<false, 1>,  yk_render_persistent<false, 2>,
-      yk_render_counting<false, 3>,   yk_render_persistent<false, 4>, yk_render_counting<false, 5>,
-      yk_render_persistent<false, 6>, yk_render_counting<false, 7>,  yk_render_persistent<true, 0>,
-      yk_render_counting<true, 1>,    yk_render_persistent<true, 2>,  yk_render_counting<true, 3>,
-      yk_render_persistent<true, 4>,  yk_render_counting<true, 5>,    yk_render_persistent<true, 6>,
-      yk_render_counting<true, 7>};
-  return k[(lds ? 8 : 0) + (mode & 7)];
-}
-
-#endif  // YK_SPLIT != 2
-
-#if YK_SPLIT != 1
-
-// ---- render<float> (YK_PRECISION_FP32) ---------------------------------------------------
-// The same persistent, sample-parallel structure as yk_render_persistent (refill, slots, start
-// records from yk_mt_warmup, attenuation-id stack, SoA colours reduced by yk_reduce_samples),
-// with the path in float (yk_device_f32.hpp).  Closest hit: the FP32 tree culls — its boxes and
-// a per-ray cone carry the float sphere test's proven error — the spheres of an
-// entered leaf get the reference's float discriminant and bounds of their float root, and the
-// survivors' exact float roots are evaluated after the traversal: the minimum root wins, an exact
-// tie goes to the later tuple index.  Rays outside the tree's proven range take the ordered scan
-// (hittable_list.hpp:32-58).
-template <class G>
-__device__ __forceinline__ float f_uniform01(G& g) { return ykf::uniform(g, 0.0f, 1.0f); }
-
-// sphere::hit_impl<float> (sphere.hpp:25-48) bit for bit, without t_max.  Returns 2 with the root
-// in r (root1 if >= tmin, else root2: the reference accepts it iff r <= t_max, because root2 >=
-// root1 under monotonic rounding), 1 when both roots lie below tmin, 0 when disc < 0.
-// n / a for a root, a's refined reciprocal ra shared by the ray's candidates (ykf::div_by); a wave
-// with any lane out of range takes the full division
-__device__ __forceinline__ float f32_root_div(float n, float a, float ra, bool a_ok) {
-  float q = ykf::div_by(n, a, ra);
-  if (__builtin_expect(__ballot(!(a_ok && ykf::num_range(n))) != 0, 0)) q = n / a;
-  return q;
-}
-__device__ __forceinline__ int f32_root(float4 sg, ykf::v3 o, ykf::v3 d, float a, float ra, bool a_ok, float tmin,
-                                        float& r, uint32_t& nit) {
-  const ykf::v3 oc = {o.x - sg.x, o.y - sg.y, o.z - sg.z};
-  const float hb = ykf::dot(oc, d);
-  const float c = ykf::len2(oc) - sg.w;
-  const float disc = hb * hb - a * c;
-  if (disc < 0) return 0;
-  const float sq = ykf::nsqrt(disc, nit);
-  r = f32_root_div(-hb - sq, a, ra, a_ok);
-  if (r < tmin) {
-    r = f32_root_div(-hb + sq, a, ra, a_ok);
-    if (r < tmin) return 1;
-  }
-  return 2;
-}
-
-// the cone keeps a far bound on an axis with |d| >= kF32FarAt s, and gives the slow-axis bound
-// to one with |d| < kF32SlowAt s (d - s sign d stays clear of 0 in both)
-constexpr float kF32FarAt = 1.0f + 0x1p-10f, kF32SlowAt = 1.0f - 0x1p-10f;
-
-// Bounds of the root f32_root returns, from the exact float discriminant: the
-// approximation r = (-hb ∓ v_sqrt_f32(disc)) · v_rcp_f32(a) differs from the exact root by at most
-// (|hb| + √disc)/a · 9u (one-step sqrt within 1.5u, v_sqrt/v_rcp within an ulp, three roundings;
-// u = 2^-24); m takes 256u, plus an absolute term for underflowing products.  A disc outside the
-// one-step square root's range [2^-100, 2^100] gets no bound (m = inf: always a candidate).
-// Returns false when both roots certainly lie below tmin; else lb <= the accepted root <= ub
-// (ub = inf when neither root is certainly >= tmin).  NaN anywhere keeps the sphere (every
-// comparison that would drop it is false).
-__device__ __forceinline__ bool f32_root_bounds(float hb, float disc, float ia, float tmin, float& lb, float& ub) {
-  const float sq = __builtin_amdgcn_sqrtf(disc);
-  const float r1 = (-hb - sq) * ia, r2 = (-hb + sq) * ia;
-  float m = (fabsf(hb) + sq) * ia * 0x1p-16f + 0x1p-120f;
-  if (!(disc >= 0x1p-100f && disc <= 0x1p100f)) m = INFINITY;
-  if (r2 + m < tmin) return false;
-  lb = fmaxf(tmin, r1 - m);
-  ub = (r1 - m >= tmin) ? r1 + m : ((r2 - m >= tmin) ? r2 + m : INFINITY);
-  return true;
-}
-
-// One axis of the ray's cone: near planes are crossed at (plane - o) * in, far
-// planes at (plane - o) * jf, with in = 1/(d + s sign d) and jf = (1 + 2^-17)/(d - s sign d); an
-// axis with |d| < kF32FarAt s keeps no far bound (jf = 0, constant +inf).  Slab FMA operands:
-// plane * in + nc.  Culling arithmetic only: v_rcp_f32's ulp is inside the relative margins (d - s
-// sign d is exact for |d| <= 2s, Sterbenz).
-__device__ __forceinline__ void cone_axis(float dk, float ok, float s, f2& in2, f2& nc2, f2& jf2, f2& fc2) {
-  const float sg = dk < 0.0f ? -s : s;
-  const float in = __builtin_amdgcn_rcpf(dk + sg);
-  const bool far = fabsf(dk) >= kF32FarAt * s;
-  const float jf = far ? __builtin_amdgcn_rcpf(dk - sg) * (1.0f + 0x1p-17f) : 0.0f;
-  const float nc = -(ok * in), fc = far ? -(ok * jf) : INFINITY;
-  // the pairs (in, nc) and (jf, fc), read by op_sel (yk_slab.hpp); nc2 / fc2 are unused (dropping
-  // the two dead parameters changes the FP32 kernels' schedule)
-  in2 = f2{in, nc};
-  jf2 = f2{jf, fc};
-  nc2 = fc2 = f2{0.0f, 0.0f};
-}
-
-// kSceneInLds: the FP32 tree, its float4 leaf geometry and its leaf ids copied into LDS per
-// workgroup, as in the FP64 kernel.  kMode bit 0: the work counters; bit 2: the yk::xor128
-// engine (as for the FP64 kernel)
-template <bool kSceneInLds, int kMode>
-__global__ __launch_bounds__(mode_block<kMode>())
-void yk_render_f32(KernelArgs ka) {
-  constexpr int kBlk = mode_block<kMode>();
-  constexpr bool kCount = (kMode & 1) != 0;
-  using Gen = typename std::conditional<(kMode & 4) != 0, ykd::X128Lane, ykd::MtLane>::type;
-  const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63u;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const char* __restrict__ nodes = (const char*)ka.nodes;
-  const float4* __restrict__ leaf_geo = (const float4*)ka.leaf_geo;
-  const uint32_t* __restrict__ leaf_ids = ka.leaf_ids;
-  const float4* __restrict__ geo_f = ka.geo_f;  // tuple order: hit records
-  const SphereMat* __restrict__ mat = ka.mat;   // shading, attenuation unwind
-  if (kSceneInLds) {
-    // as in the FP64 kernel: the BVH, its leaf geometry and ids, and the tuple-order tables
-    const uint4* src[5] = {(const uint4*)ka.nodes, (const uint4*)ka.leaf_geo, (const uint4*)ka.leaf_ids,
-                           (const uint4*)ka.geo_f, (const uint4*)ka.mat};
-    const uint32_t off[5] = {0u, ka.lds_geo_off, ka.lds_ids_off, ka.lds_tgeo_off, ka.lds_mat_off};
-    const uint32_t n16[5] = {(ka.n_nodes * (uint32_t)sizeof(DevNode) + 15u) / 16u, ka.nspheres,
-                             (ka.nspheres + 3u) / 4u, ka.nspheres, ka.nspheres * 4u};
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      uint4* dst = (uint4*)(smem + off[k]);
-      for (uint32_t i = threadIdx.x; i < n16[k]; i += kBlk) dst[i] = src[k][i];
-    }
-    __syncthreads();
-    nodes = smem;
-    leaf_geo = (const float4*)(smem + ka.lds_geo_off);
-    leaf_ids = (const uint32_t*)(smem + ka.lds_ids_off);
-    geo_f = (const float4*)(smem + ka.lds_tgeo_off);
-    mat = (const SphereMat*)(smem + ka.lds_mat_off);
-  }
-  int32_t* const stk = (int32_t*)(smem + ka.lds_stack_off) + threadIdx.x;  // [sp * kBlk]
-  __builtin_amdgcn_s_setprio(1);  // over the co-resident warm-up waves, as in FP64
-  YK_CLOCK_BEGIN(ka);
-  Gen g;
-  rng_init(g, ka, gid);
-  uint16_t* const id_spill = ka.id_scratch + (size_t)gid * ka.id_stride;
-  uint32_t n_seg = 0, n_test = 0, n_sqrt = 0, n_fb = 0, n_nit = 0, n_ncall = 0, n_node = 0, n_lin = 0;
-  uint32_t n_words = 0, n_swords = 0, n_twist = 0;  // as in yk_render_persistent
-  YK_STAMPS_BEGIN(ka.counters, lane);
-  const float tmin = (float)ka.t_min;  // world.hit(r, 0.001, ...) converts to T (hittable.hpp:32)
-  uint32_t slot = 0, depth = 0, nstk = 0;
-  uint32_t st0 = 0, st1 = 0, st2 = 0, st3 = 0;
-  ykf::v3 o = {0, 0, 0}, d = {0, 0, 0};
-  bool in_path = false;
-  uint32_t res_base = 0, res_left = 0;
-
-  for (;;) {
-    if (claim_slots(ka, in_path, lane, slot, res_base, res_left)) {
-      YK_STAMPS_EXHAUSTED(ka.counters);
-      break;
-    }
-    YK_STAMP(0);
-
-    // ---- start: seed, jitter, camera<float>::get_ray (source.cpp:154-165, camera.hpp:29-32)
-    bool start = !in_path;
-    uint32_t qpix = 0;
-    // mt19937: the start (draws and camera<float> ray) comes precomputed (yk_mt_warmup<lens,
-    // true>: StartRecF), which alone says whether the slot is empty, as in the FP64 kernel
-    constexpr bool kRec = std::is_same<Gen, ykd::MtLane>::value;
-    uint4 rq0 = {0, 0, 0, 0}, rq1 = {0, 0, 0, 0}, rq2 = {0, 0, 0, 0};
-    if (start) {
-      if constexpr (kRec) {
-        const uint4* rp = (const uint4*)ka.start + 3u * slot;
-        rq0 = rp[0];
-        rq1 = rp[1];
-        rq2 = rp[2];
-        asm volatile("" ::"v"(rq0.x), "v"(rq0.y), "v"(rq0.z), "v"(rq0.w), "v"(rq1.x), "v"(rq1.y),
-                     "v"(rq2.x), "v"(rq2.y), "v"(rq2.z), "v"(rq2.w));
-        start = rq2.w != kPadSlot;
-      } else {
-        const uint32_t sl = fdiv(slot, ka.nps_m, ka.nps_sh);
-        qpix = ka.order[slot - sl * ka.npix_slots];
-        start = qpix != kNoPixel;
-      }
-    }
-    if (start) {
-      bool pre = false;
-      if constexpr (kRec) {
-        StartRecF r;
-        __builtin_memcpy((char*)&r, &rq0, 16);
-        __builtin_memcpy((char*)&r + 16, &rq1, 16);
-        __builtin_memcpy((char*)&r + 32, &rq2, 16);
-        pre = r.j != kNoStart;
-        if (pre) {
-          if (kCount) n_swords += r.j;
-          g.a0 = r.a0;
-          g.a1 = r.a1;
-          g.b = r.b;
-          g.j = r.j;
-          o = ykf::v3{r.ox, r.oy, r.oz};
-          d = ykf::v3{r.dx, r.dy, r.dz};
-        }
-      }
-      if (!pre) {
-        const uint32_t sl = fdiv(slot, ka.nps_m, ka.nps_sh);
-        if constexpr (kRec) qpix = ka.order[slot - sl * ka.npix_slots];
-        const uint32_t s = ka.s0 + sl;
-        const uint32_t tr = fdiv(qpix, ka.w_m, ka.w_sh);
-        const uint32_t x = tile_col_x(ka.col_begin, ka.col_stride, ka.col_band, qpix - tr * ka.Wt);
-        const uint32_t y = tile_row_y(ka.row_begin, ka.row_stride, ka.band_log2, tr);
-        const uint32_t seed = ykd::sample_seed(ka.seed_mode, ka.seed_key, ka.seed0, y, x, ka.W, ka.spp, s);
-        const bool lens = ka.cam.lens_radius > 0;  // (decided in double, as for the warm-up)
-        rng_start_full(g, seed);
-        const float uc = f_uniform01(g);
-        const float vc = f_uniform01(g);
-        float px = 0, py = 0;
-        if (lens) {  // thin-lens extension: random_in_unit_disk by rejection, x then y
-          do {
-            px = ykf::uniform(g, -1.0f, 1.0f);
-            py = ykf::uniform(g, -1.0f, 1.0f);
-          } while (!(px * px + py * py < 1.0f));
-        }
-        camera_ray_f32(ka.camf, ka.H, x, y, uc, vc, lens, px, py, o, d);
-      }
-      depth = ka.max_depth;
-      nstk = 0;
-      in_path = true;
-    }
-
-    YK_STAMP(1);
-    if (kCount && (ka.flags & kFlagTrace) && in_path) trace_ray(ka, slot, ka.max_depth - depth, o, d);
-
-    // ---- closest hit (hittable_list.hpp:32-58 over sphere.hpp:25-48, in float)
-    const bool alive = in_path && depth != 0;
-    float T = INFINITY;
-    int hid = -1;
-    if (alive) {
-      ++n_seg;
-      const float a = ykf::len2(d);
-      const float onorm = fmaxf(fabsf(o.x), fmaxf(fabsf(o.y), fabsf(o.z)));
-      // the tree serves the rays its bound is proven for: |d|^2 in [2^-60, 2^60],
-      // origin within origin_bound (< 0: the scene is outside the proven scale); the rest scan
-      bool linear = (ka.flags & kFlagLinearScan) || !(a >= 0x1p-60f && a <= 0x1p60f) ||
-                    !((double)onorm <= ka.origin_bound);
-      if (!linear) {
-        const float s = __builtin_sqrtf(a) * ykbvh::kF32Cone;  // the cone's slope (>= kF32Cone |d|)
-        const float tmin_lo = tmin * (1.0f - 0x1p-17f);
-        float ustar_f = INFINITY;  // T (1 + 2^-18): every box that may hold a root <= T passes
-        f2 inx, ncx, jfx, fcx, iny, ncy, jfy, fcy, inz, ncz, jfz, fcz;
-        cone_axis(d.x, o.x, s, inx, ncx, jfx, fcx);
-        cone_axis(d.y, o.y, s, iny, ncy, jfy, fcy);
-        cone_axis(d.z, o.z, s, inz, ncz, jfz, fcz);
-        // the (near x4, far x4) plane quads of the ray's direction signs inside a WideNode
-        const char* const px = nodes + (d.x < 0.0f ? 16u : 0u);
-        const char* const py = nodes + 48u + (d.y < 0.0f ? 16u : 0u);
-        const char* const pz = nodes + 96u + (d.z < 0.0f ? 16u : 0u);
-        // A slow axis (|d| < s, the cone opens both ways along it) has no far bound, but the cone
-        // still enters a box that lies against the direction of travel only after its far-side
-        // plane: o + (d - s sign d) t reaches it at t = (plane - o) / (d - s sign d) > 0, a lower
-        // bound like a near distance (same FMA form and error).  Without it, a
-        // ray grazing a field of boxes enters every box under its path.  One slow axis per ray
-        // gets the bound (y, then x, then z); the others keep L = -inf.
-        f2 jl2 = {0.0f, -INFINITY};  // the (jl, cl) pair
-        const char* pl = px + 16;
-        {
-          const float slow = s * kF32SlowAt;
-          const float dk[3] = {d.z, d.x, d.y}, ok[3] = {o.z, o.x, o.y};
-          const char* const pk[3] = {pz, px, py};
-#pragma unroll
-          for (int k = 0; k < 3; ++k) {
-            if (fabsf(dk[k]) < slow) {
-              const float jl = __builtin_amdgcn_rcpf(dk[k] - (dk[k] < 0.0f ? -s : s));
-              jl2 = f2{jl, -(ok[k] * jl)};  // (jl, cl), read by op_sel
-              pl = pk[k] + 16;
-            }
-          }
-        }
-        // U*: proven upper bound of the minimum root (culls with ustar_f = U* (1 + 2^-18)); the
-        // candidate list (tuple index, lower bound) as in the FP64 kernel, nc = 5 on overflow
-        const float ia = __builtin_amdgcn_rcpf(a);  // a in [2^-60, 2^60] here
-        float ustar = INFINITY;
-        uint32_t nc = 0, c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-        float l0 = 0, l1 = 0, l2 = 0, l3 = 0;
-        uint32_t overflow = 0;  // a VGPR, not a lane-mask bool (see the FP64 kernel)
-        int32_t node = ka.bvh_root;
-        int32_t* top = stk;
-        const int32_t* const stk_cap = stk + ka.stack_cap * kBlk;
-        for (;;) {
-          if (node >= 0) {
-            if (kCount) ++n_node;
-            YK_STAMP_NODE_ITERATION(lane);
-            // the FP64 kernel's visit (same planes, margins and visit order), the cone's operands
-            const f4 qnx = *(const f4*)(px + node), qfx = *(const f4*)(px + node + 16);
-            const f4 qny = *(const f4*)(py + node), qfy = *(const f4*)(py + node + 16);
-            const f4 qnz = *(const f4*)(pz + node), qfz = *(const f4*)(pz + node + 16);
-            const int4 ch = *(const int4*)(nodes + node + 144);
-            bool hk[4];
-            const f2 nx[2] = {slab_fma(qnx.xy, inx), slab_fma(qnx.zw, inx)};
-            const f2 fx[2] = {slab_fma(qfx.xy, jfx), slab_fma(qfx.zw, jfx)};
-            const f2 ny[2] = {slab_fma(qny.xy, iny), slab_fma(qny.zw, iny)};
-            const f2 fy[2] = {slab_fma(qfy.xy, jfy), slab_fma(qfy.zw, jfy)};
-            const f2 nz[2] = {slab_fma(qnz.xy, inz), slab_fma(qnz.zw, inz)};
-            const f2 fz[2] = {slab_fma(qfz.xy, jfz), slab_fma(qfz.zw, jfz)};
-            const f4 qsl = *(const f4*)(pl + node);
-            const f2 sl[2] = {slab_fma(qsl.xy, jl2), slab_fma(qsl.zw, jl2)};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              const float tn = slab_max3(slab_max3(nx[k >> 1][k & 1], ny[k >> 1][k & 1], nz[k >> 1][k & 1]),
-                                         sl[k >> 1][k & 1], tmin_lo);
-              const float tf = slab_min(slab_min3(fx[k >> 1][k & 1], fy[k >> 1][k & 1], fz[k >> 1][k & 1]), ustar_f);
-              hk[k] = tn <= tf;
-            }
-            asm volatile("" ::"v"(ch.x), "v"(ch.y), "v"(ch.z), "v"(ch.w));
-            if (hk[0] || hk[1] || hk[2] || hk[3]) {
-              node = hk[3] ? ch.w : (hk[2] ? ch.z : (hk[1] ? ch.y : ch.x));
-              *top = ch.x;
-              top += (hk[0] && (hk[1] || hk[2] || hk[3])) ? kBlk : 0;
-              *top = ch.y;
-              top += (hk[1] && (hk[2] || hk[3])) ? kBlk : 0;
-              *top = ch.z;
-              top += (hk[2] && hk[3]) ? kBlk : 0;
-              if (top > stk_cap) {  // stack full: abandon, the linear scan decides
-                overflow = 1;
-                top = stk;
-                node = ykbvh::kEmptyLeaf;
-              }
-              continue;
-            }
-            if (top == stk) {  // as in the FP64 kernel
-              node = ykbvh::kEmptyLeaf;
-            } else {
-              top -= kBlk;
-              node = *top;
-            }
-            continue;
-          } else {
-            YK_STAMP(2);
-            const uint32_t v = ~(uint32_t)node, first = v >> 4, cnt = v & 15u;
-            // bound-then-evaluate, as in the FP64 kernel: the exact discriminant decides disc < 0,
-            // the root gets bounds only, and the survivors' exact roots are evaluated after the
-            // traversal, with the lanes converged
-            // (the FP32 tree has at most two spheres per leaf: the loop unrolled, without a loop
-            // counter or latch; FP32 512 spp: -2.7%)
-#pragma unroll
-            for (uint32_t k = 0; k < kLeafCapF32; ++k) {
-              if (k >= cnt) break;
-              const float4 sg = leaf_geo[first + k];
-              const uint32_t id = leaf_ids[first + k];
-              asm volatile("" ::"v"(id));
-              if (kCount) ++n_test;
-              const ykf::v3 oc = {o.x - sg.x, o.y - sg.y, o.z - sg.z};
-              const float hb = ykf::dot(oc, d);
-              const float c = ykf::len2(oc) - sg.w;
-              const float disc = hb * hb - a * c;
-              if (disc < 0) continue;
-              YK_STAMP_DISC_POS();
-              float lb, ub;
-              if (!f32_root_bounds(hb, disc, ia, tmin, lb, ub)) continue;
-              if (!(lb <= ustar)) continue;
-              if (ub < ustar) {
-                ustar = ub;
-                ustar_f = ub * (1.0f + 0x1p-18f);
-              }
-              if (nc == 4) {  // compact: drop entries the new bound has excluded
-                uint32_t m2 = 0;
-                uint32_t d0 = c0, d1 = c1, d2 = c2, d3 = c3;
-                float e0 = l0, e1 = l1, e2 = l2, e3 = l3;
-                if (e0 <= ustar) { YK_CAND_SET(m2, d0, e0); ++m2; }
-                if (e1 <= ustar) { YK_CAND_SET(m2, d1, e1); ++m2; }
-                if (e2 <= ustar) { YK_CAND_SET(m2, d2, e2); ++m2; }
-                if (e3 <= ustar) { YK_CAND_SET(m2, d3, e3); ++m2; }
-                nc = m2;
-              }
-              if (nc < 4) {
-                c3 = c2, l3 = l2, c2 = c1, l2 = l1, c1 = c0, l1 = l0;
-                c0 = id, l0 = lb;
-                ++nc;
-              } else {
-                nc = 5;  // the list is full: the ordered scan decides
-              }
-            }
-            YK_STAMP(6);
-          }
-          if (top == stk) break;
-          top -= kBlk;
-          node = *top;
-        }
-        YK_STAMP(2);
-        if (overflow != 0) linear = true;
-        if (nc > 4) linear = true;
-        if (!linear) {
-          // the survivors' exact roots: the minimum wins, an exact tie goes to the later tuple
-          // index (hittable_list.hpp:36-43); a candidate whose lower bound exceeds the final U*
-          // cannot be the minimum
-#define YK_F32_EVAL(C, L)                                                       \
-  if ((L) <= ustar) {                                                           \
-    float r = 0.0f;                                                             \
-    const int res = f32_root(geo_f[C], o, d, a, ra, a_ok, tmin, r, n_nit);      \
-    if (kCount && res > 0) ++n_sqrt, ++n_ncall;                                 \
-    if (res == 2 && (r < T || (r == T && (int)(C) > hid))) T = r, hid = (int)(C); \
-  }
-          const bool a_ok = ykf::div_range(a);
-          const float ra = ykf::rcp_refined(a);
-          if (nc > 0) YK_F32_EVAL(c0, l0)
-          if (nc > 1) YK_F32_EVAL(c1, l1)
-          if (nc > 2) YK_F32_EVAL(c2, l2)
-          if (nc > 3) YK_F32_EVAL(c3, l3)
-#undef YK_F32_EVAL
-        }
-      }
-      if (linear) {  // the reference's ordered scan in tuple order (wave-uniform scalar loads)
-        ++n_lin;
-        T = INFINITY;
-        hid = -1;
-        for (uint32_t i = 0; i < ka.nspheres; ++i) {
-          const float4 sg = ka.geo_f[i];
-          if (kCount) ++n_test;
-          const ykf::v3 oc = {o.x - sg.x, o.y - sg.y, o.z - sg.z};
-          const float hb = ykf::dot(oc, d);
-          const float c = ykf::len2(oc) - sg.w;
-          const float disc = hb * hb - a * c;
-          if (disc < 0) continue;
-          if (kCount) ++n_sqrt, ++n_ncall;
-          const float sq = ykf::nsqrt(disc, n_nit);
-          float root = (-hb - sq) / a;
-          if (root < tmin || T < root) {
-            root = (-hb + sq) / a;
-            if (root < tmin || T < root) continue;
-          }
-          T = root;
-          hid = (int)i;
-        }
-      }
-    }
-
-    YK_STAMP(3);
-    // ---- shade (raytracer.hpp:25-36, material.hpp), material-uniform as in the FP64 kernel: one
-    //      block of canonicals (float: one word each) for lambertian's vec3::random (3), the fuzzed
-    //      metal's factor and vector (4) and the dielectric's uniform (1, drawn speculatively and
-    //      given back on total internal reflection); one normalisation; one second square root
-    //      (the fuzzed metal's |vector|, the dielectric's sin(theta)).  Each lane's own operations
-    //      and their order are the reference's render<float>.
-    bool ended = in_path && !alive;
-    double L_r = 0, L_g = 0, L_b = 0;
-    if (alive) {
-      SphereMat m{};
-      ykf::v3 p{0, 0, 0}, nrm{0, 0, 0};
-      bool front = false;
-      if (hid >= 0) {
-        const float4 sg = geo_f[hid];
-        m = mat[hid];
-        p = ykf::add(o, ykf::mul(d, T));  // ray::at
-        const ykf::v3 outward = ykf::divs_fast_r(ykf::sub(p, ykf::v3{sg.x, sg.y, sg.z}), (float)m.radius, m.inv_rf);
-        front = ykf::dot(d, outward) < 0;
-        nrm = front ? outward : ykf::neg(outward);
-      }
-      const bool lamb = hid >= 0 && m.kind == YK_MATERIAL_LAMBERTIAN;
-      const bool fuzzy = hid >= 0 && m.kind == YK_MATERIAL_METAL && m.fuzz > 0;
-      const bool diel = hid >= 0 && m.kind == YK_MATERIAL_DIELECTRIC;
-      const bool spec = diel && ykd::rng_can_speculate(g);
-      const Gen saved = g;  // the dielectric's engine before its speculative draw
-      const uint32_t ncan = lamb ? 3u : (fuzzy ? 4u : (spec ? 1u : 0u));
-      float c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-      if (__ballot(ncan > 0 && !ykd::rng_lazy_ok(g, ncan)) == 0) {
-        if (ncan > 0) c0 = ykf::canonical<true>(g);
-        if (ncan > 1) c1 = ykf::canonical<true>(g);
-        if (ncan > 2) c2 = ykf::canonical<true>(g);
-        if (ncan > 3) c3 = ykf::canonical<true>(g);
-      } else {
-        if (ncan > 0) c0 = ykf::canonical(g);
-        if (ncan > 1) c1 = ykf::canonical(g);
-        if (ncan > 2) c2 = ykf::canonical(g);
-        if (ncan > 3) c3 = ykf::canonical(g);
-      }
-      // lambertian: vec3::random(-1, 1), x then y then z; fuzzed metal: the length factor first
-      const ykf::v3 rv = lamb ? ykf::v3{ykf::uniform_of(c0, -1.0f, 1.0f), ykf::uniform_of(c1, -1.0f, 1.0f),
-                                        ykf::uniform_of(c2, -1.0f, 1.0f)}
-                              : ykf::v3{ykf::uniform_of(c1, -1.0f, 1.0f), ykf::uniform_of(c2, -1.0f, 1.0f),
-                                        ykf::uniform_of(c3, -1.0f, 1.0f)};
-      const ykf::v3 vn = lamb ? rv : d;
-      if (kCount) ++n_ncall;
-      const ykf::v3 un = ykf::divs_fast(vn, ykf::nsqrt(ykf::len2(vn), n_nit));
-      float ct = 0;  // dielectric: cos(theta) = min(dot(-unit, n), 1)
-      if (diel) {
-        ct = ykf::dot(ykf::neg(un), nrm);
-        if (!(ct < 1.0f)) ct = 1.0f;
-      }
-      float sq2 = 0;  // fuzzed metal: |random vector|; dielectric: sin(theta)
-      if (fuzzy || diel) sq2 = ykf::nsqrt(fuzzy ? ykf::len2(rv) : 1.0f - ct * ct, n_nit);
-      if (hid < 0) {
-        // sky: normalized(dir).y is a float; + 1.0 and the lerp are double (raytracer.hpp:35-36)
-        const double t = ((double)un.y + 1.0) / 2;
-        L_r = (1.0 - t) * 1.0 + t * 0.5;
-        L_g = (1.0 - t) * 1.0 + t * 0.7;
-        L_b = (1.0 - t) * 1.0 + t * 1.0;
-        ended = true;
-      } else {
-        bool scattered = true, push = true;
-        ykf::v3 nd;
-        if (m.kind == YK_MATERIAL_LAMBERTIAN) {
-          nd = ykf::add(nrm, un);
-          if (ykf::near_zero(nd)) nd = nrm;
-        } else if (m.kind == YK_MATERIAL_METAL) {
-          nd = ykf::reflect(un, nrm);
-          if (fuzzy) {
-            const float k = ykf::uniform_of(c0, 0.01f, 0.99f);
-            const ykf::v3 ru = ykf::divs_fast(rv, sq2);
-            nd = ykf::add(nd, ykf::mul(ykf::mul(ru, k), (float)m.fuzz));
-          }
-          scattered = ykf::dot(nd, nrm) > 0;
-        } else {  // dielectric extension, in float
-          push = false;
-          const float ior = (float)m.ior;
-          const float ratio = front ? (1.0f / ior) : ior;
-          const bool cannot = ratio * sq2 > 1.0f;
-          float u = 0;
-          if (cannot) {
-            if (spec) g = saved;  // `cannot || ...` never draws: give the word back
-          } else {
-            u = spec ? c0 : ykf::canonical(g);
-          }
-          if (cannot || ykf::reflectance(ct, ratio) > u) {
-            nd = ykf::reflect(un, nrm);
-          } else {
-            const ykf::v3 perp = ykf::mul(ykf::add(un, ykf::mul(nrm, ct)), ratio);
-            const float pl = 1.0f - ykf::len2(perp);
-            nd = ykf::add(perp, ykf::mul(nrm, -ykf::nsqrt(pl < 0 ? -pl : pl, n_nit)));
-          }
-        }
-        if (!scattered) {
-          ended = true;
-        } else {
-          if (push) {
-            if (nstk >= kStackRegs) id_spill[nstk - kStackRegs] = (uint16_t)(st3 >> 16);
-            st3 = (st3 << 16) | (st2 >> 16);
-            st2 = (st2 << 16) | (st1 >> 16);
-            st1 = (st1 << 16) | (st0 >> 16);
-            st0 = (st0 << 16) | (uint32_t)hid;
-            ++nstk;
-          }
-          o = p;
-          d = nd;
-          --depth;
-        }
-      }
-    }
-
-    YK_STAMP(4);
-    if (ended) {
-      // attenuation (double albedo) back to front, as in FP64 (raytracer.hpp:31)
-      while (nstk > 0) {
-        const uint32_t id = st0 & 0xffffu;
-        st0 = (st0 >> 16) | (st1 << 16);
-        st1 = (st1 >> 16) | (st2 << 16);
-        st2 = (st2 >> 16) | (st3 << 16);
-        st3 = (st3 >> 16) | (nstk > kStackRegs ? ((uint32_t)id_spill[nstk - kStackRegs - 1] << 16) : 0u);
-        --nstk;
-        const SphereMat m = mat[id];
-        L_r = m.ar * L_r;
-        L_g = m.ag * L_g;
-        L_b = m.ab * L_b;
-      }
-      if (ykd::mt_used_fallback(g)) ++n_fb;
-      if (kCount) n_words += ykd::rng_words(g), n_twist += ykd::rng_twists(g);
-      colour_store(ka.col, slot, L_r, L_g, L_b);
-      in_path = false;
-    }
-    YK_STAMP(5);
-  }
-  YK_CLOCK_END(ka);
-  YK_STAMPS_END(ka.counters, lane);
-  if (kCount) {
-    atomicAdd(&ka.counters[0], (unsigned long long)n_seg);
-    atomicAdd(&ka.counters[1], (unsigned long long)n_test);
-    atomicAdd(&ka.counters[2], (unsigned long long)n_sqrt);
-    atomicAdd(&ka.counters[4], (unsigned long long)n_node);
-    atomicAdd(&ka.counters[5], (unsigned long long)n_lin);
-    atomicAdd(&ka.counters[6], (unsigned long long)n_ncall);
-    atomicAdd(&ka.counters[7], (unsigned long long)n_nit);
-    atomicAdd(&ka.counters[29], (unsigned long long)n_words);
-    atomicAdd(&ka.counters[30], (unsigned long long)n_swords);
-    atomicAdd(&ka.counters[31], (unsigned long long)n_twist);
-  }
-  if (n_fb) atomicAdd(&ka.counters[3], (unsigned long long)n_fb);
-}
-
-// The FP32 instance for (scene in LDS, kMode)
-RenderKernel f32_kernel(bool lds, int mode) {
-  static const RenderKernel k[8] = {yk_render_f32<false, 0>, yk_render_f32<false, 1>, yk_render_f32<false, 4>,
-                                    yk_render_f32<false, 5>, yk_render_f32<true, 0>,  yk_render_f32<true, 1>,
-                                    yk_render_f32<true, 4>,  yk_render_f32<true, 5>};
-  return k[(lds ? 4 : 0) + ((mode & 1) | ((mode & 4) >> 1))];
-}
-
-#endif  // YK_SPLIT != 1
-
 // ykgpu_math_sqrt_f32: the FP32 path's math::sqrt<float> on a buffer (diagnostic).
 __global__ __launch_bounds__(256) void yk_math_sqrt_f32(const float* in, float* out, uint64_t n) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2402,127 +675,20 @@ __global__ __launch_bounds__(256) void yk_math_sqrt_f32(const float* in, float* 
 
 }  // namespace
 
-#if YK_SPLIT == 2
-// the FP32 unit's instances, for the main unit's f32_kernel()
-extern "C" const void* yk_split_f32_kernel(bool lds, int mode) { return (const void*)f32_kernel(lds, mode); }
-#else
-#if YK_SPLIT == 1
-extern "C" const void* yk_split_f32_kernel(bool lds, int mode);  // ykgpu_render_f32.o
+// the render units' instances (yk_render_f64.hip, yk_render_f32.hip), by (scene in LDS, kMode)
 namespace {
-RenderKernel f32_kernel(bool lds, int mode) { return (RenderKernel)yk_split_f32_kernel(lds, mode); }
+RenderKernel fp64_kernel(bool lds, int mode) { return (RenderKernel)yk_fp64_kernel(lds, mode); }
+RenderKernel f32_kernel(bool lds, int mode) { return (RenderKernel)yk_f32_kernel(lds, mode); }
 }  // namespace
-#endif
 
 // =========================================================================================
 // C-ABI
 // =========================================================================================
-// ---- Host-side tuning constants (each overridable with -DYK_...; the kernels' are at the top of
-// the file) ----
-#ifndef YK_LAUNCH_MB
-#define YK_LAUNCH_MB 8192
-#endif
-// colour records of one launch at most: bounds a launch's slots for very large tiles (kmax in
-// launch())
-constexpr uint64_t kLaunchBytes = (uint64_t)YK_LAUNCH_MB << 20;
+// (the host-side tuning constants and the launch schedule rule: yk_schedule.hpp)
 // the render kernel addresses a slot's start record as 4 * slot uint4s (FP32: 3) in 32-bit
 // arithmetic
 static_assert(kLaunchBytes / (8 * kColStride) * 4 < (1ull << 32), "4 * slot must fit 32 bits");
-// samples per pixel per launch at most: many mid-sized launches beat a few big ones, because the
-// launches alternate between two streams and each one's drain overlaps the next one's start
-// (round 1, 1920x1080x512 259.5 -> 254.0 ms at 64 spp/launch; with the render
-// streams at top priority, bench 205.5 ms at 64, 199.6 at 32, 199.8 at 24, 206.3 at 16)
-#ifndef YK_LAUNCH_SPP
-#define YK_LAUNCH_SPP 32
-#endif
-constexpr uint32_t kLaunchSpp = YK_LAUNCH_SPP;
-// ... and for a call enqueued while the previous one still runs (launch() `inflight`): its launches
-// need no ramp and overlap the calls around them, so the per-launch handover is what is left, and
-// half as many launches pay it (frame: 8 of 64 instead of 16 of 32: bench -1.7%); a synced call
-// keeps kLaunchSpp (64 there cost it 2%: the 64-spp warm-up under the ramp's 32-spp render and a
-// longer last launch alone on the device, profiles/r06_ab/shade/).  The rings hold the larger
-// launch in both, so a synced call and the in-flight calls after it share one ring geometry.
-#ifndef YK_LAUNCH_SPP_OV
-#define YK_LAUNCH_SPP_OV 64
-#endif
-constexpr uint32_t kLaunchSppOv = YK_LAUNCH_SPP_OV;
-// ... or spp / kLaunchesPerCall when that is more (a long call: launch())
-#ifndef YK_LAUNCHES_PER_CALL
-#define YK_LAUNCHES_PER_CALL 32
-#endif
-constexpr uint32_t kLaunchesPerCall = YK_LAUNCHES_PER_CALL;
-// ... and launches of about kLaunchSlots sample slots when the tile is small: a launch has a fixed
-// cost (the handover of every CU from its render workgroup to the next launch's, filled by seed
-// walks: ~0.2 ms per launch), so a call is split into round(slots / kLaunchSlots)
-// launches — the frame's 32-spp launches are 66M slots, and a tile's launches are as large (the
-// 8-way tile of 1920x1080x512: 2 launches of 256 spp; with 2^25-slot launches, 4 of 128, its
-// back-to-back calls cost 2% more per sample than the frame's, profiles/r06_ab/tiles/)
-#ifndef YK_LAUNCH_SLOTS
-#define YK_LAUNCH_SLOTS (1u << 26)
-#endif
-constexpr uint64_t kLaunchSlots = YK_LAUNCH_SLOTS;
-// ... and of about kLaunchSlotsOv for an in-flight call (as kLaunchSppOv for the frame), never
-// fewer than two launches where a synced call has two: the 4-way tile 38.73 -> 38.59 ms, the 2-way
-// 76.73 -> 76.18, config 4's 8-way 153.78 -> 153.10, the 8-way unchanged (profiles/r06_ab/tiles/r06ae_*)
-#ifndef YK_LAUNCH_SLOTS_OV
-#define YK_LAUNCH_SLOTS_OV (1u << 27)
-#endif
-constexpr uint64_t kLaunchSlotsOv = YK_LAUNCH_SLOTS_OV;
-// global launch numbers whose dependency events (ykgpu_context::gev) are kept: more than any ring
-// is deep
-constexpr uint32_t kDepRing = 16;
-// Under memory pressure (launch()): launches shrink down to this many sample slots before a call
-// fails with YK_ERR_NOMEM, and the rings leave kMemReserve of the device free
-constexpr uint64_t kMemFloorSlots = 1ull << 24;
-constexpr size_t kMemReserve = (size_t)512 << 20;
-// Start-record ring: the warm-ups run on ctx->aux, beside the render launches (their wave slots
-// and VGPRs fit next to the render kernel's, and the render leaves most VALU issue slots idle),
-// into a ring of min(launches, kWarmRingDepth) launch buffers (YKGPU_WARM_RING overrides); warm-up
-// c waits for the render of launch c - ring.  Sized to the call: ring x slots x record (1920x1080
-// at 32 spp per launch: 66M slots x 64 B = 4.2 GB per launch buffer).
-#ifndef YK_WARM_RING
-#define YK_WARM_RING 3
-#endif
-constexpr uint32_t kWarmRingDepth = YK_WARM_RING;
-#ifndef YK_FIRST_LAUNCH
-#define YK_FIRST_LAUNCH 4
-#endif
-constexpr uint32_t kFirstLaunch = YK_FIRST_LAUNCH;  // samples per pixel in the first launch
-// ... and each next launch grows by this factor until kmax: 4, 8, 16, 32, 32, ... (1920x1080x512:
-// 4 + 8 + 16 + 14 x 32 + 18 + 18 = 512 spp in 19 launches).  Before round 4: 8, 32, 32, ...; its second
-// warm-up (32 spp of walks beside the first render) sometimes finished late and delayed every
-// launch after it: 20 synced calls on one box spread 173.6-177.4 ms (max/min 1.022), against
-// 173.6-174.6 (1.0059) with 4, 8, 16 (tools/variance_ab.py, profiles/r04_ab/variance/)
-#ifndef YK_SCHED_GROW
-#define YK_SCHED_GROW 2
-#endif
-constexpr uint32_t kSchedGrow = YK_SCHED_GROW;
-// ... and for a call enqueued while the previous one still runs (launch(): `inflight`): every
-// launch at kmax (YK_FIRST_LAUNCH_OV 0; else that many samples per pixel first, growing by
-// YK_SCHED_GROW_OV)
-#ifndef YK_FIRST_LAUNCH_OV
-#define YK_FIRST_LAUNCH_OV 0
-#endif
-#ifndef YK_SCHED_GROW_OV
-#define YK_SCHED_GROW_OV 4
-#endif
-constexpr uint32_t kFirstLaunchOv = YK_FIRST_LAUNCH_OV, kSchedGrowOv = YK_SCHED_GROW_OV;
-static_assert(YK_FIRST_LAUNCH >= 1 && YK_LAUNCH_SPP >= 1, "launch sizes must be >= 1 sample per pixel");
-#ifndef YK_TILE
-#define YK_TILE 8
-#endif
-constexpr uint32_t kTile = YK_TILE;  // processing blocks of kTile x kTile pixels (0: row-major)
-// colour buffers in flight (col_ring())
-#ifndef YK_COL_RING
-#define YK_COL_RING 2
-#endif
-// FP64 warm-up grid: blocks per CU (warm_per_cu(); each thread walks n / grid slots, at least kWarmSlots)
-#ifndef YK_WARM_PER_CU
-#define YK_WARM_PER_CU 32
-#endif
-#ifndef YK_WARM_SLOTS
-#define YK_WARM_SLOTS 4
-#endif
-constexpr uint32_t kWarmSlots = YK_WARM_SLOTS;
+static_assert(yksched::kColourBytes == kColStride * sizeof(double), "yk_schedule.hpp's colour record");
 
 // A BVH on the device: the FP64 kernel's (boxes grown for the exact test's rounding, DESIGN.md
 // §4) or the FP32 kernel's (grown for render<float>'s sphere test, §4.1), with its LDS layout
@@ -2678,17 +844,6 @@ struct ykgpu_group {
 };
 
 namespace {
-
-// A/B knobs: environment overrides of the launch schedule, rings, grids and tree build that the
-// A/B tools time (tools/abtime.py `lib@YKGPU_X=v`).  They exist only in variant builds
-// (tools/build_def_variant.sh <name> -DYK_AB_KNOBS): in the product library ab_knob() is a
-// constant nullptr, so nothing in a caller's environment changes the schedule or the tree.  The
-// documented diagnostics YKGPU_TIMELINE and YKGPU_OVERLAP stay.
-#ifdef YK_AB_KNOBS
-const char* ab_knob(const char* name) { return std::getenv(name); }
-#else
-constexpr const char* ab_knob(const char*) { return nullptr; }
-#endif
 
 uint64_t host_row_y(const yk_render_params* p, uint32_t t) {
   const uint32_t L = p->row_band_log2;
@@ -2891,17 +1046,48 @@ inline uint32_t warm_blocks_for(uint64_t n, uint64_t cap, uint32_t ilp) {
 // chunk (ykgpu_film_accumulate) passes its window and the film: the same schedule rule applied to
 // the window's length, the same rings and streams, each launch folded into the film's own planes
 // by yk_film_reduce (carry-in and carry-out), in the film's own processing order.
-int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, double* sums_dev,
-           hipStream_t st, uint32_t s_begin, uint32_t s_end, ykgpu_film* film) {
-  const bool f32 = p->precision == YK_PRECISION_FP32;
-  const bool x128 = p->rng == YK_RNG_XOR128;  // no warm-ups, no MT scratch
-  const DevTree& tree = f32 ? ctx->t32 : ctx->t64;
-  const DevTree::Plan& plan = tree.plan[x128 ? 1 : 0];
-  const int grid = plan.grid, block = block_of(x128);
+//
+// launch() is four steps: plan_launch (the schedule, the ring depths, the lens-retry ring, the
+// buffers grown), fill_args (the kernels' argument records), enqueue_launches (the event graph and
+// the warm-up / render / reduce loop) and call_stats.
+
+// What a call's first step settles and the others read
+struct LaunchPlan {
+  bool f32, x128;  // x128: no warm-ups, no MT scratch
+  bool group;      // a group of an adaptive pass: the film's compacted order of the pixels that take this window
+  const DevTree* tree;
+  const DevTree::Plan* plan;
+  int grid, block;
+  uint64_t seed_key;
+  const uint32_t* order;
+  uint32_t nps;  // processing slots (>= pixels)
+  uint32_t spp;  // samples per pixel of this call (p->samples_per_pixel stays the stride of the seeds)
+  std::vector<std::pair<uint32_t, uint32_t>> sched;  // (s0, samples)
+  uint64_t shape;
+  bool warm_first;
+  uint32_t K, nlaunch, kWarmRing, kColRing, mem_shrinks;
+  size_t welem;  // start records (StartRec, FP32 StartRecF: each sample's whole start)
+  uint32_t retry_cap;  // records per wave
+  size_t retry_n;
+};
+
+// slots per warm-up wave of an FP64 launch of nl slots
+uint64_t warm_wave_slots(const ykgpu_context* ctx, uint64_t nl) {
+  const uint64_t wb = warm_blocks_for(nl, (uint64_t)ctx->cus * warm_per_cu(false), kWalkIlp);
+  return (nl + wb * 256 - 1) / (wb * 256) * 64;
+}
+
+int plan_launch(ykgpu_context* ctx, const yk_render_params* p, uint32_t s_begin, uint32_t s_end,
+                       ykgpu_film* film, LaunchPlan& lp) {
+  const bool f32 = lp.f32 = p->precision == YK_PRECISION_FP32;
+  const bool x128 = lp.x128 = p->rng == YK_RNG_XOR128;  // no warm-ups, no MT scratch
+  const DevTree& tree = *(lp.tree = f32 ? &ctx->t32 : &ctx->t64);
+  const DevTree::Plan& plan = *(lp.plan = &tree.plan[x128 ? 1 : 0]);
+  const int grid = lp.grid = plan.grid, block = lp.block = block_of(x128);
   int rc = ensure_scratch(ctx, p->max_depth, (size_t)grid * block, !x128);
   if (rc) return rc;
   // YK_SEED_RANDOM_DEVICE without a key: one from std::random_device per call (source.cpp:159)
-  uint64_t seed_key = 0;
+  uint64_t& seed_key = lp.seed_key = 0;
   if (p->seed_mode == YK_SEED_RANDOM_DEVICE) {
     seed_key = p->seed_key;
     if (!seed_key) {
@@ -2912,62 +1098,28 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
   // (a film brings its own order, and leaves the context's alone)
   if (!film && (rc = ensure_order(ctx, tile_width(p), p->row_count, order_stride(p)))) return rc;
   // (a group of an adaptive pass: the film's compacted order of the pixels that take this window)
-  const bool group = film && film->g_slots != 0;
-  const uint32_t* const order = group ? film->d_gorder : film ? film->d_order : ctx->d_order;
-  // Launch schedule (samples per pixel per launch): kFirstLaunch (4), growing by kSchedGrow (2)
-  // up to kmax (kLaunchSpp = 32, or more for a small tile), also capped by the colour budget (32 B
-  // per sample slot, kLaunchBytes per launch); a short remainder is folded into the launches before
-  // it (1920x1080x512: 4, 8, 16, 14 x 32, 18, 18 = 19 launches).  The first render waits only for
-  // a 4-sample warm-up, and each next warm-up, twice the one before, finishes under the render
-  // before it (see kSchedGrow).  Each launch ends with the tail of its longest paths (~0.1-0.2 ms
-  // of partly idle CUs), but launches alternate between two streams, so that drain overlaps the
-  // next launch: many
-  // mid-sized launches beat a few large ones.  Independent of the image size, which matters
+  const bool group = lp.group = film && film->g_slots != 0;
+  lp.order = group ? film->d_gorder : film ? film->d_order : ctx->d_order;
+  // Launch schedule (samples per pixel per launch; the rule is yk_schedule.hpp's): a ramp up to
+  // kmax (kLaunchSpp = 32, or more for a small tile), also capped by the colour budget (32 B per
+  // sample slot, kLaunchBytes per launch); a short remainder is folded into the launches before
+  // it.  Each launch ends with the tail of its longest paths (~0.1-0.2 ms of partly idle CUs), but
+  // launches alternate between two streams, so that drain overlaps the next launch: many mid-sized
+  // launches beat a few large ones.  Independent of the image size, which matters
   // for the per-rank tiles of N GPUs.
-  const uint32_t nps = group ? film->g_slots : film ? film->nps : ctx->order_slots;  // processing slots (>= pixels)
+  const uint32_t nps = lp.nps = group ? film->g_slots : film ? film->nps : ctx->order_slots;  // processing slots (>= pixels)
   // samples per pixel of this call (p->samples_per_pixel stays the stride of the seeds)
-  const uint32_t spp = s_end - s_begin;
-  // (slots of a launch stay below 2^31: the kernels' fdiv takes 31-bit numerators)
-  // A launch of few pixels still gets enough slots to fill the persistent grid (16 per lane):
-  // a thin row tile at high spp would otherwise run dozens of launches that each pay a ramp and
-  // a drain.  Neither floor nor cap exceeds the colour budget or 2^31 slots.
-  const uint64_t fill_spp = ((uint64_t)grid * block * 16 + nps - 1) / nps;
-  uint64_t launch_slots = kLaunchSlots;  // (A/B knob: YKGPU_LAUNCH_SLOTS)
-  if (const char* e = ab_knob("YKGPU_LAUNCH_SLOTS")) launch_slots = (uint64_t)std::max(1ll, std::atoll(e));
-  auto launches_for = [&](uint64_t lslots) {
-    return std::max<uint64_t>(1, ((uint64_t)nps * spp + lslots / 2) / lslots);
-  };
-  // (in flight: never fewer than two launches where a synced call has two — a one-launch call has
-  // rings of one buffer and overlaps nothing: the 8-way tile 19.6 -> 25.5 ms, r06ad; one launch
-  // with the rings' full depth kept instead: +1.5%, profiles/r06_ab/tiles/r06al_*)
-  const uint64_t call_launches = launches_for(launch_slots);
-  const uint64_t call_launches_ov =
-      std::max(std::min<uint64_t>(call_launches, 2), launches_for(std::max(launch_slots, kLaunchSlotsOv)));
-  const uint64_t slot_spp = (spp + call_launches - 1) / call_launches;
-  const uint64_t slot_spp_ov = (spp + call_launches_ov - 1) / call_launches_ov;
-  // A long call takes longer launches: every launch pays a drain whose length is the longest path
-  // of its last samples, and many launches per call buy nothing once there are ~32 (config 5,
-  // 1920x1080x4096 at depth 200 on the glass scene: 32 spp per launch 1730 ms, 64 1631, 121 (the
-  // colour budget) 1589, with a warm ring of 2 1610; config 3's 512 spp stay at 32, where 64
-  // costs 5%; profiles/r04_ab/launch_size/).  The rings grow with the launch: config 5 holds
-  // ~64 GB (3 x 2.07M x 121 x 64 B of start records, 2 x 2.07M x 121 x 32 B of colours).
-  uint64_t launch_spp = std::max<uint64_t>(kLaunchSpp, spp / kLaunchesPerCall);
-  if (const char* e = ab_knob("YKGPU_LAUNCH_SPP")) launch_spp = (uint64_t)std::max(1, std::atoi(e));  // (A/B)
-  const uint64_t launch_spp_ov = std::max<uint64_t>(std::max<uint64_t>(kLaunchSppOv, launch_spp), spp / kLaunchesPerCall);
-  auto ideal_for = [&](uint64_t lspp, uint64_t sspp) {
-    return (uint32_t)std::max<uint64_t>(
-        1, std::min<uint64_t>({spp, kLaunchBytes / (8ull * kColStride * nps),
-                               std::max<uint64_t>({lspp, fill_spp, sspp}), ((1ull << 31) - 1) / nps}));
-  };
+  const uint32_t spp = lp.spp = s_end - s_begin;
   // the rings' launch size (an in-flight call's launches) and a synced call's, <= it
-  const uint32_t kideal = ideal_for(launch_spp_ov, slot_spp_ov), ksynced = ideal_for(launch_spp, slot_spp);
+  const yksched::LaunchSizes sizes = yksched::launch_sizes(nps, spp, (uint64_t)grid * block);
+  const uint32_t kideal = sizes.kideal, ksynced = sizes.ksynced, kfloor = sizes.kfloor;
   // A device short of memory (other contexts, other processes) makes the call slower, not fatal:
   // the rings are sized for launches of kmax samples per pixel, and when the device cannot hold
   // them — free memory (hipMemGetInfo) plus what this context's rings already hold, or a
   // hipMalloc that fails anyway — kmax halves, down to launches of kMemFloorSlots sample slots,
   // before the call fails with YK_ERR_NOMEM (yk_render_stats.launch_spp / mem_shrinks report it).
-  const uint32_t kfloor = (uint32_t)std::min<uint64_t>(kideal, std::max<uint64_t>(1, (kMemFloorSlots + nps - 1) / nps));
-  uint32_t kmax = kideal, mem_shrinks = 0;
+  uint32_t kmax = kideal;
+  uint32_t& mem_shrinks = lp.mem_shrinks = 0;
   auto shrink = [&]() {
     kmax = std::max(kfloor, kmax / 2);
     ++mem_shrinks;
@@ -2986,59 +1138,24 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
     cap = need;
     return YK_OK;
   };
-  std::vector<std::pair<uint32_t, uint32_t>> sched;  // (s0, samples)
-  uint64_t shape = 0;
+  std::vector<std::pair<uint32_t, uint32_t>>& sched = lp.sched;  // (s0, samples)
+  uint64_t& shape = lp.shape = 0;
   bool inflight = false;
-  uint32_t K = 0, nlaunch = 0, kWarmRing = 0, kColRing = 0;
+  uint32_t &K = lp.K = 0, &nlaunch = lp.nlaunch = 0, &kWarmRing = lp.kWarmRing = 0, &kColRing = lp.kColRing = 0;
   // start records (StartRec, FP32 StartRecF: each sample's whole start)
-  const size_t welem = f32 ? sizeof(StartRecF) : sizeof(StartRec);
+  const size_t welem = lp.welem = f32 ? sizeof(StartRecF) : sizeof(StartRec);
   // (diagnostic, timing only) YKGPU_ABL_WARM_FIRST=1: every launch's warm-up runs, and finishes,
   // before the first render: render_busy_ms then times the render kernels without the seed walks
   // beside them (same images)
-  const bool warm_first = ab_knob("YKGPU_ABL_WARM_FIRST") != nullptr && !x128;
+  const bool warm_first = lp.warm_first = ab_knob("YKGPU_ABL_WARM_FIRST") != nullptr && !x128;
   for (;;) {
-    // A call enqueued while the previous one still runs (back-to-back steps) starts its first
-    // warm-ups under the previous call's last launches, so it needs no small first launch: every
-    // launch at kmax — the frame is 16 launches of 32 (bench 8 steps: 172.4 ms per step with 4, 8,
-    // 16, 32; 170.8 with 8, 32; 168.4 with 32, 32, ...; profiles/r04_ab/schedule/), the 8-way tile
-    // of config 3 four of ~130 (23.1 ms per call starting at 32, 21.8 at 128; the 4-way tile 44.3
-    // -> 43.0 ms starting at 64; profiles/r04_ab/tiles/)
-    // (A/B knobs: YKGPU_FIRST_LAUNCH, YKGPU_SCHED_GROW and their _OV forms — the first launch's
-    // samples per pixel and the factor each next launch grows by until kmax)
     // (only for a call of the previous one's shape, whose rings it can overlap: launch() `ov`)
     shape = ((uint64_t)nps << 24) ^ ((uint64_t)kmax << 2) ^ (f32 ? 2u : 0u) ^ (x128 ? 1u : 0u);
     inflight = false;
     if (ctx->prev_enqueued && ctx->prev_ok && !ctx->dirty && ctx->prev_shape == shape && ctx->prev_n > 0 &&
         ctx->lev.size() >= 6ull * ctx->prev_n)
       inflight = hipEventQuery(ctx->lev[6 * (ctx->prev_n - 1) + 5]) == hipErrorNotReady;
-    // this call's largest launch: the rings' (kmax) in flight, a synced call's own below it
-    const uint32_t kcap = inflight ? kmax : std::min(kmax, ksynced);
-    uint32_t first_k = inflight ? (kFirstLaunchOv ? kFirstLaunchOv : kmax) : kFirstLaunch;
-    uint32_t grow_k = inflight ? kSchedGrowOv : kSchedGrow;
-    if (const char* e = ab_knob(inflight ? "YKGPU_FIRST_LAUNCH_OV" : "YKGPU_FIRST_LAUNCH"))
-      first_k = (uint32_t)std::max(1, std::atoi(e));
-    if (const char* e = ab_knob(inflight ? "YKGPU_SCHED_GROW_OV" : "YKGPU_SCHED_GROW"))
-      grow_k = (uint32_t)std::max(2, std::atoi(e));
-    sched.clear();
-    // the ramp (first_k, growing by grow_k), then launches of kmax; a short tail launch, which would
-    // pay its own drain, is folded into the launch before it, or that launch and the tail are split
-    // into two equal launches when one would exceed kmax — so no launch exceeds kmax, and every call
-    // of the same kmax places its launches in the rings alike (a back-to-back call overlaps the
-    // call before it, synced or not).  Launches of exactly kmax also keep the warm-up's walks
-    // aligned: at 32 spp its grid-stride is the pixel count, so a lane's four walks are four
-    // samples of one pixel (their processing-order reads coincide; a 30- or 31-spp launch fetches
-    // 1.7x the bytes per slot in the warm-up, profiles/r06_ab/pmc/)
-    for (uint32_t s0 = 0, k = std::min(first_k, kcap); s0 < spp;) {
-      uint32_t take = std::min(k, spp - s0);
-      const uint32_t rest = spp - (s0 + take);
-      if (rest > 0 && rest < std::max(1u, take / 4))
-        take = spp - s0 <= kcap ? spp - s0 : (spp - s0 + 1) / 2;
-      sched.emplace_back(s_begin + s0, take);
-      s0 += take;
-      // (a ramp growing by half past 32 or 16 spp did not recover the synced call of 64-spp
-      // launches: profiles/r06_ab/shade/r06z_*, r06aa_*)
-      k = std::min(grow_k * k, kcap);
-    }
+    yksched::launch_schedule(sched, spp, s_begin, kmax, ksynced, inflight);
     // a launch buffer of the rings holds kmax samples per pixel (every launch fits: above)
     K = kmax;
     nlaunch = (uint32_t)sched.size();
@@ -3079,18 +1196,14 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
   // The FP64 lens warm-ups of launches with at most kDeferSlots slots per warm-up wave draw their
   // lens retries after the walks (yk_mt_warmup_defer) from a ring per wave, sized to the largest
   // such launch (the frame's 32-spp launches: 640 records, 1.0 GB); longer launches run the
-  // rejection loop in line (config 5's 121-spp launches: 7600 slots per wave, where the deferral
-  // measured 0.7% slower)
+  // rejection loop in line (config 5's 128-spp launches: 8100 slots per wave; at 121 spp, 7600 per
+  // wave, the deferral measured 0.7% slower)
   const bool lens_defer = !x128 && !f32 && ctx->cam.lens_radius > 0;
-  auto wave_slots = [&](uint64_t nl) {
-    const uint64_t wb = warm_blocks_for(nl, (uint64_t)ctx->cus * warm_per_cu(false), kWalkIlp);
-    return (nl + wb * 256 - 1) / (wb * 256) * 64;
-  };
-  uint32_t retry_cap = 0;  // records per wave
+  uint32_t& retry_cap = lp.retry_cap = 0;  // records per wave
   if (lens_defer)
     for (const auto& l : sched)
-      if (wave_slots((uint64_t)nps * l.second) <= kDeferSlots)
-        retry_cap = std::max(retry_cap, retry_cap_for(wave_slots((uint64_t)nps * l.second)));
+      if (warm_wave_slots(ctx, (uint64_t)nps * l.second) <= kDeferSlots)
+        retry_cap = std::max(retry_cap, retry_cap_for(warm_wave_slots(ctx, (uint64_t)nps * l.second)));
   // a call whose launches were shrunk for want of memory runs the rejection loop in line: the
   // shrink loop above budgets the start-record and colour rings only, so the plan it settled on
   // is the plan the call runs (no ring allocated afterwards out of the reserve it kept)
@@ -3101,7 +1214,7 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
   // starts it makes itself), 0 is the in-line loop a failed ring allocation falls back to
   if (retry_cap) retry_cap = YK_RETRY_CAP_FORCE;
 #endif
-  size_t retry_n = (size_t)ctx->cus * warm_per_cu(false) * 4u * retry_cap * 3u;
+  size_t& retry_n = lp.retry_n = (size_t)ctx->cus * warm_per_cu(false) * 4u * retry_cap * 3u;
   if (retry_cap && (rc = grow(ctx->d_retry, ctx->retry_cap, retry_n, sizeof(uint4)))) {
     if (rc != YK_ERR_NOMEM) return rc;
     // a device short of memory runs the rejection loop in line instead (slower, never fatal)
@@ -3109,7 +1222,29 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
     retry_cap = 0;
     retry_n = 0;
   }
+  return YK_OK;
+}
+
+// The argument records of a call's kernels: everything but what changes from launch to launch
+// (enqueue_launches sets that)
+struct LaunchArgs {
   KernelArgs ka;
+  WarmArgs wa;
+  ReduceArgs ra;
+  FilmReduceArgs fa;
+  FilmMaskedArgs fm;
+};
+
+int fill_args(const ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, double* sums_dev,
+                     const ykgpu_film* film, const LaunchPlan& lp, LaunchArgs& la) {
+  const DevTree& tree = *lp.tree;
+  const DevTree::Plan& plan = *lp.plan;
+  const int grid = lp.grid, block = lp.block;
+  const uint32_t nps = lp.nps, retry_cap = lp.retry_cap;
+  const uint32_t* const order = lp.order;
+  const uint64_t seed_key = lp.seed_key;
+  const bool group = lp.group;
+  KernelArgs& ka = la.ka;
   ka.cam = ctx->cam;
   ka.pad_a = 0;
   {
@@ -3176,7 +1311,7 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
   ka.claim_tail = (uint32_t)grid * (uint32_t)(block / 64) * kClaim * kClaimTailFactor;
   if ((ka.flags & YK_FLAG_TRACE_RAYS) && !(ctx->d_trace && (ka.flags & YK_FLAG_COUNT_WORK)))
     return fail(YK_ERR_INVALID, "YK_FLAG_TRACE_RAYS is set by ykgpu_render_trace only");
-  WarmArgs wa;
+  WarmArgs& wa = la.wa;
   wa.W = p->image_width;
   wa.Wt = ka.Wt;
   wa.col_begin = ka.col_begin;
@@ -3211,7 +1346,7 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
   ka.w_m = wa.w_m;
   ka.w_sh = wa.w_sh;
   ka.stack_check = plan.stack_check ? 1u : 0u;
-  ReduceArgs ra;
+  ReduceArgs& ra = la.ra;
   ra.acc = ctx->d_acc;
   ra.order = order;
   ra.rgb = rgb_dev;
@@ -3219,8 +1354,8 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
   ra.npix_slots = nps;
   ra.spp = p->samples_per_pixel;
   ra.pad0 = ra.pad1 = 0;
-  FilmReduceArgs fa{};
-  FilmMaskedArgs fm{};
+  FilmReduceArgs& fa = la.fa = FilmReduceArgs{};
+  FilmMaskedArgs& fm = la.fm = FilmMaskedArgs{};
   if (group) {
     fm.plane = film->d_plane;
     fm.count = film->d_count;
@@ -3232,6 +1367,24 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
     fa.order = order;
     fa.npix_slots = nps;
   }
+  return YK_OK;
+}
+
+// Enqueues the call's launches; *launches_out receives how many.
+int enqueue_launches(ykgpu_context* ctx, hipStream_t st, uint32_t s_end, const ykgpu_film* film,
+                            const LaunchPlan& lp, LaunchArgs& la, uint32_t* launches_out) {
+  const bool f32 = lp.f32, x128 = lp.x128, group = lp.group, warm_first = lp.warm_first;
+  const DevTree::Plan& plan = *lp.plan;
+  const int grid = lp.grid, block = lp.block;
+  const uint32_t nps = lp.nps, K = lp.K, nlaunch = lp.nlaunch, kWarmRing = lp.kWarmRing, kColRing = lp.kColRing;
+  const size_t welem = lp.welem;
+  const std::vector<std::pair<uint32_t, uint32_t>>& sched = lp.sched;
+  KernelArgs& ka = la.ka;
+  WarmArgs& wa = la.wa;
+  ReduceArgs& ra = la.ra;
+  FilmReduceArgs& fa = la.fa;
+  FilmMaskedArgs& fm = la.fm;
+  int rc = YK_OK;
   // Cross-call pipelining: the launches are numbered across calls (ctx->g_next) and a launch's
   // ring slots (start records, colours, slot counter), scratch parity and render stream follow its
   // global number, so a call whose rings have the previous call's geometry needs no barrier
@@ -3333,7 +1486,7 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
     wa.n = (uint64_t)nps * sched[c].second;
     wa.out = ctx->d_warm + (size_t)((g0 + c) % kWarmRing) * nps * K * welem;
     wa.counter = ctx->d_counter + (g0 + c) % kWarmRing;
-    const bool defer = !x128 && !f32 && wa.lens && wa.retry_cap && wave_slots(wa.n) <= kDeferSlots;
+    const bool defer = !x128 && !f32 && wa.lens && wa.retry_cap && warm_wave_slots(ctx, wa.n) <= kDeferSlots;
     const uint32_t wblocks = warm_blocks_for(wa.n, (uint64_t)ctx->cus * warm_per_cu(f32), defer ? kWalkIlp : 1u);
     YK_HIP(hipEventRecord(ev[0], ctx->aux));
     if (!x128) {
@@ -3432,17 +1585,29 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
   ctx->prev_n = nlaunch;
   ctx->run_len = (same_run ? ctx->run_len : 0) + nlaunch;
   ctx->prev_geom = geom;
-  ctx->prev_shape = shape;
+  ctx->prev_shape = lp.shape;
   ctx->prev_ok = !x128 && !warm_first;
   ctx->prev_enqueued = true;
   ctx->dirty = false;
+  *launches_out = launches;
+  return YK_OK;
+}
+
+// The call's statistics, as far as the host knows them (finish_stats adds the device's)
+void call_stats(ykgpu_context* ctx, const yk_render_params* p, const double* sums_dev, const ykgpu_film* film,
+                       const LaunchPlan& lp, uint32_t launches) {
+  const bool x128 = lp.x128;
+  const int grid = lp.grid, block = lp.block;
+  const uint32_t nps = lp.nps, K = lp.K, nlaunch = lp.nlaunch, kWarmRing = lp.kWarmRing, kColRing = lp.kColRing;
+  const size_t welem = lp.welem, retry_n = lp.retry_n;
+  const uint32_t retry_cap = lp.retry_cap;
   ctx->stats = yk_render_stats{};
-  ctx->stats.samples = (uint64_t)p->row_count * tile_width(p) * spp;
+  ctx->stats.samples = (uint64_t)p->row_count * tile_width(p) * lp.spp;
   ctx->stats.launches = launches;
   ctx->stats.grid_blocks = (uint32_t)grid;
   ctx->stats.launch_spp = K;
-  ctx->stats.mem_shrinks = mem_shrinks;
-  ctx->stats.seed_key = seed_key;
+  ctx->stats.mem_shrinks = lp.mem_shrinks;
+  ctx->stats.seed_key = lp.seed_key;
   // what this call needed (device_bytes: what the context holds)
   {
     const uint64_t lanes = (uint64_t)grid * block;
@@ -3460,7 +1625,18 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
     ctx->stats.call_bytes = cb;
   }
   ctx->stats_pending = true;
-  return YK_OK;
+}
+
+int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, double* sums_dev, hipStream_t st,
+           uint32_t s_begin, uint32_t s_end, ykgpu_film* film) {
+  LaunchPlan lp;
+  LaunchArgs la;
+  uint32_t launches = 0;
+  int rc = plan_launch(ctx, p, s_begin, s_end, film, lp);
+  if (!rc) rc = fill_args(ctx, p, rgb_dev, sums_dev, film, lp, la);
+  if (!rc) rc = enqueue_launches(ctx, st, s_end, film, lp, la, &launches);
+  if (!rc) call_stats(ctx, p, sums_dev, film, lp, launches);
+  return rc;
 }
 
 // Device memory the context holds (yk_render_stats.device_bytes)
@@ -3663,23 +1839,6 @@ int upload_tree(ykgpu_context* ctx, DevTree& t, const std::vector<double>& cente
 extern "C" {
 
 uint32_t ykgpu_abi_version(void) { return YKGPU_ABI_VERSION; }
-
-#ifdef YK_DRAIN_DIAG
-// (diagnostic builds only, tools/drain_probe.py) the wave records since the last clear:
-// [launch][block][wave] x {start, end, HW_ID | XCC_ID << 32}
-int ykgpu_diag_wave_times(unsigned long long* out, size_t n) {
-  const size_t cap = sizeof(yk_wave_times) / sizeof(unsigned long long);
-  YK_HIP(hipDeviceSynchronize());
-  YK_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(yk_wave_times), std::min(n, cap) * sizeof(unsigned long long)));
-  return YK_OK;
-}
-int ykgpu_diag_wave_times_clear(void) {
-  YK_HIP(hipDeviceSynchronize());
-  static std::vector<unsigned long long> z(sizeof(yk_wave_times) / sizeof(unsigned long long), 0ull);
-  YK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(yk_wave_times), z.data(), z.size() * sizeof(unsigned long long)));
-  return YK_OK;
-}
-#endif
 
 const char* ykgpu_last_error(void) { return g_last_error.c_str(); }
 
@@ -4605,4 +2764,3 @@ int yk_film_view_of(ykgpu_film* film, yk_film_view* out) {
   out->feature_grid = &film->feature_grid;
   return YK_OK;
 }
-#endif  // YK_SPLIT != 2
