@@ -143,7 +143,7 @@ def test_invalid_arguments_are_reported():
 
 def test_fastdiv_magic_numbers_divide_exactly():
     """The kernels divide 31-bit slot and pixel indices by runtime-invariant divisors with the
-    host's magic numbers (ykgpu_render.hip fastdiv / yk_render_device.hpp fdiv): q = (n * m) >> sh, sh = 31 + ceil(log2 d),
+    host's magic numbers (yk_pipeline.hip fastdiv / yk_render_device.hpp fdiv): q = (n * m) >> sh, sh = 31 + ceil(log2 d),
     m = ceil(2^sh / d).  Restated here and checked against integer division on every divisor kind
     the renderer meets (image widths, padded pixel counts) and random ones, at the numerator's
     extremes and at random numerators."""

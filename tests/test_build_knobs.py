@@ -3,7 +3,10 @@
 Round 11 removed every structural `YK_*` switch of the render kernels, keeping the branch the
 product was built with (profiles/r11_knobs/README.md lists them, the value kept and the evidence).
 Round 12 took the two path kernels out of ykgpu_render.hip into units of their own, each source
-file compiled once (profiles/r12_split/README.md), which removed `YK_SPLIT` too.  Three things keep that true: the
+file compiled once (profiles/r12_split/README.md), which removed `YK_SPLIT` too.  Round 13 split the rest of that
+file into context, pipeline, film, group and math units behind yk_host_internal.hpp
+(profiles/r13_units/README.md), which removed the film view the denoise and feature units worked
+through and their copies of the error macro.  Three things keep that true: the
 product's Makefile recipes define no `YK_*` at all, none of the removed names comes back into the
 sources, and a test variant compiles one host-side unit with its switch and links the product's
 other objects.
@@ -15,11 +18,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "uecraytracing_amd", "csrc")
 
 # the library's units: one object each (the Makefile's HIP_UNITS and CXX_UNITS)
-HIP_UNITS = ("yk_render_f64", "yk_render_f32", "ykgpu_render", "yk_denoise", "yk_features")
+HIP_UNITS = ("yk_render_f64", "yk_render_f32", "yk_pipeline", "yk_context", "yk_film", "yk_group", "yk_math",
+             "yk_denoise", "yk_features")
 CXX_UNITS = ("yk_host", "yk_bvh")
 # the rules that make the product: the two object patterns and the link
 PRODUCT_TARGETS = ("%.o", "libykgpu.so")
-TEST_VARIANTS = {"abl/libykgpu_retry%.so": "YK_RETRY_CAP_FORCE", "abl/libykgpu_stack%.so": "YK_STACK_CAP_FORCE"}
+# target -> (its switch, the one unit that reads it, the Makefile variable of the product's other objects)
+TEST_VARIANTS = {"abl/libykgpu_retry%.so": ("YK_RETRY_CAP_FORCE", "yk_pipeline", "REST_RETRY"),
+                 "abl/libykgpu_stack%.so": ("YK_STACK_CAP_FORCE", "yk_context", "REST_STACK")}
 
 REMOVED = [
     "YK_NODE_BF",
@@ -53,6 +59,11 @@ REMOVED = [
     "kLensDefer",
     "YK_SPLIT",
     "yk_split_f32_kernel",
+    "yk_film_view",
+    "yk_film_view_of",
+    "yk_film_fail",
+    "YKD_HIP",
+    "YKF_HIP",
 ]
 
 
@@ -92,6 +103,9 @@ def test_units_are_the_makefiles():
         assert os.path.exists(os.path.join(CSRC, u + ".hip")), u
     for u in CXX_UNITS:
         assert os.path.exists(os.path.join(CSRC, u + ".cpp")), u
+    # every .hip file is a unit of the library, and the file the round-13 split dissolved is gone
+    assert sorted(f[:-4] for f in os.listdir(CSRC) if f.endswith(".hip")) == sorted(HIP_UNITS)
+    assert not os.path.exists(os.path.join(CSRC, "ykgpu_render.hip"))
 
 
 def test_product_recipes_define_no_yk_switch():
@@ -117,28 +131,32 @@ def test_product_recipes_define_no_yk_switch():
 
 def test_test_variants_compile_one_host_unit_and_link_the_products_objects():
     rules = recipes()
-    assert variable("REST") == ["$(filter-out", "$(LIB)/ykgpu_render.o,$(OBJS))"]
     assert variable("OBJS") == ["$(HIP_UNITS:%=$(LIB)/%.o)", "$(CXX_UNITS:%=$(LIB)/%.o)"]
-    for target, switch in TEST_VARIANTS.items():
+    for target, (switch, unit, rest) in TEST_VARIANTS.items():
+        assert variable(rest) == ["$(filter-out", "$(LIB)/%s.o,$(OBJS))" % unit]
         lines = [l for l in rules[target] if not l.strip().startswith("@")]
         compiles = [l for l in lines if " -c " in l]
         links = [l for l in lines if " -shared " in l]
         assert len(compiles) == 1 and len(links) == 1 and len(lines) == 2, lines
-        # the one compile: ykgpu_render.hip with the variant's switch, and nothing else defined
+        # the one compile: the unit that reads the switch, with that switch and nothing else defined
         assert re.findall(r"-D\S*", compiles[0]) == [f"-D{switch}=$*"], compiles[0]
         assert re.fullmatch(r"YK_\w+_FORCE", switch)
-        assert compiles[0].split()[-1] == "ykgpu_render.hip"
+        assert compiles[0].split()[-1] == unit + ".hip"
         obj = compiles[0].split()[compiles[0].split().index("-o") + 1]
         # the link: that object and the product's other objects, unchanged
-        assert links[0].split()[links[0].split().index("$@") + 1:] == [obj, "$(REST)"], links[0]
-    # the switches are host code of ykgpu_render.hip, a unit without a render kernel
-    for f in os.listdir(CSRC):
-        text = open(os.path.join(CSRC, f), errors="replace").read()
-        if f not in ("ykgpu_render.hip", "Makefile"):
-            assert "_CAP_FORCE" not in text, f
-    main = open(os.path.join(CSRC, "ykgpu_render.hip")).read()
-    assert not re.search(r"void\s+yk_render_\w+\s*\(", main)
-    assert "#include \"yk_path.hpp\"" not in main
+        assert links[0].split()[links[0].split().index("$@") + 1:] == [obj, "$(%s)" % rest], links[0]
+        # the switch is host code of its unit alone, a unit without a render kernel
+        for f in os.listdir(CSRC):
+            text = open(os.path.join(CSRC, f), errors="replace").read()
+            if f not in (unit + ".hip", "Makefile"):
+                assert switch not in text, f
+            if f not in [u + ".hip" for _, u, _ in TEST_VARIANTS.values()] + ["Makefile"]:
+                assert "_CAP_FORCE" not in text, f
+        main = open(os.path.join(CSRC, unit + ".hip")).read()
+        assert switch in main
+        assert [w for w in re.findall(r"YK_\w+_CAP_FORCE", main) if w != switch] == [], unit
+        assert not re.search(r"void\s+yk_render_\w+\s*\(", main)
+        assert "#include \"yk_path.hpp\"" not in main
 
 
 def test_no_removed_switch_in_the_sources():

@@ -1,6 +1,6 @@
 """The launch schedule of a render call as a pure function (csrc/yk_schedule.hpp), on the CPU.
 
-launch() (csrc/ykgpu_render.hip) takes a call's launch sizes and its (first sample, samples) list
+launch() (csrc/yk_pipeline.hip) takes a call's launch sizes and its (first sample, samples) list
 from yksched::launch_sizes / launch_schedule; the library exports them for this test as
 yk_schedule_plan (yk_host.cpp; not in include/ykgpu.h).
 

@@ -2,8 +2,7 @@
 // variance-guided non-local-means filter over a film's own tile, defined operation by operation in
 // IEEE double so that numpy restates it bit for bit (tests/film_denoise_ref.py).
 //
-// A unit of its own: the render unit's kernels compile exactly as before, and this one reaches a
-// film only through yk_film_view (yk_film_internal.hpp).  Three kernels on the context's stream:
+// A unit of its own.  Three kernels on the context's stream:
 //   yk_film_moments  slot-order sums and second moments → pixel-order planes m_c, v_c
 //   yk_film_nlm      the filter, one workgroup per 32 x 8 pixels, m and v of the block and its
 //                    halo in LDS
@@ -22,24 +21,18 @@
 #include "../../include/ykgpu.h"
 #include "yk_device.hpp"
 #include "yk_film_internal.hpp"
+#include "yk_host_internal.hpp"
+
+using namespace ykhost;
 
 namespace {
 
-constexpr uint32_t kNoPixel = 0xffffffffu;
 constexpr uint32_t kMaxRadius = 10, kMaxPatch = 3;
 // The block of output pixels of one workgroup.  32 wide: a wave is two rows of 32 threads, and the
 // 32 lanes an 8-byte LDS read is serviced in (ds_read_b64: two groups of 32 lanes over 64 banks of
 // 4 B) are one row — 32 consecutive doubles, every bank once — whatever the plane's pitch and
 // whatever the window offset.
 constexpr uint32_t kBlockW = 32, kBlockH = 8, kThreads = kBlockW * kBlockH;
-
-#define YKD_HIP(call)                                                                             \
-  do {                                                                                            \
-    hipError_t e_ = (call);                                                                       \
-    if (e_ != hipSuccess)                                                                         \
-      return yk_film_fail(e_ == hipErrorOutOfMemory ? YK_ERR_NOMEM : YK_ERR_DEVICE,               \
-                          (std::string(#call) + ": " + hipGetErrorString(e_)).c_str());           \
-  } while (0)
 
 // m_c = s_c / nd and v_c = max(0, (q_c - (s_c*s_c)/nd) / (nd*(nd - 1))) (film_e2's v_c) of every
 // slot, gathered through the film's slot → pixel order into six pixel-order planes
@@ -314,12 +307,118 @@ size_t nlm_lds_bytes(uint32_t R, uint32_t F) {
   return (6 * (kBlockW + 2 * H) * (kBlockH + 2 * H) + 2 * (kBlockW + 2 * F) * (kBlockH + 2 * F)) * sizeof(double);
 }
 
+// The body of both denoise entry points: the checks, the film's denoise buffers, the moments, the
+// caller's filter, the RGB8 conversion and the read-back.  `name` is the entry point's, for the
+// error text.  The callers differ in three steps:
+//   feature_checks()          after the colour parameters' checks and before the other checks
+//                             (guided: the feature parameters and the scene's generation)
+//   prepare()                 after every check: the filter kernel's dynamic-LDS attribute (per call:
+//                             the attribute belongs to the current device; guided: the feature
+//                             planes first)
+//   filter(a, grid, lds, st)  enqueues the filter on st and returns the launch's error
+// stats (may be null) receives moments_ms, filter_ms and total_ms.
+template <typename Checks, typename Prepare, typename Filter>
+int denoise_call(ykgpu_film* film, const char* name, const yk_denoise_params& dp, double* mean_host, uint8_t* rgb_host,
+                 yk_denoise_stats* stats, Checks&& feature_checks, Prepare&& prepare, Filter&& filter) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (int rc = film_ready(film)) return rc;
+  if (dp.radius > kMaxRadius) return fail(YK_ERR_INVALID, "denoise: radius must be <= 10");
+  if (dp.patch > kMaxPatch) return fail(YK_ERR_INVALID, "denoise: patch must be <= 3");
+  if (!(dp.k2 > 0) || !std::isfinite(dp.k2)) return fail(YK_ERR_INVALID, "denoise: k2 must be finite and > 0");
+  if (!(dp.alpha >= 0) || !std::isfinite(dp.alpha)) return fail(YK_ERR_INVALID, "denoise: alpha must be finite and >= 0");
+  if (!(dp.eps > 0) || !std::isfinite(dp.eps)) return fail(YK_ERR_INVALID, "denoise: eps must be finite and > 0");
+  if (int rc = feature_checks()) return rc;
+  if (!mean_host && !rgb_host) return fail(YK_ERR_INVALID, "denoise: mean_host and rgb_host are both null");
+  if (!film_consecutive(film))
+    return fail(YK_ERR_UNSUPPORTED, "denoise: the film's tile is not consecutive image rows and columns");
+  const uint32_t* const count = film_counts(film);
+  if (!count && film->done < 2) return fail(YK_ERR_INVALID, "denoise needs at least two samples in every pixel");
+
+  YK_HIP(hipSetDevice(film->device));
+  if (int rc = prepare()) return rc;
+  const uint32_t rows = film->p.row_count, wt = tile_width(&film->p);
+  const hipStream_t stream = film->ctx->stream;  // (film calls are synchronous on it)
+  const size_t npix = (size_t)rows * wt;
+  // the film's denoise buffers: [m, v planes: 6 npix doubles][out: 3 npix doubles][rgb: 3 npix bytes][low]
+  const size_t off_out = align256(6 * npix * sizeof(double)), off_rgb = off_out + align256(3 * npix * sizeof(double));
+  const size_t off_low = off_rgb + align256(3 * npix), bytes = off_low + 256;
+  if (!film->d_denoise) YK_HIP(hipMalloc(&film->d_denoise, bytes));  // (a film's tile never changes size)
+  char* const base = (char*)film->d_denoise;
+  double* const d_mv = (double*)base;
+  double* const d_out = (double*)(base + off_out);
+  uint8_t* const d_rgb = (uint8_t*)(base + off_rgb);
+  unsigned long long* const d_low = (unsigned long long*)(base + off_low);
+
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 3 && stats && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
+  const auto record = [&](int k) {
+    if (stats && e == hipSuccess) e = hipEventRecord(ev[k], stream);
+  };
+  unsigned long long low = 0;
+  if (e == hipSuccess) e = hipMemsetAsync(d_low, 0, sizeof low, stream);
+  record(0);
+  if (e == hipSuccess) {
+    const uint32_t blocks = std::max(1u, std::min((film->nps + 255) / 256, 2048u));
+    hipLaunchKernelGGL(yk_film_moments, dim3(blocks), dim3(256), 0, stream, film->d_plane, film->d_order, count, d_mv,
+                       d_low, film->nps, (uint32_t)npix, film->done);
+    e = hipGetLastError();
+  }
+  record(1);
+  // (the filter does not depend on the verdict: it is enqueued behind the moments, and its result
+  // is dropped if a count turns out to be below 2)
+  if (e == hipSuccess) {
+    NlmArgs a{};
+    a.mv = d_mv;
+    a.out = d_out;
+    a.rows = rows;
+    a.wt = wt;
+    a.npix = (uint32_t)npix;
+    a.radius = dp.radius;
+    a.patch = dp.patch;
+    a.k2 = dp.k2;
+    a.alpha = dp.alpha;
+    a.eps = dp.eps;
+    a.npatch = (double)(3 * (2 * dp.patch + 1) * (2 * dp.patch + 1));
+    const dim3 grid((wt + kBlockW - 1) / kBlockW, (rows + kBlockH - 1) / kBlockH);
+    e = filter(a, grid, nlm_lds_bytes(dp.radius, dp.patch), stream);
+  }
+  if (e == hipSuccess && rgb_host) {
+    const uint32_t blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>((3 * npix + 255) / 256, 2048));
+    hipLaunchKernelGGL(yk_film_rgb8, dim3(blocks), dim3(256), 0, stream, d_out, d_rgb, (uint64_t)(3 * npix));
+    e = hipGetLastError();
+  }
+  record(2);
+  if (e == hipSuccess) e = hipMemcpyAsync(&low, d_low, sizeof low, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  // (the outputs are written only once the call is known to succeed)
+  if (e == hipSuccess && low == 0) {
+    if (mean_host) e = hipMemcpyAsync(mean_host, d_out, 3 * npix * sizeof(double), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && rgb_host) e = hipMemcpyAsync(rgb_host, d_rgb, 3 * npix, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  }
+  float ms_m = 0, ms_f = 0;
+  if (stats && e == hipSuccess) e = hipEventElapsedTime(&ms_m, ev[0], ev[1]);
+  if (stats && e == hipSuccess) e = hipEventElapsedTime(&ms_f, ev[1], ev[2]);
+  for (hipEvent_t v : ev)
+    if (v) (void)hipEventDestroy(v);
+  if (e != hipSuccess)
+    return fail(e == hipErrorOutOfMemory ? YK_ERR_NOMEM : YK_ERR_DEVICE, std::string(name) + ": " + hipGetErrorString(e));
+  if (low) return fail(YK_ERR_INVALID, "denoise needs at least two samples in every pixel");
+  if (stats) {
+    stats->moments_ms = ms_m;
+    stats->filter_ms = ms_f;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return YK_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int yk_denoise_defaults(yk_denoise_params* out) {
-  if (!out) return yk_film_fail(YK_ERR_INVALID, "null out");
+  if (!out) return fail(YK_ERR_INVALID, "null out");
   out->radius = 5;
   out->patch = 1;
   out->k2 = 0.5;
@@ -330,105 +429,24 @@ int yk_denoise_defaults(yk_denoise_params* out) {
 
 int ykgpu_film_denoise(ykgpu_film* film, const yk_denoise_params* params, double* mean_host, uint8_t* rgb_host,
                        yk_denoise_stats* stats) {
-  const auto t0 = std::chrono::steady_clock::now();
-  yk_film_view f{};
-  if (int rc = yk_film_view_of(film, &f)) return rc;
   yk_denoise_params dp;
   yk_denoise_defaults(&dp);
   if (params) dp = *params;
-  if (dp.radius > kMaxRadius) return yk_film_fail(YK_ERR_INVALID, "denoise: radius must be <= 10");
-  if (dp.patch > kMaxPatch) return yk_film_fail(YK_ERR_INVALID, "denoise: patch must be <= 3");
-  if (!(dp.k2 > 0) || !std::isfinite(dp.k2)) return yk_film_fail(YK_ERR_INVALID, "denoise: k2 must be finite and > 0");
-  if (!(dp.alpha >= 0) || !std::isfinite(dp.alpha)) return yk_film_fail(YK_ERR_INVALID, "denoise: alpha must be finite and >= 0");
-  if (!(dp.eps > 0) || !std::isfinite(dp.eps)) return yk_film_fail(YK_ERR_INVALID, "denoise: eps must be finite and > 0");
-  if (!mean_host && !rgb_host) return yk_film_fail(YK_ERR_INVALID, "denoise: mean_host and rgb_host are both null");
-  if (!f.consecutive)
-    return yk_film_fail(YK_ERR_UNSUPPORTED, "denoise: the film's tile is not consecutive image rows and columns");
-  if (!f.count && f.done < 2) return yk_film_fail(YK_ERR_INVALID, "denoise needs at least two samples in every pixel");
-
-  YKD_HIP(hipSetDevice(f.device));
-  const size_t npix = (size_t)f.rows * f.wt;
-  // the film's denoise buffers: [m, v planes: 6 npix doubles][out: 3 npix doubles][rgb: 3 npix bytes][low]
-  const size_t off_out = align256(6 * npix * sizeof(double)), off_rgb = off_out + align256(3 * npix * sizeof(double));
-  const size_t off_low = off_rgb + align256(3 * npix), bytes = off_low + 256;
-  if (!*f.scratch) YKD_HIP(hipMalloc(f.scratch, bytes));  // (a film's tile never changes size)
-  char* const base = (char*)*f.scratch;
-  double* const d_mv = (double*)base;
-  double* const d_out = (double*)(base + off_out);
-  uint8_t* const d_rgb = (uint8_t*)(base + off_rgb);
-  unsigned long long* const d_low = (unsigned long long*)(base + off_low);
-
-  // (per call: the attribute belongs to the current device)
-  YKD_HIP(hipFuncSetAttribute((const void*)yk_film_nlm, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)nlm_lds_bytes(kMaxRadius, kMaxPatch)));
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 3 && stats && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
-  const auto record = [&](int k) {
-    if (stats && e == hipSuccess) e = hipEventRecord(ev[k], f.stream);
-  };
-  unsigned long long low = 0;
-  if (e == hipSuccess) e = hipMemsetAsync(d_low, 0, sizeof low, f.stream);
-  record(0);
-  if (e == hipSuccess) {
-    const uint32_t blocks = std::max(1u, std::min((f.nps + 255) / 256, 2048u));
-    hipLaunchKernelGGL(yk_film_moments, dim3(blocks), dim3(256), 0, f.stream, f.plane, f.order, f.count, d_mv, d_low,
-                       f.nps, (uint32_t)npix, f.done);
-    e = hipGetLastError();
-  }
-  record(1);
-  // (the filter does not depend on the verdict: it is enqueued behind the moments, and its result
-  // is dropped if a count turns out to be below 2)
-  if (e == hipSuccess) {
-    NlmArgs a{};
-    a.mv = d_mv;
-    a.out = d_out;
-    a.rows = f.rows;
-    a.wt = f.wt;
-    a.npix = (uint32_t)npix;
-    a.radius = dp.radius;
-    a.patch = dp.patch;
-    a.k2 = dp.k2;
-    a.alpha = dp.alpha;
-    a.eps = dp.eps;
-    a.npatch = (double)(3 * (2 * dp.patch + 1) * (2 * dp.patch + 1));
-    const dim3 grid((f.wt + kBlockW - 1) / kBlockW, (f.rows + kBlockH - 1) / kBlockH);
-    hipLaunchKernelGGL(yk_film_nlm, grid, dim3(kThreads), nlm_lds_bytes(dp.radius, dp.patch), f.stream, a);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess && rgb_host) {
-    const uint32_t blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>((3 * npix + 255) / 256, 2048));
-    hipLaunchKernelGGL(yk_film_rgb8, dim3(blocks), dim3(256), 0, f.stream, d_out, d_rgb, (uint64_t)(3 * npix));
-    e = hipGetLastError();
-  }
-  record(2);
-  if (e == hipSuccess) e = hipMemcpyAsync(&low, d_low, sizeof low, hipMemcpyDeviceToHost, f.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(f.stream);
-  // (the outputs are written only once the call is known to succeed)
-  if (e == hipSuccess && low == 0) {
-    if (mean_host) e = hipMemcpyAsync(mean_host, d_out, 3 * npix * sizeof(double), hipMemcpyDeviceToHost, f.stream);
-    if (e == hipSuccess && rgb_host) e = hipMemcpyAsync(rgb_host, d_rgb, 3 * npix, hipMemcpyDeviceToHost, f.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(f.stream);
-  }
-  float ms_m = 0, ms_f = 0;
-  if (stats && e == hipSuccess) e = hipEventElapsedTime(&ms_m, ev[0], ev[1]);
-  if (stats && e == hipSuccess) e = hipEventElapsedTime(&ms_f, ev[1], ev[2]);
-  for (hipEvent_t v : ev)
-    if (v) (void)hipEventDestroy(v);
-  if (e != hipSuccess)
-    return yk_film_fail(e == hipErrorOutOfMemory ? YK_ERR_NOMEM : YK_ERR_DEVICE,
-                        (std::string("ykgpu_film_denoise: ") + hipGetErrorString(e)).c_str());
-  if (low) return yk_film_fail(YK_ERR_INVALID, "denoise needs at least two samples in every pixel");
-  if (stats) {
-    stats->moments_ms = ms_m;
-    stats->filter_ms = ms_f;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return YK_OK;
+  return denoise_call(
+      film, "ykgpu_film_denoise", dp, mean_host, rgb_host, stats, [] { return YK_OK; },
+      []() -> int {
+        YK_HIP(hipFuncSetAttribute((const void*)yk_film_nlm, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)nlm_lds_bytes(kMaxRadius, kMaxPatch)));
+        return YK_OK;
+      },
+      [](const NlmArgs& a, dim3 grid, size_t lds, hipStream_t st) {
+        hipLaunchKernelGGL(yk_film_nlm, grid, dim3(kThreads), lds, st, a);
+        return hipGetLastError();
+      });
 }
 
 int yk_guided_defaults(yk_denoise_params* colour, yk_feature_params* feat) {
-  if (!colour && !feat) return yk_film_fail(YK_ERR_INVALID, "null out");
+  if (!colour && !feat) return fail(YK_ERR_INVALID, "null out");
   if (colour) {
     yk_denoise_defaults(colour);
     colour->k2 = 2.0;  // the pair of DESIGN.md §6.4 (tools/features_tune.py)
@@ -447,117 +465,52 @@ int yk_guided_defaults(yk_denoise_params* colour, yk_feature_params* feat) {
 
 int ykgpu_film_denoise_guided(ykgpu_film* film, const yk_denoise_params* params, const yk_feature_params* fparams,
                               double* mean_host, uint8_t* rgb_host, yk_guided_stats* stats) {
-  const auto t0 = std::chrono::steady_clock::now();
-  yk_film_view f{};
-  if (int rc = yk_film_view_of(film, &f)) return rc;
   yk_denoise_params dp;
   yk_feature_params fp;
   yk_guided_defaults(&dp, &fp);
   if (params) dp = *params;
   if (fparams) fp = *fparams;
-  if (dp.radius > kMaxRadius) return yk_film_fail(YK_ERR_INVALID, "denoise: radius must be <= 10");
-  if (dp.patch > kMaxPatch) return yk_film_fail(YK_ERR_INVALID, "denoise: patch must be <= 3");
-  if (!(dp.k2 > 0) || !std::isfinite(dp.k2)) return yk_film_fail(YK_ERR_INVALID, "denoise: k2 must be finite and > 0");
-  if (!(dp.alpha >= 0) || !std::isfinite(dp.alpha)) return yk_film_fail(YK_ERR_INVALID, "denoise: alpha must be finite and >= 0");
-  if (!(dp.eps > 0) || !std::isfinite(dp.eps)) return yk_film_fail(YK_ERR_INVALID, "denoise: eps must be finite and > 0");
-  if (fp.grid < 1 || fp.grid > 4) return yk_film_fail(YK_ERR_INVALID, "features: grid must be 1..4");
-  if (fp.reserved) return yk_film_fail(YK_ERR_INVALID, "features: reserved must be 0");
-  if (!(fp.k2 > 0) || !std::isfinite(fp.k2)) return yk_film_fail(YK_ERR_INVALID, "features: k2 must be finite and > 0");
-  if (!(fp.alpha >= 0) || !std::isfinite(fp.alpha)) return yk_film_fail(YK_ERR_INVALID, "features: alpha must be finite and >= 0");
-  for (double tau : {fp.tau_albedo, fp.tau_normal, fp.tau_depth})
-    if (!(tau > 0)) return yk_film_fail(YK_ERR_INVALID, "features: tau must be > 0 (+inf switches a group off)");
-  if (f.stale) return yk_film_fail(YK_ERR_INVALID, "the context's scene was set after the film was created");
-  if (!mean_host && !rgb_host) return yk_film_fail(YK_ERR_INVALID, "denoise: mean_host and rgb_host are both null");
-  if (!f.consecutive)
-    return yk_film_fail(YK_ERR_UNSUPPORTED, "denoise: the film's tile is not consecutive image rows and columns");
-  if (!f.count && f.done < 2) return yk_film_fail(YK_ERR_INVALID, "denoise needs at least two samples in every pixel");
-
   const double* d_feat = nullptr;
   double ms_feat = 0;
-  if (int rc = yk_film_features_ensure(f, fp.grid, &d_feat, &ms_feat)) return rc;
-  const size_t npix = (size_t)f.rows * f.wt;
-  // the film's denoise buffers, ykgpu_film_denoise's
-  const size_t off_out = align256(6 * npix * sizeof(double)), off_rgb = off_out + align256(3 * npix * sizeof(double));
-  const size_t off_low = off_rgb + align256(3 * npix), bytes = off_low + 256;
-  if (!*f.scratch) YKD_HIP(hipMalloc(f.scratch, bytes));
-  char* const base = (char*)*f.scratch;
-  double* const d_mv = (double*)base;
-  double* const d_out = (double*)(base + off_out);
-  uint8_t* const d_rgb = (uint8_t*)(base + off_rgb);
-  unsigned long long* const d_low = (unsigned long long*)(base + off_low);
-
-  YKD_HIP(hipFuncSetAttribute((const void*)yk_film_nlm_guided, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)nlm_lds_bytes(kMaxRadius, kMaxPatch)));
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 3 && stats && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
-  const auto record = [&](int k) {
-    if (stats && e == hipSuccess) e = hipEventRecord(ev[k], f.stream);
-  };
-  unsigned long long low = 0;
-  if (e == hipSuccess) e = hipMemsetAsync(d_low, 0, sizeof low, f.stream);
-  record(0);
-  if (e == hipSuccess) {
-    const uint32_t blocks = std::max(1u, std::min((f.nps + 255) / 256, 2048u));
-    hipLaunchKernelGGL(yk_film_moments, dim3(blocks), dim3(256), 0, f.stream, f.plane, f.order, f.count, d_mv, d_low,
-                       f.nps, (uint32_t)npix, f.done);
-    e = hipGetLastError();
-  }
-  record(1);
-  if (e == hipSuccess) {
-    GuidedArgs g{};
-    NlmArgs& a = g.c;
-    a.mv = d_mv;
-    a.out = d_out;
-    a.rows = f.rows;
-    a.wt = f.wt;
-    a.npix = (uint32_t)npix;
-    a.radius = dp.radius;
-    a.patch = dp.patch;
-    a.k2 = dp.k2;
-    a.alpha = dp.alpha;
-    a.eps = dp.eps;
-    a.npatch = (double)(3 * (2 * dp.patch + 1) * (2 * dp.patch + 1));
-    g.feat = d_feat;
-    g.k2 = fp.k2;
-    g.alpha = fp.alpha;
-    g.tau[0] = fp.tau_albedo;
-    g.tau[1] = fp.tau_normal;
-    g.tau[2] = fp.tau_depth;
-    const dim3 grid((f.wt + kBlockW - 1) / kBlockW, (f.rows + kBlockH - 1) / kBlockH);
-    hipLaunchKernelGGL(yk_film_nlm_guided, grid, dim3(kThreads), nlm_lds_bytes(dp.radius, dp.patch), f.stream, g);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess && rgb_host) {
-    const uint32_t blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>((3 * npix + 255) / 256, 2048));
-    hipLaunchKernelGGL(yk_film_rgb8, dim3(blocks), dim3(256), 0, f.stream, d_out, d_rgb, (uint64_t)(3 * npix));
-    e = hipGetLastError();
-  }
-  record(2);
-  if (e == hipSuccess) e = hipMemcpyAsync(&low, d_low, sizeof low, hipMemcpyDeviceToHost, f.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(f.stream);
-  // (the outputs are written only once the call is known to succeed)
-  if (e == hipSuccess && low == 0) {
-    if (mean_host) e = hipMemcpyAsync(mean_host, d_out, 3 * npix * sizeof(double), hipMemcpyDeviceToHost, f.stream);
-    if (e == hipSuccess && rgb_host) e = hipMemcpyAsync(rgb_host, d_rgb, 3 * npix, hipMemcpyDeviceToHost, f.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(f.stream);
-  }
-  float ms_m = 0, ms_f = 0;
-  if (stats && e == hipSuccess) e = hipEventElapsedTime(&ms_m, ev[0], ev[1]);
-  if (stats && e == hipSuccess) e = hipEventElapsedTime(&ms_f, ev[1], ev[2]);
-  for (hipEvent_t v : ev)
-    if (v) (void)hipEventDestroy(v);
-  if (e != hipSuccess)
-    return yk_film_fail(e == hipErrorOutOfMemory ? YK_ERR_NOMEM : YK_ERR_DEVICE,
-                        (std::string("ykgpu_film_denoise_guided: ") + hipGetErrorString(e)).c_str());
-  if (low) return yk_film_fail(YK_ERR_INVALID, "denoise needs at least two samples in every pixel");
-  if (stats) {
+  yk_denoise_stats ds{};
+  const int rc = denoise_call(
+      film, "ykgpu_film_denoise_guided", dp, mean_host, rgb_host, stats ? &ds : nullptr,
+      [&]() -> int {
+        if (fp.grid < 1 || fp.grid > 4) return fail(YK_ERR_INVALID, "features: grid must be 1..4");
+        if (fp.reserved) return fail(YK_ERR_INVALID, "features: reserved must be 0");
+        if (!(fp.k2 > 0) || !std::isfinite(fp.k2)) return fail(YK_ERR_INVALID, "features: k2 must be finite and > 0");
+        if (!(fp.alpha >= 0) || !std::isfinite(fp.alpha)) return fail(YK_ERR_INVALID, "features: alpha must be finite and >= 0");
+        for (double tau : {fp.tau_albedo, fp.tau_normal, fp.tau_depth})
+          if (!(tau > 0)) return fail(YK_ERR_INVALID, "features: tau must be > 0 (+inf switches a group off)");
+        if (film->scene_gen != film->ctx->scene_gen)
+          return fail(YK_ERR_INVALID, "the context's scene was set after the film was created");
+        return YK_OK;
+      },
+      [&]() -> int {
+        if (int rc = yk_film_features_ensure(film, fp.grid, &d_feat, &ms_feat)) return rc;
+        YK_HIP(hipFuncSetAttribute((const void*)yk_film_nlm_guided, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)nlm_lds_bytes(kMaxRadius, kMaxPatch)));
+        return YK_OK;
+      },
+      [&](const NlmArgs& a, dim3 grid, size_t lds, hipStream_t st) {
+        GuidedArgs g{};
+        g.c = a;
+        g.feat = d_feat;
+        g.k2 = fp.k2;
+        g.alpha = fp.alpha;
+        g.tau[0] = fp.tau_albedo;
+        g.tau[1] = fp.tau_normal;
+        g.tau[2] = fp.tau_depth;
+        hipLaunchKernelGGL(yk_film_nlm_guided, grid, dim3(kThreads), lds, st, g);
+        return hipGetLastError();
+      });
+  if (!rc && stats) {
     stats->features_ms = ms_feat;
-    stats->moments_ms = ms_m;
-    stats->filter_ms = ms_f;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stats->moments_ms = ds.moments_ms;
+    stats->filter_ms = ds.filter_ms;
+    stats->total_ms = ds.total_ms;
   }
-  return YK_OK;
+  return rc;
 }
 
 }  // extern "C"

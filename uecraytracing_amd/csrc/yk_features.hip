@@ -2,10 +2,9 @@
 // first-hit albedo, normal and depth of every pixel of a film's tile, defined operation by operation
 // in IEEE double so that numpy restates it bit for bit (tests/film_features_ref.py).
 //
-// A unit of its own, like yk_denoise.hip: the render unit's kernels compile exactly as before, and
-// this one reaches a film only through yk_film_view (yk_film_internal.hpp).  One kernel,
-// yk_film_features, on the context's stream; its result lives in planes the film owns and is
-// computed once per (film, grid).
+// A unit of its own, like yk_denoise.hip.  One kernel, yk_film_features, on the context's stream;
+// its result lives in planes the film owns (ykgpu_film, yk_host_internal.hpp) and is computed once
+// per (film, grid).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -16,10 +15,11 @@
 #include "../../include/ykgpu.h"
 #include "yk_device.hpp"
 #include "yk_film_internal.hpp"
+#include "yk_host_internal.hpp"
+
+using namespace ykhost;
 
 namespace {
-
-using ykd::v3;
 
 constexpr uint32_t kMaxGrid = 4;
 // The block of pixels of one workgroup, yk_film_nlm's: a wave is two rows of 32 pixels.
@@ -28,13 +28,14 @@ constexpr uint32_t kBlockW = 32, kBlockH = 8, kThreads = kBlockW * kBlockH;
 // 160 KiB, more than its waves allow), and the final scene's 485 spheres are one chunk.
 constexpr uint32_t kChunk = 512;
 
-#define YKF_HIP(call)                                                                             \
-  do {                                                                                            \
-    hipError_t e_ = (call);                                                                       \
-    if (e_ != hipSuccess)                                                                         \
-      return yk_film_fail(e_ == hipErrorOutOfMemory ? YK_ERR_NOMEM : YK_ERR_DEVICE,               \
-                          (std::string(#call) + ": " + hipGetErrorString(e_)).c_str());           \
-  } while (0)
+// the device tables as the kernel reads them: the geometry as 4 doubles per sphere (cx, cy, cz,
+// radius*radius), the materials as kYkMatStride bytes per sphere with the albedo, the radius and the
+// kind at these offsets
+constexpr size_t kYkMatStride = 64, kYkMatAlbedo = 0, kYkMatRadius = 32, kYkMatKind = 48;
+static_assert(sizeof(SphereGeo) == 4 * sizeof(double) && offsetof(SphereGeo, rr) == 3 * sizeof(double), "FeatArgs::geo");
+static_assert(sizeof(SphereMat) == kYkMatStride && offsetof(SphereMat, ar) == kYkMatAlbedo &&
+                  offsetof(SphereMat, ab) == kYkMatAlbedo + 16 && offsetof(SphereMat, radius) == kYkMatRadius &&
+                  offsetof(SphereMat, kind) == kYkMatKind, "FeatArgs::mat");
 
 struct FeatArgs {
   yk_camera cam;
@@ -46,8 +47,6 @@ struct FeatArgs {
   uint32_t W, H, rows, wt, npix;
   uint32_t row_begin, row_stride, row_band, col_begin, col_stride, col_band;
 };
-
-__device__ __forceinline__ v3 ld3(const double* p) { return {p[0], p[1], p[2]}; }
 
 // One thread per pixel of the tile, its g x g sub-rays one after the other, row-major, the sums of
 // f and f*f in registers: the fold order is the definition's.  Every ray leaves the camera's origin,
@@ -174,57 +173,63 @@ __global__ __launch_bounds__(kThreads) void yk_film_features(FeatArgs a) {
 
 }  // namespace
 
-int yk_film_features_ensure(const yk_film_view& f, uint32_t grid, const double** planes, double* ms) {
-  if (grid < 1 || grid > kMaxGrid) return yk_film_fail(YK_ERR_INVALID, "features: grid must be 1..4");
-  if (f.stale) return yk_film_fail(YK_ERR_INVALID, "the context's scene was set after the film was created");
-  YKF_HIP(hipSetDevice(f.device));
-  const size_t npix = (size_t)f.rows * f.wt;
-  if (!*f.features) {  // (a film's tile never changes size)
-    *f.feature_grid = 0;
-    YKF_HIP(hipMalloc(f.features, kYkFeatPlanes * npix * sizeof(double)));
+int ykhost::yk_film_features_ensure(ykgpu_film* film, uint32_t grid, const double** planes, double* ms) {
+  if (grid < 1 || grid > kMaxGrid) return fail(YK_ERR_INVALID, "features: grid must be 1..4");
+  const ykgpu_context* ctx = film->ctx;
+  if (film->scene_gen != ctx->scene_gen)
+    return fail(YK_ERR_INVALID, "the context's scene was set after the film was created");
+  YK_HIP(hipSetDevice(film->device));
+  const yk_render_params& p = film->p;
+  const uint32_t rows = p.row_count, wt = tile_width(&p);
+  const hipStream_t stream = ctx->stream;  // (film calls are synchronous on it)
+  const size_t npix = (size_t)rows * wt;
+  if (!film->d_features) {  // (a film's tile never changes size)
+    film->feature_grid = 0;
+    YK_HIP(hipMalloc(&film->d_features, kYkFeatPlanes * npix * sizeof(double)));
   }
-  *planes = (const double*)*f.features;
+  *planes = (const double*)film->d_features;
   if (ms) *ms = 0.0;
-  if (*f.feature_grid == grid) return YK_OK;
-  *f.feature_grid = 0;  // (until the pass is whole)
+  if (film->feature_grid == grid) return YK_OK;
+  film->feature_grid = 0;  // (until the pass is whole)
+  const TileCols cols = film_cols(film);
   FeatArgs a{};
-  a.cam = f.cam;
-  a.geo = f.geo;
-  a.mat = f.mat;
-  a.out = (double*)*f.features;
-  a.t_min = f.t_min;
-  a.nspheres = f.nspheres;
+  a.cam = ctx->cam;
+  a.geo = (const double*)ctx->d_geo;
+  a.mat = (const unsigned char*)ctx->d_mat;
+  a.out = (double*)film->d_features;
+  a.t_min = p.t_min;
+  a.nspheres = ctx->nspheres;
   a.grid = grid;
-  a.W = f.W;
-  a.H = f.H;
-  a.rows = f.rows;
-  a.wt = f.wt;
+  a.W = p.image_width;
+  a.H = p.image_height;
+  a.rows = rows;
+  a.wt = wt;
   a.npix = (uint32_t)npix;
-  a.row_begin = f.row_begin;
-  a.row_stride = f.row_stride;
-  a.row_band = f.row_band;
-  a.col_begin = f.col_begin;
-  a.col_stride = f.col_stride;
-  a.col_band = f.col_band;
+  a.row_begin = p.row_begin;
+  a.row_stride = p.row_stride;
+  a.row_band = p.row_band_log2;
+  a.col_begin = cols.begin;
+  a.col_stride = cols.stride;
+  a.col_band = cols.band;
   hipEvent_t ev[2] = {nullptr, nullptr};
   hipError_t e = hipEventCreate(&ev[0]);
   if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-  if (e == hipSuccess) e = hipEventRecord(ev[0], f.stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
   if (e == hipSuccess) {
-    const dim3 blocks((f.wt + kBlockW - 1) / kBlockW, (f.rows + kBlockH - 1) / kBlockH);
-    hipLaunchKernelGGL(yk_film_features, blocks, dim3(kThreads), 0, f.stream, a);
+    const dim3 blocks((wt + kBlockW - 1) / kBlockW, (rows + kBlockH - 1) / kBlockH);
+    hipLaunchKernelGGL(yk_film_features, blocks, dim3(kThreads), 0, stream, a);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipEventRecord(ev[1], f.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(f.stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
   float t = 0;
   if (e == hipSuccess) e = hipEventElapsedTime(&t, ev[0], ev[1]);
   for (hipEvent_t v : ev)
     if (v) (void)hipEventDestroy(v);
   if (e != hipSuccess)
-    return yk_film_fail(e == hipErrorOutOfMemory ? YK_ERR_NOMEM : YK_ERR_DEVICE,
-                        (std::string("ykgpu_film_features: ") + hipGetErrorString(e)).c_str());
-  *f.feature_grid = grid;
+    return fail(e == hipErrorOutOfMemory ? YK_ERR_NOMEM : YK_ERR_DEVICE,
+                std::string("ykgpu_film_features: ") + hipGetErrorString(e));
+  film->feature_grid = grid;
   if (ms) *ms = t;
   return YK_OK;
 }
@@ -232,19 +237,18 @@ int yk_film_features_ensure(const yk_film_view& f, uint32_t grid, const double**
 extern "C" {
 
 int ykgpu_film_features(ykgpu_film* film, uint32_t grid, double* mean_host, double* var_host, double* ms) {
-  yk_film_view f{};
-  if (int rc = yk_film_view_of(film, &f)) return rc;
+  if (int rc = film_ready(film)) return rc;
   const double* planes = nullptr;
   double t = 0;
-  if (int rc = yk_film_features_ensure(f, grid, &planes, &t)) return rc;
+  if (int rc = yk_film_features_ensure(film, grid, &planes, &t)) return rc;
   if (mean_host || var_host) {
     // the planes are channel-major (the filter's reads are rows of one channel); the caller's
     // arrays are pixel-major: transposed on the host, in memory of the call's own, so that nothing
     // is written when the copy fails
-    const size_t npix = (size_t)f.rows * f.wt;
+    const size_t npix = (size_t)film->p.row_count * tile_width(&film->p);
     std::vector<double> h(2 * kYkFeatChannels * npix);
-    YKF_HIP(hipMemcpyAsync(h.data(), planes, h.size() * sizeof(double), hipMemcpyDeviceToHost, f.stream));
-    YKF_HIP(hipStreamSynchronize(f.stream));
+    YK_HIP(hipMemcpyAsync(h.data(), planes, h.size() * sizeof(double), hipMemcpyDeviceToHost, film->ctx->stream));
+    YK_HIP(hipStreamSynchronize(film->ctx->stream));
     for (uint32_t c = 0; c < kYkFeatChannels; ++c) {
       const double* m = h.data() + (size_t)c * npix;
       const double* v = m + kYkFeatChannels * npix;

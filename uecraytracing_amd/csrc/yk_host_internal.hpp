@@ -1,0 +1,242 @@
+// yk_host_internal.hpp — what more than one host unit of the library needs, defined once: the error
+// slot and the YK_HIP macro, the structs behind the C-ABI's opaque handles (ykgpu_context,
+// ykgpu_film, ykgpu_group) and the host functions that cross units (namespace ykhost).  Not part of
+// the C-ABI, not installed.  Who defines what: yk_context.hip the error slot and the statistics,
+// yk_pipeline.hip the parameter checks, the tile helpers, the processing order and launch(),
+// yk_film.hip film_ready, yk_features.hip the feature pass.
+#ifndef YK_HOST_INTERNAL_HPP
+#define YK_HOST_INTERNAL_HPP
+
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cstdint>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/ykgpu.h"
+#include "yk_render_device.hpp"
+
+namespace ykhost {
+// sets ykgpu_last_error's message for the calling thread and returns code
+int fail(int code, const std::string& msg);
+// that message (ykgpu_group_create and ykgpu_render_devices keep it across a clean-up)
+std::string& last_error();
+}  // namespace ykhost
+
+#define YK_HIP(call)                                                                      \
+  do {                                                                                    \
+    hipError_t e_ = (call);                                                               \
+    if (e_ != hipSuccess)                                                                 \
+      return ykhost::fail(e_ == hipErrorOutOfMemory ? YK_ERR_NOMEM : YK_ERR_DEVICE,       \
+                          std::string(#call) + ": " + hipGetErrorString(e_));             \
+  } while (0)
+
+// A BVH on the device: the FP64 kernel's (boxes grown for the exact test's rounding, DESIGN.md
+// §4) or the FP32 kernel's (grown for render<float>'s sphere test, §4.1), with its LDS layout
+// [nodes][leaf geometry][leaf ids][traversal stacks] and the persistent grid it leaves room for.
+struct DevTree {
+  DevNode* nodes = nullptr;
+  void* leaf_geo = nullptr;      // SphereGeo (FP64) or float4 (FP32), in leaf order
+  uint32_t* leaf_ids = nullptr;  // leaf slot → tuple index
+  int32_t root = 0;              // root code (byte offset of the root node, or a leaf code)
+  uint32_t depth = 0, n_nodes = 0;
+  double origin_bound = 0;  // |o|_inf beyond which a ray takes the linear scan (< 0: every ray)
+  uint32_t geo_off = 0, ids_off = 0;  // leaf geometry and ids in LDS, after the nodes
+  size_t bytes = 0;                   // device bytes of nodes, leaf geometry and ids
+  // LDS plan per kernel shape: [0] kBlock threads (mt19937 instances), [1] kBlockX128 (xor128)
+  struct Plan {
+    bool in_lds = false;
+    uint32_t lds_bytes = 0, stack_off = 0, stack_cap = 0, stack_entries = 0;
+    bool stack_check = true;  // the kernel checks the stack top against stack_cap
+    uint32_t tgeo_off = 0, mat_off = 0;  // shading tables in LDS (FP64 kernel), 0: none
+    int grid = 0;                        // persistent blocks: occupancy x CUs
+  } plan[2];
+  void release() {
+    (void)hipFree(nodes);
+    (void)hipFree(leaf_geo);
+    (void)hipFree(leaf_ids);
+    nodes = nullptr;
+    leaf_geo = nullptr;
+    leaf_ids = nullptr;
+    bytes = 0;
+  }
+};
+
+struct ykgpu_context {
+  int device = 0;
+  int cus = 0;
+  DevTree t64, t32;  // the FP64 and FP32 kernels' trees over the current scene
+  size_t scratch_lanes = 0;
+  char* d_warm = nullptr;  // warm-up ring: a StartRec (FP64) or StartRecF (FP32) per sample slot
+  uint4* d_retry = nullptr;  // the FP64 warm-ups' lens-retry rings: retry_cap x 48 B per wave
+  size_t retry_cap = 0;
+  double* d_col = nullptr;     // sample colours of one launch (kColStride doubles per slot)
+  double* d_acc = nullptr;     // running per-pixel sums between launches
+  size_t col_cap = 0, acc_cap = 0;
+  uint32_t* d_order = nullptr;  // processing slot → tile pixel, for (order_w, order_rows)
+  uint32_t order_w = 0, order_rows = 0, order_slots = 0, order_stride = 0, order_mode = 0;
+  size_t warm_cap = 0;
+  hipStream_t stream = nullptr;
+  hipStream_t aux = nullptr;  // the MT warm-ups run here, beside the render launches
+  hipStream_t red = nullptr;  // the ordered reduces run here, beside the next render launch
+  hipStream_t alt = nullptr;  // odd render launches: a launch starts while the previous drains
+  hipStream_t ren = nullptr;  // even render launches (alt and ren: the device's top stream priority)
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  std::vector<hipEvent_t> lev;  // per launch: warm-up start, render start, reduce start, end
+  uint32_t lev_used = 0;
+  // Cross-call pipelining (launch()): the previous call's per-launch events and ring geometry, and
+  // a global launch counter that numbers the ring slots, the scratch parity and the render
+  // stream across calls
+  std::vector<hipEvent_t> lev_prev;
+  uint32_t lev_prev_used = 0;  // (events of the previous call in lev_prev: YKGPU_TIMELINE prints them)
+  uint32_t prev_n = 0;
+  // per global launch number g (mod kDepRing): its render's end and its reduce's end, the events a
+  // later launch that reuses its start-record or colour buffer waits for, whichever call it was in
+  std::vector<hipEvent_t> gev;
+  // launches enqueued back to back with the current ring geometry (prev_geom), over calls: a call
+  // overlaps the ones before it only when the last max(ring depths) launches had its geometry
+  uint64_t run_len = 0;
+  // the previous call's ring and scratch geometry: a call overlaps it only when every field is
+  // equal (launch() `ov`; equal slot offsets in every ring buffer and scratch slice)
+  struct RingGeom {
+    uint64_t nps = 0, K = 0, welem = 0, warm_ring = 0, col_ring = 0, lanes = 0, id_stride = 0;
+    const void *warm = nullptr, *col = nullptr, *mt = nullptr, *ids = nullptr;
+    bool operator==(const RingGeom& o) const {
+      return nps == o.nps && K == o.K && welem == o.welem && warm_ring == o.warm_ring && col_ring == o.col_ring &&
+             lanes == o.lanes && id_stride == o.id_stride && warm == o.warm && col == o.col && mt == o.mt &&
+             ids == o.ids;
+    }
+  } prev_geom;
+  uint64_t prev_shape = 0;  // (nps, kmax, precision, engine) of the previous call: launch() `inflight`
+  bool prev_ok = false;
+  bool prev_enqueued = false;  // the previous call's launches were all enqueued (its events exist)
+  bool dirty = false;          // a call failed part-way: its enqueued work is not tracked
+  uint64_t g_next = 0;
+  SphereGeo* d_geo = nullptr;
+  SphereMat* d_mat = nullptr;
+  float4* d_geo_f = nullptr;  // FP32 geometry (cx, cy, cz, r*r in float), tuple order
+  uint32_t nspheres = 0;
+  yk_camera cam{};
+  bool have_scene = false;
+  uint64_t scene_gen = 0;  // counts ykgpu_set_scene calls: a film renders only the scene it was created with
+  uint32_t* d_counter = nullptr;        // sample-slot counters, one per launch of a call
+  uint32_t counter_cap = 0;
+  unsigned long long* d_clk = nullptr;  // shader-clock probes, 4 words per launch (YK_CLOCK_*)
+  unsigned long long* d_stats = nullptr;  // kCounters counters
+  uint32_t* d_mt = nullptr;            // grid*256*624 words
+  uint16_t* d_ids = nullptr;            // grid*256*id_stride
+  uint32_t id_stride = 0;
+  size_t id_lanes = 0;
+  uint8_t* d_rgb = nullptr;
+  size_t rgb_cap = 0;
+  double* d_sums = nullptr;
+  size_t sums_cap = 0;
+  yk_render_stats stats{};
+  bool stats_pending = false;
+  double* d_trace = nullptr;  // ykgpu_render_trace's buffers (only during that call)
+  uint32_t* d_trace_counts = nullptr;
+  uint32_t trace_cap = 0;
+  std::chrono::steady_clock::time_point t0;
+};
+
+// A film (include/ykgpu.h): the accumulation state of one tile, owned by the film — the six planes
+// (yk_film_reduce) and the processing order they are laid out in, on the device and on the host
+// (read and write permute there) — plus what fixes its samples: the params, with the seed key
+// drawn at create, and the scene generation.
+struct ykgpu_film {
+  ykgpu_context* ctx = nullptr;
+  int device = 0;
+  yk_render_params p{};
+  uint64_t scene_gen = 0;
+  uint32_t done = 0;
+  uint32_t nps = 0;   // processing slots (>= pixels)
+  uint64_t npix = 0;  // pixels of the tile
+  double* d_plane = nullptr;   // 6 * nps
+  uint32_t* d_order = nullptr;  // nps
+  unsigned long long* d_result = nullptr;  // yk_film_error's count and maximum
+  std::vector<uint32_t> order;
+  bool torn = false;  // an accumulate failed part-way: the planes hold part of a chunk (until a write)
+  // Adaptive passes.  hist: count value → pixels holding it (the host's whole knowledge of the
+  // counts: a pass reads back one word per candidate value, never a per-pixel array).  While it
+  // has one entry the film is uniform, `done` is that value and d_count is not kept up to date
+  // (yk_film_reduce does not touch it): an adaptive pass fills it first.
+  std::map<uint32_t, uint64_t> hist;
+  uint32_t* d_count = nullptr;  // nps, slot order
+  uint32_t* d_take = nullptr;   // nps: the pass's samples per slot, 0 = not selected
+  uint32_t* d_blocks = nullptr;  // ceil(nps / 256): the compaction's block totals / offsets
+  uint32_t* d_gorder = nullptr;  // the current group's processing order (g_slots of its nps-slot buffer)
+  uint32_t* d_gmap = nullptr;    // ... and its slots' film slots
+  unsigned long long* d_hist = nullptr;  // kFilmVals words
+  uint32_t g_slots = 0;  // != 0: launch() renders the group (d_gorder, d_gmap) instead of the film's order
+  // ykgpu_film_denoise's buffers (yk_denoise.hip), allocated at the film's first denoise
+  void* d_denoise = nullptr;
+  // ykgpu_film_features' planes (yk_features.hip), allocated at the first pass, and their grid
+  void* d_features = nullptr;
+  uint32_t feature_grid = 0;
+  bool uniform() const { return hist.size() <= 1; }
+};
+
+struct ykgpu_group {
+  std::vector<ykgpu_context*> ctx;  // one per entry of the device list
+  std::vector<uint8_t*> tile;       // each entry's RGB8 tile on its device
+  std::vector<size_t> tile_cap;
+  std::vector<yk_render_stats> st;  // the last render's, per entry
+  yk_render_stats total{};          // ... and of the whole call
+};
+
+// the render units' instances (yk_render_f64.hip, yk_render_f32.hip), by (scene in LDS, kMode).
+// (Inline here, not in yk_pipeline.hip: KernelArgs lives in the anonymous namespace, so a function
+// that returns a RenderKernel has internal linkage and cannot be declared across units.)
+namespace {
+inline RenderKernel fp64_kernel(bool lds, int mode) { return (RenderKernel)yk_fp64_kernel(lds, mode); }
+inline RenderKernel f32_kernel(bool lds, int mode) { return (RenderKernel)yk_f32_kernel(lds, mode); }
+}  // namespace
+
+namespace ykhost {
+
+// yk_pipeline.hip
+int check_params(const ykgpu_context* ctx, const yk_render_params* p);
+uint32_t tile_width(const yk_render_params* p);
+uint64_t host_row_y(const yk_render_params* p, uint32_t t);
+uint64_t host_col_x(const yk_render_params* p, uint32_t j);
+uint32_t order_mode();
+uint32_t order_stride(const yk_render_params* p);
+std::vector<uint32_t> build_order(uint32_t W, uint32_t rows, uint32_t stride, uint32_t mode);
+hipError_t create_render_stream(hipStream_t* s);
+int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, double* sums_dev, hipStream_t st,
+           uint32_t s_begin, uint32_t s_end, ykgpu_film* film);
+// yk_context.hip
+uint64_t device_bytes(const ykgpu_context* ctx);
+int finish_stats(ykgpu_context* ctx);
+// yk_film.hip: null or torn film: YK_ERR_INVALID with the last error set, like every film call
+int film_ready(const ykgpu_film* film);
+// yk_features.hip: the feature planes of the film at grid g (1..4) on the device, computed on the
+// context's stream unless the film already holds them; *ms (may be null) receives the pass's device
+// time, 0 when the cached planes were reused.  Synchronous.  YK_ERR_INVALID on a stale scene or a
+// grid out of range.
+int yk_film_features_ensure(ykgpu_film* film, uint32_t grid, const double** planes, double* ms);
+
+// What the denoise and feature units derive from a film:
+// its per-slot counts, null while the film is uniform (every count == done)
+inline const uint32_t* film_counts(const ykgpu_film* film) { return film->uniform() ? nullptr : film->d_count; }
+// the tile is image rows y0.. and image columns x0.. without gaps
+// (both maps increase strictly, so the last entry tells whether any step was larger than one)
+inline bool film_consecutive(const ykgpu_film* film) {
+  const yk_render_params& p = film->p;
+  return host_row_y(&p, p.row_count - 1) == (uint64_t)p.row_begin + p.row_count - 1 &&
+         host_col_x(&p, tile_width(&p) - 1) == (uint64_t)p.col_begin + tile_width(&p) - 1;
+}
+// the tile's column set as the kernels take it: the whole width (col_count == 0) is 0, 1, 0
+struct TileCols {
+  uint32_t begin, stride, band;
+};
+inline TileCols film_cols(const ykgpu_film* film) {
+  const yk_render_params& p = film->p;
+  return p.col_count ? TileCols{p.col_begin, p.col_stride, p.col_band_log2} : TileCols{0, 1, 0};
+}
+
+}  // namespace ykhost
+
+#endif

@@ -1,7 +1,7 @@
 // yk_render_device.hpp — what every kernel unit of the renderer shares: the execution model, the
 // device-side records (scene tables, kernel arguments, start records), the kernel-side tuning block
 // and the address and camera helpers the warm-up and both path kernels use.
-// (The execution model is described at the top of ykgpu_render.hip.)
+// (The execution model is described at the top of yk_pipeline.hip.)
 #ifndef YK_RENDER_DEVICE_HPP
 #define YK_RENDER_DEVICE_HPP
 
@@ -19,7 +19,7 @@
 using ykd::v3;
 
 // The render kernels' instances, by (scene in LDS, kMode): each unit hands out pointers to its own
-// kernels (yk_render_f64.hip, yk_render_f32.hip), and ykgpu_render.hip launches through them
+// kernels (yk_render_f64.hip, yk_render_f32.hip), and yk_pipeline.hip launches through them
 const void* yk_fp64_kernel(bool lds, int mode);
 const void* yk_f32_kernel(bool lds, int mode);
 

@@ -1,5 +1,5 @@
 // yk_render_f64.hip — the FP64 path kernel (yk_render_persistent, and yk_render_counting with the
-// work counters): the execution model is described at the top of ykgpu_render.hip.
+// work counters): the execution model is described at the top of yk_pipeline.hip.
 #include "yk_path.hpp"
 #ifdef YK_DRAIN_DIAG
 #include <algorithm>
@@ -763,7 +763,7 @@ const void* yk_fp64_kernel(bool lds, int mode) { return (const void*)fp64_kernel
 
 #ifdef YK_DRAIN_DIAG
 // (the records live in this unit, so their accessors do too: hipMemcpyFromSymbol needs the defining
-// unit.  They report a HIP failure by code alone; the last-error text is ykgpu_render.hip's.)
+// unit.  They report a HIP failure by code alone; the last-error text is yk_context.hip's.)
 #define YK_DIAG_HIP(call) \
   do {                    \
     if ((call) != hipSuccess) return YK_ERR_DEVICE; \

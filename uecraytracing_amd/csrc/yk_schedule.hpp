@@ -128,7 +128,7 @@ constexpr const char* ab_knob(const char*) { return nullptr; }
 #endif
 }  // namespace
 
-// ---- The launch schedule of a render call (launch(), ykgpu_render.hip) as a pure rule ----
+// ---- The launch schedule of a render call (launch(), yk_pipeline.hip) as a pure rule ----
 namespace yksched {
 
 // a sample slot's colour record (kColStride doubles, yk_render_device.hpp)
