@@ -409,6 +409,23 @@ int ykgpu_set_scene(ykgpu_context* ctx, const yk_sphere* spheres, uint32_t count
   int rc = upload_tree(ctx, ctx->t64, centers, radii, cam_ext, bopt, kLeafCapF64, geo.data(), sizeof(SphereGeo),
                        sizeof(SphereGeo), k64, true);
   if (rc) return rc;
+  // The FP64 visit's float distances assume neither overflow nor underflow.  With
+  // B = origin_bound: the origin product o * (1/d), |1/d| < 1e30 < 2^100 (the kernel's own guard),
+  // stays finite for B <= 2^27 (inf - inf would cull a box that holds the hit); and a scaled
+  // distance 2^-24 t below float's normal range is off by up to 2^-126 absolutely, 2^-102 in t,
+  // which the box growth's unused share delta |1/d| / 8 = 2^-24 B |1/d| covers with 2^18 to spare
+  // for B >= 2^-60 max(1, D), D bounding the primary rays' direction components (secondary
+  // directions have unit length).  A scene outside that scale renders FP64 with the linear scan.
+  {
+    double dmax = 1.0;
+    for (int k = 0; k < 3; ++k)
+      dmax = std::max(dmax, std::fabs(camera->lower_left_corner[k]) + std::fabs(camera->horizontal[k]) +
+                                std::fabs(camera->vertical[k]) + std::fabs(camera->origin[k]) +
+                                std::fabs(camera->lens_radius) *
+                                    (std::fabs(camera->lens_u[k]) + std::fabs(camera->lens_v[k])));
+    if (!(ctx->t64.origin_bound <= 0x1p27) || !(ctx->t64.origin_bound >= 0x1p-60 * dmax))
+      ctx->t64.origin_bound = -1.0;
+  }
   ykbvh::Options fopt = bopt;
   fopt.max_leaf = kLeafCapF32;  // the FP32 kernel's leaf loop is unrolled for two spheres
   if (const char* e = ab_knob("YKGPU_BVH_ALLAXES_F32")) fopt.all_axes = std::atoi(e) != 0;  // (A/B; on: neutral)
