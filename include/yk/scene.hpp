@@ -22,6 +22,7 @@
 #pragma once
 
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <tuple>
 #include <type_traits>
@@ -53,6 +54,22 @@ template <class T, class A>
 constexpr vec3<T, A> operator*(const vec3<T, A>& v, T s) { return {v.x * s, v.y * s, v.z * s}; }
 template <class T, class A>
 constexpr vec3<T, A> operator/(const vec3<T, A>& v, T s) { return {v.x / s, v.y / s, v.z / s}; }
+
+// ---- rays and hit records (reference: yk/ray.hpp:11-20, yk/hittable.hpp:16-22): the data members
+// the bridge's renderer::hit reads and fills; the arithmetic runs on the GPU ------------------
+template <class T>
+struct ray {
+  pos3<T, world_tag> origin;
+  vec3<T> direction;
+};
+template <class T>
+struct hit_record {
+  pos3<T, world_tag> p;
+  vec3<T> normal;
+  T t;
+  std::size_t id;
+  bool front_face;
+};
 
 // ---- colours (reference: yk/color.hpp:13-24,119-120) ---------------------------------------
 template <class T>

@@ -21,6 +21,7 @@
 #include <cstdint>
 #include <cstring>
 #include <iomanip>
+#include <optional>
 #include <ostream>
 #include <stdexcept>
 #include <initializer_list>
@@ -365,6 +366,8 @@ class renderer {
     if (!ctx_ || group_) throw error(YK_ERR_UNSUPPORTED, "a film belongs to one context: not a device group");
     return ctx_;
   }
+  // the camera last set
+  const yk_camera& camera() const { return cam_; }
   // the scene last set (yk_scene_hash of it names the scene a saved film belongs to)
   uint64_t scene_hash() const { return yk_scene_hash(spheres_.data(), (uint32_t)spheres_.size(), &cam_); }
 
@@ -481,6 +484,40 @@ class renderer {
           }
         }
     }
+  }
+
+  // world.hit(r, t_min, t_max) (hittable.hpp:32-34) of the scene last set, for a batch of rays of
+  // either yk::ray type: one hit_record<double> per ray, id set, or nothing for a miss (include/
+  // ykgpu.h "ray queries": the reference's ordered scan in double, bit for bit).  A ray outside the
+  // query's domain (a NaN, a zero direction, ...) is reported as an error: the reference would not
+  // have returned.  One context only, like a film.
+  template <class Ray, class T>
+  std::vector<std::optional<yk::hit_record<double>>> hit(const std::vector<Ray>& rays, T t_min, T t_max) {
+    if (!ctx_ || group_) throw error(YK_ERR_UNSUPPORTED, "ray queries belong to one context: not a device group");
+    std::vector<yk_ray> in(rays.size());
+    for (size_t i = 0; i < rays.size(); ++i) {
+      detail::put3(in[i].origin, rays[i].origin);
+      detail::put3(in[i].direction, rays[i].direction);
+      in[i].t_min = static_cast<double>(t_min);
+      in[i].t_max = static_cast<double>(t_max);
+    }
+    std::vector<yk_hit> out(rays.size());
+    check(ykgpu_cast_rays(ctx_, in.data(), in.size(), 0, out.data()), "ykgpu_cast_rays");
+    std::vector<std::optional<yk::hit_record<double>>> recs(rays.size());
+    for (size_t i = 0; i < out.size(); ++i) {
+      const yk_hit& h = out[i];
+      if (h.flags & YK_HIT_OUT_OF_DOMAIN)
+        throw error(YK_ERR_INVALID, "hit: ray " + std::to_string(i) + " is outside the query's domain");
+      if (!(h.flags & YK_HIT_HIT)) continue;
+      yk::hit_record<double> r{};
+      r.p.x = h.p[0], r.p.y = h.p[1], r.p.z = h.p[2];
+      r.normal.x = h.normal[0], r.normal.y = h.normal[1], r.normal.z = h.normal[2];
+      r.t = h.t;
+      r.id = h.id;
+      r.front_face = (h.flags & YK_HIT_FRONT_FACE) != 0;
+      recs[i] = r;
+    }
+    return recs;
   }
 
   // the last render's statistics (a group: the whole call, include/ykgpu.h)

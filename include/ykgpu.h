@@ -576,6 +576,79 @@ int ykgpu_film_features(ykgpu_film* film, uint32_t grid, double* mean_host, doub
 int ykgpu_film_denoise_guided(ykgpu_film* film, const yk_denoise_params* colour, const yk_feature_params* feat,
                               double* mean_host, uint8_t* rgb_host, yk_guided_stats* stats);
 
+/* ---- ray queries (ABI 11) -------------------------------------------------
+ * The reference's public world.hit(r, t_min, t_max) (hittable.hpp:32-34, hittable_list.hpp:32-58,
+ * sphere.hpp:25-48) for batches of arbitrary rays against the scene of the last ykgpu_set_scene:
+ * closest hits and occlusion tests, in double, bit for bit.  FP64 only: hit with T = float and
+ * device groups are out of scope (a group's contexts can be queried one by one).
+ *
+ * CLOSEST MODE (default).  For a ray in the domain (below) the result is hittable_list::hit_impl's:
+ * the ordered scan in tuple order with closest_so_far = the ray's t_max at first.  Per sphere
+ * (centre c, radius r), o and d the ray's origin and direction:
+ *   oc = o - c;  a = (d.x*d.x + d.y*d.y) + d.z*d.z;  half_b = (oc.x*d.x + oc.y*d.y) + oc.z*d.z
+ *   cc = ((oc.x*oc.x + oc.y*oc.y) + oc.z*oc.z) - r*r;  disc = half_b*half_b - a*cc;  disc < 0: a miss
+ *   sq = math::sqrt(disc);  root = (-half_b - sq) / a
+ *   if (root < t_min || closest < root) { root = (-half_b + sq) / a;  the same test: a miss }
+ *   closest = root, the sphere is the hit (so of equal roots the later index wins)
+ * and of the last accepted sphere:  p = o + d*t,  outward = (p - c) / r,
+ * front_face = dot(d, outward) < 0,  normal = front_face ? outward : -outward.
+ * Every + - * / is one IEEE double operation, rounded on its own and never fused.
+ * A hit: p, normal, t as above, id the sphere's tuple index, flags YK_HIT_HIT (| YK_HIT_FRONT_FACE).
+ * A miss: every double +0.0, id 0xFFFFFFFF, flags 0.
+ *
+ * ANY-HIT MODE (YK_CAST_ANY_HIT).  flags carries YK_HIT_HIT exactly when closest mode would report
+ * a hit; every other field is as for a miss (which sphere occludes is not reported, so the
+ * traversal stops at the first accepted sphere and the output stays deterministic).
+ *
+ * DOMAIN.  math::sqrt does not terminate on a NaN or infinite discriminant, so the query never
+ * feeds it one.  ykgpu_set_scene records E = max_i(max(|cx|, |cy|, |cz|) + |r|).  With
+ * mo = max_k |o_k| and md = max_k |d_k|, a ray is in the domain iff
+ *   its six components are finite;  t_min is finite and >= 0;  t_max >= t_min (so not NaN; +inf is
+ *   allowed);  2^-500 <= md <= 2^500;  s = mo + E <= 2^500;  md*s <= 2^500
+ * (then half_b^2 <= 9 * 2^1000 and a*cc <= 12 * 2^1000: every discriminant is finite).  A ray
+ * outside the domain does no arithmetic: its doubles are +0.0, its id 0xFFFFFFFF and its flags
+ * YK_HIT_OUT_OF_DOMAIN.  That is a per-ray status, not a call error: one bad ray does not void a
+ * batch.
+ *
+ * YK_CAST_LINEAR_SCAN serves every ray by the ordered scan instead of the BVH (same bytes; A/B and
+ * debugging); YK_CAST_COUNT_WORK counts node visits and sphere tests (slower).
+ *
+ * ykgpu_cast_rays is synchronous: it stages rays and hits through device buffers the context owns
+ * (grown on demand, counted in yk_render_stats.device_bytes, released with the context), in chunks
+ * of at most 2^22 rays, and sums the chunks' kernel times.  ykgpu_cast_rays_async launches on
+ * `stream` (NULL: the context's), reads n yk_ray at rays_device and writes n yk_hit at hits_device
+ * (both 16-byte aligned device memory); it neither synchronises nor records statistics.
+ * ykgpu_set_scene waits for the context's casts, so it cannot pull the scene from under one.
+ * Both calls are independent of the render's rings and streams and leave films untouched.
+ * ykgpu_cast_get_stats reports the last synchronous cast.
+ *   n == 0               YK_OK, nothing done
+ *   YK_ERR_INVALID       a null pointer with n > 0; unknown flag bits
+ *   YK_ERR_NO_SCENE      a call before ykgpu_set_scene */
+typedef struct yk_ray {            /* 64 bytes */
+  double origin[3], direction[3];
+  double t_min, t_max;             /* t_max may be +inf */
+} yk_ray;
+
+typedef struct yk_hit {            /* 64 bytes */
+  double p[3], normal[3], t;       /* hit_record (hittable.hpp:17-22) */
+  uint32_t id;                     /* tuple index, 0xFFFFFFFF when none */
+  uint32_t flags;                  /* YK_HIT_* */
+} yk_hit;
+enum { YK_HIT_HIT = 1u, YK_HIT_FRONT_FACE = 2u, YK_HIT_OUT_OF_DOMAIN = 4u };
+enum { YK_CAST_ANY_HIT = 1u, YK_CAST_LINEAR_SCAN = 2u, YK_CAST_COUNT_WORK = 4u };
+
+typedef struct yk_cast_stats {     /* 64 bytes */
+  double kernel_ms, total_ms;      /* device time of the kernels; the call's host wall clock */
+  uint64_t rays, hits, out_of_domain;
+  uint64_t scan_rays;              /* rays served by the ordered scan */
+  uint64_t node_visits, sphere_tests; /* YK_CAST_COUNT_WORK only, else 0 */
+} yk_cast_stats;
+
+int ykgpu_cast_rays(ykgpu_context* ctx, const yk_ray* rays_host, uint64_t n, uint32_t flags, yk_hit* hits_host);
+int ykgpu_cast_rays_async(ykgpu_context* ctx, const void* rays_device, uint64_t n, uint32_t flags,
+                          void* hits_device, void* stream);
+int ykgpu_cast_get_stats(ykgpu_context* ctx, yk_cast_stats* out); /* the last synchronous cast */
+
 /* ---- host-side scene helpers (no device needed) ---------------------------------------- */
 
 /* camera<double>{} of camera.hpp:16-27 (16:9, viewport height 2, focal length 1, origin 0). */

@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 from . import records
-from .records import Camera, DenoiseParams, DenoiseStats, FeatureParams, FilmPass, GuidedStats, FilmStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
+from .records import CastStats, Hit, Ray, Camera, DenoiseParams, DenoiseStats, FeatureParams, FilmPass, GuidedStats, FilmStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(PKG_DIR, "lib")
@@ -38,6 +38,7 @@ EXPORTS = (
     "yk_film_save_counts", "yk_film_load_counts",
     "yk_denoise_defaults", "ykgpu_film_denoise",
     "yk_guided_defaults", "ykgpu_film_features", "ykgpu_film_denoise_guided",
+    "ykgpu_cast_rays", "ykgpu_cast_rays_async", "ykgpu_cast_get_stats",
 )
 ABI_VERSION = 11
 SCENE_DIR = os.path.join(PKG_DIR, "scenes")  # committed scene files of the BASELINE configs
@@ -125,6 +126,9 @@ def load_library():
         "ykgpu_film_features": ([c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, P(c.c_double)], c.c_int),
         "ykgpu_film_denoise_guided": ([c.c_void_p, P(DenoiseParams), P(FeatureParams), c.c_void_p, c.c_void_p,
                                        P(GuidedStats)], c.c_int),
+        "ykgpu_cast_rays": ([c.c_void_p, c.c_void_p, c.c_uint64, c.c_uint32, c.c_void_p], c.c_int),
+        "ykgpu_cast_rays_async": ([c.c_void_p, c.c_void_p, c.c_uint64, c.c_uint32, c.c_void_p, c.c_void_p], c.c_int),
+        "ykgpu_cast_get_stats": ([c.c_void_p, P(CastStats)], c.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
@@ -545,6 +549,41 @@ class Renderer:
         _check(self._lib.ykgpu_get_stats(self._ctx, ctypes.byref(st)))
         return st.as_dict()
 
+    def cast_rays(self, origins, directions, t_min=records.T_MIN, t_max=float("inf"), any_hit: bool = False,
+                  linear_scan: bool = False, count_work: bool = False) -> np.ndarray:
+        """The reference's world.hit for N rays (include/ykgpu.h "ray queries"): origins and
+        directions float64[N, 3], the limits scalars or float64[N].  Returns records.HIT_DTYPE[N]:
+        p, normal, t, id (records.NO_HIT_ID when none) and flags (records.HIT_*)."""
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise YkError("cast_rays: origins and directions must both be [N, 3]")
+        n = o.shape[0]
+        rays = np.empty(n, records.RAY_DTYPE)
+        rays["origin"], rays["direction"] = o, d
+        rays["t_min"] = np.broadcast_to(np.asarray(t_min, np.float64), (n,))
+        rays["t_max"] = np.broadcast_to(np.asarray(t_max, np.float64), (n,))
+        hits = np.empty(n, records.HIT_DTYPE)
+        flags = ((records.CAST_ANY_HIT if any_hit else 0) | (records.CAST_LINEAR_SCAN if linear_scan else 0) |
+                 (records.CAST_COUNT_WORK if count_work else 0))
+        _check(self._lib.ykgpu_cast_rays(self._ctx, rays.ctypes.data if n else None, n, flags,
+                                         hits.ctypes.data if n else None))
+        return hits
+
+    def cast_rays_device(self, rays_ptr: int, n: int, hits_ptr: int, stream_ptr: int = 0, flags: int = 0):
+        """Enqueue a cast over device memory (ykgpu_cast_rays_async): n yk_ray records at rays_ptr,
+        n yk_hit records written at hits_ptr (e.g. float64 [N, 8] CUDA tensors' data_ptr()), on the
+        stream (0: the context's).  Does not synchronise."""
+        _check(self._lib.ykgpu_cast_rays_async(self._ctx, ctypes.c_void_p(rays_ptr or None), n, flags,
+                                               ctypes.c_void_p(hits_ptr or None),
+                                               ctypes.c_void_p(stream_ptr or None)))
+
+    def cast_stats(self) -> dict:
+        """yk_cast_stats of the last synchronous cast_rays."""
+        st = CastStats()
+        _check(self._lib.ykgpu_cast_get_stats(self._ctx, ctypes.byref(st)))
+        return st.as_dict()
+
 
 class Group:
     """Several device contexts in one process (ykgpu_group): rows dealt cyclically over the
@@ -605,5 +644,5 @@ def render_devices(devices, spheres, camera: Camera, params: RenderParams) -> np
     return out
 
 
-__all__ = ["Renderer", "Film", "FilmPass", "DenoiseParams", "DenoiseStats", "denoise_defaults", "FeatureParams", "GuidedStats", "guided_defaults", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
+__all__ = ["Renderer", "Film", "Ray", "Hit", "CastStats", "FilmPass", "DenoiseParams", "DenoiseStats", "denoise_defaults", "FeatureParams", "GuidedStats", "guided_defaults", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
            "make_params", "load_library", "records", "EXPORTS", "LIB_PATH", "CLI_PATH"]

@@ -106,7 +106,12 @@ const char* kHelp =
     "      --feature-grid arg    sub-rays per pixel side of the feature pass, 1..4 (default: 2)\n"
     "      --aov arg             also write the feature means F as arg.albedo.png, arg.normal.png\n"
     "                            and arg.depth.png: trunc(clamp(x, 0, 0.999) * 256) of F0..F2, of\n"
-    "                            0.5 * F + 0.5 for F3..F5, and of F6 / (1 + F6) (grey: r = g = b)\n";
+    "                            0.5 * F + 0.5 for F3..F5, and of F6 / (1 + F6) (grey: r = g = b)\n"
+    "      --pick arg            arg = X,Y: cast the pixel-centre pinhole ray of image pixel (X, Y)\n"
+    "                            (column, row from the top) at the render's t_min, print\n"
+    "                            'pick X Y: id <n> t <t> p (<x>, <y>, <z>) normal (<x>, <y>, <z>)\n"
+    "                            front <0|1>' (%.17g) or 'pick X Y: miss', and exit without\n"
+    "                            rendering (no output file needed)\n";
 
 struct args {
   bool help = false, verbose_flag = false, stats = false;
@@ -134,6 +139,9 @@ struct args {
   bool denoise_features = false, have_feature_grid = false;
   yk_feature_params fp{};
   std::string aov;
+  // --pick X,Y: one ray query instead of a render
+  bool have_pick = false;
+  uint32_t pick_x = 0, pick_y = 0;
   bool film() const { return denoise || !aov.empty() || adaptive || have_progressive || have_until || have_stop_after || !checkpoint.empty(); }
 };
 
@@ -223,6 +231,14 @@ args parse(int argc, char** argv) {
         a.aov = value(i, n, inl);
         if (a.aov.empty()) throw option_error{"Option 'aov' needs a file name prefix"};
       }
+      else if (n == "pick") {
+        const std::string v = value(i, n, inl);
+        const size_t c = v.find(',');
+        if (c == std::string::npos) throw option_error{"Option 'pick' needs X,Y"};
+        a.pick_x = to_u32(n, v.substr(0, c));
+        a.pick_y = to_u32(n, v.substr(c + 1));
+        a.have_pick = true;
+      }
       else if (n == "checkpoint") {
         a.checkpoint = value(i, n, inl);
         if (a.checkpoint.empty()) throw option_error{"Option 'checkpoint' needs a file name"};
@@ -276,7 +292,7 @@ int main(int argc, char* argv[]) {
     std::cerr << "raytrace: " << e.what << " (see --help)" << std::endl;
     return 2;
   }
-  if (a.help || !a.have_output) {
+  if (a.help || (!a.have_output && !a.have_pick)) {
     std::cout << kHelp << std::endl;
     std::exit(EXIT_SUCCESS);
   }
@@ -285,6 +301,11 @@ int main(int argc, char* argv[]) {
   if (!a.levels.empty()) verbose = a.levels.back();
 
   const uint32_t W = a.width, H = yk_image_height_for(W);
+  if (a.have_pick && (a.pick_x >= W || a.pick_y >= H)) {
+    std::cerr << "raytrace: Option 'pick' names a pixel outside the " << W << " x " << H << " image (see --help)"
+              << std::endl;
+    return 2;
+  }
   const uint32_t seed0 = a.have_seed0 ? a.seed0 : 0u;
   ykgpu::render_options ro;
   ro.seed_mode = a.have_seed0 ? YK_SEED_COUNTER : YK_SEED_RANDOM_DEVICE;
@@ -342,6 +363,27 @@ int main(int argc, char* argv[]) {
       yk_scene_build(a.scene.c_str(), a.scene_seed, s.data(), n, &n, nullptr);
       gpu.set_records(s, cam);
       if (!a.save_scene.empty()) yk_scene_write(a.save_scene.c_str(), s.data(), n, &cam);
+    }
+    if (a.have_pick) {
+      // the feature pass's sub-ray with a = b = 0.5 (include/ykgpu.h "film features"), every step one
+      // IEEE double operation, through the bridge's hit()
+      const yk_camera& c = gpu.camera();
+      const double u = ((double)a.pick_x + 0.5) / (double)W;
+      const double v = ((double)(H - a.pick_y - 1) + 0.5) / (double)H;
+      yk::ray<double> r{};
+      r.origin = {c.origin[0], c.origin[1], c.origin[2]};
+      r.direction = {((c.lower_left_corner[0] + c.horizontal[0] * u) + c.vertical[0] * v) - c.origin[0],
+                     ((c.lower_left_corner[1] + c.horizontal[1] * u) + c.vertical[1] * v) - c.origin[1],
+                     ((c.lower_left_corner[2] + c.horizontal[2] * u) + c.vertical[2] * v) - c.origin[2]};
+      const auto rec = gpu.hit(std::vector<yk::ray<double>>{r}, ro.t_min, (double)INFINITY)[0];
+      if (!rec) {
+        std::printf("pick %u %u: miss\n", a.pick_x, a.pick_y);
+      } else {
+        std::printf("pick %u %u: id %zu t %.17g p (%.17g, %.17g, %.17g) normal (%.17g, %.17g, %.17g) front %d\n",
+                    a.pick_x, a.pick_y, rec->id, rec->t, rec->p.x, rec->p.y, rec->p.z, rec->normal.x, rec->normal.y,
+                    rec->normal.z, rec->front_face ? 1 : 0);
+      }
+      return EXIT_SUCCESS;
     }
     std::cout << "rendering..." << std::endl;
     yk_render_stats st{};

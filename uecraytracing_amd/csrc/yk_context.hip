@@ -55,6 +55,8 @@ uint64_t device_bytes(const ykgpu_context* ctx) {
   if (ctx->d_mt) b += 2ull * ctx->scratch_lanes * ykd::kMtN * sizeof(uint32_t);
   if (ctx->d_ids) b += 2ull * ctx->id_lanes * ctx->id_stride * sizeof(uint16_t);
   b += ctx->rgb_cap + ctx->sums_cap * sizeof(double);
+  b += (uint64_t)ctx->cast_cap * (sizeof(yk_ray) + sizeof(yk_hit));
+  if (ctx->d_cast_counters) b += (uint64_t)kCastStripes * kCastCounters * sizeof(unsigned long long);
   return b;
 }
 
@@ -177,6 +179,7 @@ int upload_tree(ykgpu_context* ctx, DevTree& t, const std::vector<double>& cente
   t.bytes = nn * sizeof(DevNode) + count * elem + count * sizeof(uint32_t);
   t.root = root_code;
   t.depth = bvh.depth;
+  t.wide_depth = wdepth;
   t.origin_bound = bvh.origin_bound;
   t.n_nodes = (uint32_t)snodes.size();
   // LDS layout: [nodes][leaf geometry][leaf ids][tuple-order geometry][materials][traversal
@@ -318,6 +321,10 @@ int ykgpu_context_destroy(ykgpu_context* ctx) {
   (void)hipFree(ctx->d_ids);
   (void)hipFree(ctx->d_rgb);
   (void)hipFree(ctx->d_sums);
+  (void)hipFree(ctx->d_cast_rays);
+  (void)hipFree(ctx->d_cast_hits);
+  (void)hipFree(ctx->d_cast_counters);
+  if (ctx->cast_ev) (void)hipEventDestroy(ctx->cast_ev);
   for (hipEvent_t e : ctx->lev) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->lev_prev) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->gev) (void)hipEventDestroy(e);
@@ -371,6 +378,8 @@ int ykgpu_set_scene(ykgpu_context* ctx, const yk_sphere* spheres, uint32_t count
   // ... and for every stream of the context: a launch() that failed part-way may have queued
   // warm-ups, renders or reduces without recording ev1 (still not the rest of the device)
   for (hipStream_t s : {ctx->aux, ctx->red, ctx->ren, ctx->alt}) YK_HIP(hipStreamSynchronize(s));
+  // ... and for the last ray query enqueued on a caller's stream (ykgpu_cast_rays_async)
+  if (ctx->cast_ev) YK_HIP(hipEventSynchronize(ctx->cast_ev));
   ++ctx->scene_gen;  // from here on the device holds another scene: the context's films are over
   if (count > ctx->nspheres || !ctx->d_geo) {
     (void)hipFree(ctx->d_geo);
@@ -445,6 +454,16 @@ int ykgpu_set_scene(ykgpu_context* ctx, const yk_sphere* spheres, uint32_t count
   YK_HIP(hipStreamSynchronize(ctx->stream));
   ctx->nspheres = count;
   ctx->cam = *camera;
+  // the ray queries' domain rule (include/ykgpu.h): E = max_i(max(|cx|, |cy|, |cz|) + |r|)
+  double ext = 0;
+  for (uint32_t i = 0; i < count; ++i) {
+    const yk_sphere& s = spheres[i];
+    const double e = std::fmax(std::fabs(s.center[0]), std::fmax(std::fabs(s.center[1]), std::fabs(s.center[2]))) +
+                     std::fabs(s.radius);
+    ext = e > ext || e != e ? e : ext;  // (a NaN stays: no ray is then in the domain)
+    if (ext != ext) break;
+  }
+  ctx->cast_extent = ext;
   ctx->have_scene = true;
   return YK_OK;
 }

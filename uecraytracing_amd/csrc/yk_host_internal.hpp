@@ -3,7 +3,7 @@
 // ykgpu_film, ykgpu_group) and the host functions that cross units (namespace ykhost).  Not part of
 // the C-ABI, not installed.  Who defines what: yk_context.hip the error slot and the statistics,
 // yk_pipeline.hip the parameter checks, the tile helpers, the processing order and launch(),
-// yk_film.hip film_ready, yk_features.hip the feature pass.
+// yk_film.hip film_ready, yk_features.hip the feature pass, yk_cast.hpp the ray queries.
 #ifndef YK_HOST_INTERNAL_HPP
 #define YK_HOST_INTERNAL_HPP
 
@@ -42,6 +42,7 @@ struct DevTree {
   uint32_t* leaf_ids = nullptr;  // leaf slot → tuple index
   int32_t root = 0;              // root code (byte offset of the root node, or a leaf code)
   uint32_t depth = 0, n_nodes = 0;
+  uint32_t wide_depth = 0;  // inner wide nodes on the longest root-to-leaf path
   double origin_bound = 0;  // |o|_inf beyond which a ray takes the linear scan (< 0: every ray)
   uint32_t geo_off = 0, ids_off = 0;  // leaf geometry and ids in LDS, after the nodes
   size_t bytes = 0;                   // device bytes of nodes, leaf geometry and ids
@@ -63,6 +64,10 @@ struct DevTree {
     bytes = 0;
   }
 };
+
+// counters of a synchronous ray query (yk_cast.hpp): rays, hits, out of domain, scan rays, node
+// visits, sphere tests (8 words), in kCastStripes copies that the waves spread their atomics over
+constexpr int kCastCounters = 8, kCastStripes = 64;
 
 struct ykgpu_context {
   int device = 0;
@@ -139,6 +144,16 @@ struct ykgpu_context {
   uint32_t* d_trace_counts = nullptr;
   uint32_t trace_cap = 0;
   std::chrono::steady_clock::time_point t0;
+  // Ray queries (yk_cast.hpp): E = max_i(max |c_k| + |r|) of the scene (the domain rule of
+  // include/ykgpu.h "ray queries"), the synchronous call's staging buffers (cast_cap rays and as
+  // many hits), its counters and statistics, and the event after the last asynchronous cast
+  double cast_extent = 0;
+  void* d_cast_rays = nullptr;
+  void* d_cast_hits = nullptr;
+  size_t cast_cap = 0;
+  unsigned long long* d_cast_counters = nullptr;
+  hipEvent_t cast_ev = nullptr;
+  yk_cast_stats cast_stats{};
 };
 
 // A film (include/ykgpu.h): the accumulation state of one tile, owned by the film — the six planes

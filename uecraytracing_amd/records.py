@@ -220,6 +220,64 @@ class GuidedStats(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+HIT_HIT = 1  # yk_hit.flags (include/ykgpu.h "ray queries")
+HIT_FRONT_FACE = 2
+HIT_OUT_OF_DOMAIN = 4
+CAST_ANY_HIT = 1  # ykgpu_cast_rays' flags
+CAST_LINEAR_SCAN = 2
+CAST_COUNT_WORK = 4
+NO_HIT_ID = 0xFFFFFFFF
+
+
+class Ray(ctypes.Structure):
+    """yk_ray (include/ykgpu.h "ray queries"): origin, direction and the limits of one ray."""
+    _fields_ = [
+        ("origin", D3),
+        ("direction", D3),
+        ("t_min", ctypes.c_double),
+        ("t_max", ctypes.c_double),  # may be +inf
+    ]
+
+
+class Hit(ctypes.Structure):
+    """yk_hit (include/ykgpu.h): the hit_record of one ray, the sphere's tuple index and HIT_* flags."""
+    _fields_ = [
+        ("p", D3),
+        ("normal", D3),
+        ("t", ctypes.c_double),
+        ("id", ctypes.c_uint32),  # NO_HIT_ID when none
+        ("flags", ctypes.c_uint32),
+    ]
+
+
+class CastStats(ctypes.Structure):
+    """yk_cast_stats (include/ykgpu.h): what the last synchronous ykgpu_cast_rays did."""
+    _fields_ = [
+        ("kernel_ms", ctypes.c_double),
+        ("total_ms", ctypes.c_double),
+        ("rays", ctypes.c_uint64),
+        ("hits", ctypes.c_uint64),
+        ("out_of_domain", ctypes.c_uint64),
+        ("scan_rays", ctypes.c_uint64),  # rays served by the ordered scan
+        ("node_visits", ctypes.c_uint64),  # CAST_COUNT_WORK only, else 0
+        ("sphere_tests", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+def _np_dtype(names, formats, itemsize):
+    import numpy as np
+    return np.dtype({"names": names, "formats": formats, "itemsize": itemsize})
+
+
+# numpy views of yk_ray and yk_hit: arrays of these dtypes are the C records, byte for byte
+RAY_DTYPE = _np_dtype(["origin", "direction", "t_min", "t_max"], [("<f8", 3), ("<f8", 3), "<f8", "<f8"], 64)
+HIT_DTYPE = _np_dtype(["p", "normal", "t", "id", "flags"], [("<f8", 3), ("<f8", 3), "<f8", "<u4", "<u4"], 64)
+
+assert ctypes.sizeof(Ray) == 64 and ctypes.sizeof(Hit) == 64 and ctypes.sizeof(CastStats) == 64
+assert RAY_DTYPE.itemsize == 64 and HIT_DTYPE.itemsize == 64
 assert ctypes.sizeof(Sphere) == 80
 assert ctypes.sizeof(FeatureParams) == 48
 assert ctypes.sizeof(GuidedStats) == 32
