@@ -56,7 +56,8 @@ template <class T, class A>
 constexpr vec3<T, A> operator/(const vec3<T, A>& v, T s) { return {v.x / s, v.y / s, v.z / s}; }
 
 // ---- rays and hit records (reference: yk/ray.hpp:11-20, yk/hittable.hpp:16-22): the data members
-// the bridge's renderer::hit reads and fills; the arithmetic runs on the GPU ------------------
+// the bridge's renderer::hit reads and fills and renderer::ray_color reads; the arithmetic runs on
+// the GPU --------------------------------------------------------------------------------------
 template <class T>
 struct ray {
   pos3<T, world_tag> origin;

@@ -520,6 +520,36 @@ class renderer {
     return recs;
   }
 
+  // raytracer::ray_color(ray, world, depth, gen) (raytracer.hpp:19-37) against the scene last set, with
+  // gen = Engine(seed) after discard(skip): the colour the ray carries (include/ykgpu.h "radiance
+  // queries": double, bit for bit; the engine and t_min are the options').  A ray outside the query's
+  // domain is reported as an error, as by hit().  One context only.
+  template <class Ray>
+  yk::color3d ray_color(const Ray& ray, uint32_t depth, uint32_t seed, uint32_t skip = 0,
+                        const render_options& o = render_options{}) {
+    yk_path_ray in{};
+    detail::put3(in.origin, ray.origin);
+    detail::put3(in.direction, ray.direction);
+    in.seed = seed;
+    in.skip = skip;
+    const yk_radiance r = radiance(std::vector<yk_path_ray>{in}, depth, o)[0];
+    if (r.flags & YK_RAD_OUT_OF_DOMAIN) throw error(YK_ERR_INVALID, "ray_color: the ray is outside the query's domain");
+    return {r.colour[0], r.colour[1], r.colour[2]};
+  }
+
+  // ... and the whole records of a batch of path rays (yk_camera_sample_ray makes a render's)
+  std::vector<yk_radiance> radiance(const std::vector<yk_path_ray>& rays, uint32_t max_depth,
+                                    const render_options& o = render_options{}) {
+    if (!ctx_ || group_) throw error(YK_ERR_UNSUPPORTED, "radiance queries belong to one context: not a device group");
+    yk_radiance_params p{};
+    p.max_depth = max_depth;
+    p.rng = o.rng;
+    p.t_min = o.t_min;
+    std::vector<yk_radiance> out(rays.size());
+    check(ykgpu_radiance_rays(ctx_, &p, rays.data(), rays.size(), out.data()), "ykgpu_radiance_rays");
+    return out;
+  }
+
   // the last render's statistics (a group: the whole call, include/ykgpu.h)
   yk_render_stats stats() {
     yk_render_stats s;

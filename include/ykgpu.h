@@ -649,6 +649,113 @@ int ykgpu_cast_rays_async(ykgpu_context* ctx, const void* rays_device, uint64_t 
                           void* hits_device, void* stream);
 int ykgpu_cast_get_stats(ykgpu_context* ctx, yk_cast_stats* out); /* the last synchronous cast */
 
+/* ---- radiance queries (ABI 11) --------------------------------------------
+ * The reference's third public call, raytracer<double,double>::ray_color(ray, world, depth, gen)
+ * (raytracer.hpp:19-37), for batches of arbitrary rays against the scene of the last
+ * ykgpu_set_scene: the colour a ray carries, bit for bit.  FP64 only: ray_color with T = float and
+ * device groups are out of scope (a group's contexts can be queried one by one).
+ *
+ * MEANING.  For a ray in the domain the record is ray_color(ray, world, max_depth, gen) with
+ * gen = Engine(seed) after gen.discard(skip) (Engine: mt19937 or xor128, yk_radiance_params.rng):
+ *   - every segment is world.hit(r, t_min, +inf) exactly as the ray queries above define it;
+ *   - a hit scatters by its sphere's material: lambertian (normal + random_unit_vector, the normal
+ *     alone when near_zero), metal (reflect(normalized(d), n), plus fuzz * random_in_unit_sphere whose
+ *     length factor uniform(0.01, 0.99) is drawn BEFORE its vector; absorbed unless dot(dir, n) > 0),
+ *     dielectric (Schlick; the reflect-or-refract uniform is drawn only when refraction is possible);
+ *   - a miss returns the sky: t = (normalized(d).y + 1.0) / 2, (1 - t) * 1 + t * (0.5, 0.7, 1.0);
+ *   - depth 0 and an absorbed ray return (0, 0, 0);
+ *   - the product a_1 * (a_2 * (... * L)) is multiplied back to front, so zeros keep their sign;
+ *   - every + - * / is one IEEE double operation, never fused; square roots are math::sqrt.
+ * colour is ray_color's value; t_first the first segment's root (+0.0 without a hit); id_first and
+ * id_last the tuple index of the first and the last sphere hit (0xFFFFFFFF without); words the
+ * engine words the reference's engine has produced when ray_color returns, skip included; segments
+ * the ray_color calls that ran a closest hit; flags how the path ended (one of YK_RAD_SKY,
+ * YK_RAD_ABSORBED, YK_RAD_DEPTH, YK_RAD_OUT_OF_DOMAIN) and YK_RAD_MT_FALLBACK when an mt19937 path
+ * drew more than 227 words (it then ran the full 624-word engine: a cost, not a difference).
+ * A record depends on its ray and the scene alone, never on the batch or the ray's place in it.
+ * skip costs one draw per word.
+ *
+ * DOMAIN.  The start ray must pass the ray queries' domain rule with its t_max = +inf.  A ray that
+ * does not does no arithmetic: doubles +0.0, both ids 0xFFFFFFFF, flags YK_RAD_OUT_OF_DOMAIN,
+ * words = segments = 0.  Every later segment's ray is put through the same test before its hit; a
+ * path that leaves the domain ends there with colour +0.0 and flags YK_RAD_OUT_OF_DOMAIN (|
+ * YK_RAD_MT_FALLBACK), the other fields as they stood (DESIGN.md 6.6 on why this is believed never
+ * to happen: after the first hit origins lie on spheres and directions have length O(1)).
+ *
+ * YK_RADIANCE_LINEAR_SCAN serves every segment by the ordered scan (same bytes);
+ * YK_RADIANCE_COUNT_WORK also counts segments, words and scan segments in the statistics.
+ *
+ * ykgpu_radiance_rays is synchronous: it stages rays and records through device buffers the context
+ * owns, in chunks of at most 2^22 rays, and records yk_radiance_stats.  ykgpu_radiance_rays_async
+ * launches on `stream` (NULL: the context's), reads n yk_path_ray at rays_device and writes n
+ * yk_radiance at out_device (both 16-byte aligned device memory); it neither synchronises nor
+ * records statistics.  A context's queries run one after the other, whatever their streams (they
+ * share the per-lane engine and attenuation scratch, which is sized by the resident lanes and
+ * max_depth, never by n, allocated at the first query, counted in yk_render_stats.device_bytes and
+ * released with the context).  ykgpu_set_scene waits for the context's queries.  Films, the rings
+ * and the render streams are untouched.
+ *   n == 0               YK_OK, nothing done
+ *   YK_ERR_INVALID       a null pointer; unknown flag bits; max_depth outside 1..65535; t_min not
+ *                        finite and >= 0; non-zero reserved fields of the params
+ *   YK_ERR_NO_SCENE      a call before ykgpu_set_scene
+ *   YK_ERR_UNSUPPORTED   an unknown rng */
+typedef struct yk_path_ray {       /* 64 bytes */
+  double origin[3], direction[3];
+  uint32_t seed;                   /* the path's engine is Engine(seed) */
+  uint32_t skip;                   /* engine words discarded before ray_color's first draw (mt19937::discard) */
+  uint64_t reserved;               /* 0 */
+} yk_path_ray;
+
+typedef struct yk_radiance {       /* 64 bytes */
+  double colour[3];                /* ray_color's return value */
+  double t_first;                  /* t of the first segment's hit, +0.0 if none */
+  uint32_t id_first, id_last;      /* tuple index of the first / last sphere hit, 0xFFFFFFFF if none */
+  uint32_t words;                  /* engine words consumed, skip included */
+  uint32_t segments;               /* ray_color calls that ran a closest hit */
+  uint32_t flags;                  /* YK_RAD_* : how the path ended */
+  uint32_t reserved[3];            /* 0 */
+} yk_radiance;
+enum { YK_RAD_SKY = 1u, YK_RAD_ABSORBED = 2u, YK_RAD_DEPTH = 4u, YK_RAD_OUT_OF_DOMAIN = 8u, YK_RAD_MT_FALLBACK = 16u };
+enum { YK_RADIANCE_LINEAR_SCAN = 1u, YK_RADIANCE_COUNT_WORK = 2u };
+
+typedef struct yk_radiance_params { /* 32 bytes */
+  uint32_t max_depth;              /* 1 .. 65535; ray_color's depth argument */
+  uint32_t rng;                    /* YK_RNG_MT19937 | YK_RNG_XOR128 */
+  uint32_t flags;                  /* YK_RADIANCE_* */
+  uint32_t reserved;
+  double t_min;                    /* 0.001 in the reference; finite, >= 0 */
+  uint64_t reserved1;
+} yk_radiance_params;
+
+typedef struct yk_radiance_stats { /* 64 bytes */
+  double kernel_ms, total_ms;      /* device time of the kernels; the call's host wall clock */
+  double starts_ms;                /* the part of kernel_ms in the starts kernel (mt19937's seed walks) */
+  uint64_t rays;
+  uint64_t segments, words;        /* YK_RADIANCE_COUNT_WORK only, else 0 */
+  uint32_t out_of_domain;          /* rays with YK_RAD_OUT_OF_DOMAIN (32-bit counts stop at 0xFFFFFFFF) */
+  uint32_t mt_fallbacks;           /* rays with YK_RAD_MT_FALLBACK */
+  uint32_t scan_segments;          /* segments served by the ordered scan (YK_RADIANCE_COUNT_WORK only) */
+  uint32_t lanes;                  /* resident lanes of the path kernel's grid */
+} yk_radiance_stats;
+
+int ykgpu_radiance_rays(ykgpu_context* ctx, const yk_radiance_params* params, const yk_path_ray* rays_host,
+                        uint64_t n, yk_radiance* out_host);
+int ykgpu_radiance_rays_async(ykgpu_context* ctx, const yk_radiance_params* params, const void* rays_device,
+                              uint64_t n, void* out_device, void* stream);
+int ykgpu_radiance_get_stats(ykgpu_context* ctx, yk_radiance_stats* out); /* the last synchronous query */
+
+/* The ray, seed and skip with which render() enters ray_color for sample s of pixel (y, x) of the
+ * image `params` names (host only, FP64, both engines): the counter or keyed seed, the two jitter
+ * canonicals, the thin lens' rejection loop and get_ray, in the reference's operation order
+ * (source.cpp:154-164, camera.hpp:29-32).  ykgpu_radiance_rays on a pixel's samples_per_pixel sample
+ * rays with params' max_depth, t_min and rng, added up in sample order from +0.0, is that pixel of
+ * ykgpu_render_sums. */
+int yk_camera_sample_ray(const yk_camera* camera, const yk_render_params* params, uint32_t y, uint32_t x,
+                         uint32_t s, yk_path_ray* out);
+/* ... for n samples (ys[i], xs[i], ss[i]) into out[i]; returns the first sample's error, if any */
+int yk_camera_sample_rays(const yk_camera* camera, const yk_render_params* params, const uint32_t* ys,
+                          const uint32_t* xs, const uint32_t* ss, uint64_t n, yk_path_ray* out);
+
 /* ---- host-side scene helpers (no device needed) ---------------------------------------- */
 
 /* camera<double>{} of camera.hpp:16-27 (16:9, viewport height 2, focal length 1, origin 0). */

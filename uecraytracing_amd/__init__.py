@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 from . import records
-from .records import CastStats, Hit, Ray, Camera, DenoiseParams, DenoiseStats, FeatureParams, FilmPass, GuidedStats, FilmStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
+from .records import CastStats, Hit, Ray, PathRay, RadianceParams, RadianceStats, Camera, DenoiseParams, DenoiseStats, FeatureParams, FilmPass, GuidedStats, FilmStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(PKG_DIR, "lib")
@@ -39,6 +39,8 @@ EXPORTS = (
     "yk_denoise_defaults", "ykgpu_film_denoise",
     "yk_guided_defaults", "ykgpu_film_features", "ykgpu_film_denoise_guided",
     "ykgpu_cast_rays", "ykgpu_cast_rays_async", "ykgpu_cast_get_stats",
+    "ykgpu_radiance_rays", "ykgpu_radiance_rays_async", "ykgpu_radiance_get_stats", "yk_camera_sample_ray",
+    "yk_camera_sample_rays",
 )
 ABI_VERSION = 11
 SCENE_DIR = os.path.join(PKG_DIR, "scenes")  # committed scene files of the BASELINE configs
@@ -129,6 +131,13 @@ def load_library():
         "ykgpu_cast_rays": ([c.c_void_p, c.c_void_p, c.c_uint64, c.c_uint32, c.c_void_p], c.c_int),
         "ykgpu_cast_rays_async": ([c.c_void_p, c.c_void_p, c.c_uint64, c.c_uint32, c.c_void_p, c.c_void_p], c.c_int),
         "ykgpu_cast_get_stats": ([c.c_void_p, P(CastStats)], c.c_int),
+        "ykgpu_radiance_rays": ([c.c_void_p, P(RadianceParams), c.c_void_p, c.c_uint64, c.c_void_p], c.c_int),
+        "ykgpu_radiance_rays_async": ([c.c_void_p, P(RadianceParams), c.c_void_p, c.c_uint64, c.c_void_p, c.c_void_p],
+                                      c.c_int),
+        "ykgpu_radiance_get_stats": ([c.c_void_p, P(RadianceStats)], c.c_int),
+        "yk_camera_sample_ray": ([P(Camera), P(RenderParams), c.c_uint32, c.c_uint32, c.c_uint32, c.c_void_p], c.c_int),
+        "yk_camera_sample_rays": ([P(Camera), P(RenderParams), c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64,
+                                   c.c_void_p], c.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
@@ -263,6 +272,24 @@ def guided_defaults():
     dp, fp = DenoiseParams(), FeatureParams()
     _check(load_library().yk_guided_defaults(ctypes.byref(dp), ctypes.byref(fp)))
     return dp, fp
+
+
+def camera_sample_rays(camera: Camera, params: RenderParams, ys, xs, ss) -> np.ndarray:
+    """yk_camera_sample_ray (host only) over arrays: records.PATH_RAY_DTYPE[N], the ray, seed and skip
+    with which render() enters ray_color for sample ss[i] of pixel (ys[i], xs[i]) of the image
+    `params` names.  Renderer.radiance on a pixel's samples, added up in sample order, is that pixel
+    of Renderer.render_sums."""
+    lib = load_library()
+    ys, xs, ss = np.broadcast_arrays(np.asarray(ys, np.int64), np.asarray(xs, np.int64), np.asarray(ss, np.int64))
+    if ys.size and (min(ys.min(), xs.min(), ss.min()) < 0 or max(ys.max(), xs.max(), ss.max()) > 0xFFFFFFFF):
+        raise YkError("camera_sample_rays: indices must fit uint32")
+    ys, xs, ss = (np.ascontiguousarray(a.ravel(), dtype=np.uint32) for a in (ys, xs, ss))
+    out = np.zeros(ys.size, records.PATH_RAY_DTYPE)
+    rc = lib.yk_camera_sample_rays(ctypes.byref(camera), ctypes.byref(params), ys.ctypes.data, xs.ctypes.data,
+                                   ss.ctypes.data, ys.size, out.ctypes.data)
+    if rc != 0:
+        raise YkError(f"{records.ERRORS.get(rc, rc)}: camera_sample_rays: a sample outside the image, or fp32")
+    return out
 
 
 class Film:
@@ -584,6 +611,55 @@ class Renderer:
         _check(self._lib.ykgpu_cast_get_stats(self._ctx, ctypes.byref(st)))
         return st.as_dict()
 
+    @staticmethod
+    def _radiance_params(max_depth, t_min, rng, linear_scan, count_work) -> RadianceParams:
+        flags = (records.RADIANCE_LINEAR_SCAN if linear_scan else 0) | (records.RADIANCE_COUNT_WORK if count_work else 0)
+        return RadianceParams(max_depth, rng, flags, 0, t_min, 0)
+
+    def radiance(self, origins, directions, seeds, skip=0, max_depth=50, t_min=records.T_MIN,
+                 rng=records.RNG_MT19937, linear_scan: bool = False, count_work: bool = False) -> np.ndarray:
+        """The reference's ray_color for N rays (include/ykgpu.h "radiance queries"): origins and
+        directions float64[N, 3], seeds and skip scalars or uint32[N] (the path's engine is
+        Engine(seed) with skip words discarded).  Returns records.RADIANCE_DTYPE[N]: colour, t_first,
+        id_first, id_last, words, segments and flags (records.RAD_*)."""
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise YkError("radiance: origins and directions must both be [N, 3]")
+        rays = np.zeros(o.shape[0], records.PATH_RAY_DTYPE)
+        rays["origin"], rays["direction"] = o, d
+        rays["seed"] = np.broadcast_to(np.asarray(seeds, np.uint32), (len(rays),))
+        rays["skip"] = np.broadcast_to(np.asarray(skip, np.uint32), (len(rays),))
+        return self.radiance_rays(rays, max_depth, t_min, rng, linear_scan, count_work)
+
+    def radiance_rays(self, rays, max_depth=50, t_min=records.T_MIN, rng=records.RNG_MT19937,
+                      linear_scan: bool = False, count_work: bool = False) -> np.ndarray:
+        """radiance() on records.PATH_RAY_DTYPE[N] (camera_sample_rays' output, for one)."""
+        rays = np.ascontiguousarray(rays, dtype=records.PATH_RAY_DTYPE)
+        n = rays.size
+        out = np.zeros(n, records.RADIANCE_DTYPE)
+        par = self._radiance_params(max_depth, t_min, rng, linear_scan, count_work)
+        _check(self._lib.ykgpu_radiance_rays(self._ctx, ctypes.byref(par), rays.ctypes.data if n else None, n,
+                                             out.ctypes.data if n else None))
+        return out
+
+    def radiance_device(self, rays_ptr: int, n: int, out_ptr: int, max_depth=50, t_min=records.T_MIN,
+                        rng=records.RNG_MT19937, linear_scan: bool = False, count_work: bool = False,
+                        stream_ptr: int = 0):
+        """Enqueue a radiance query over device memory (ykgpu_radiance_rays_async): n yk_path_ray
+        records at rays_ptr, n yk_radiance records written at out_ptr (e.g. [N, 64] uint8 or [N, 8]
+        float64 CUDA tensors' data_ptr()), on the stream (0: the context's).  Does not synchronise."""
+        par = self._radiance_params(max_depth, t_min, rng, linear_scan, count_work)
+        _check(self._lib.ykgpu_radiance_rays_async(self._ctx, ctypes.byref(par), ctypes.c_void_p(rays_ptr or None), n,
+                                                   ctypes.c_void_p(out_ptr or None),
+                                                   ctypes.c_void_p(stream_ptr or None)))
+
+    def radiance_stats(self) -> dict:
+        """yk_radiance_stats of the last synchronous radiance()."""
+        st = RadianceStats()
+        _check(self._lib.ykgpu_radiance_get_stats(self._ctx, ctypes.byref(st)))
+        return st.as_dict()
+
 
 class Group:
     """Several device contexts in one process (ykgpu_group): rows dealt cyclically over the
@@ -644,5 +720,5 @@ def render_devices(devices, spheres, camera: Camera, params: RenderParams) -> np
     return out
 
 
-__all__ = ["Renderer", "Film", "Ray", "Hit", "CastStats", "FilmPass", "DenoiseParams", "DenoiseStats", "denoise_defaults", "FeatureParams", "GuidedStats", "guided_defaults", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
+__all__ = ["Renderer", "Film", "Ray", "Hit", "CastStats", "PathRay", "RadianceParams", "RadianceStats", "camera_sample_rays", "FilmPass", "DenoiseParams", "DenoiseStats", "denoise_defaults", "FeatureParams", "GuidedStats", "guided_defaults", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
            "make_params", "load_library", "records", "EXPORTS", "LIB_PATH", "CLI_PATH"]

@@ -18,7 +18,8 @@
 //
 // Added (render parameters are compile-time macros in the reference): --width, --spp,
 // --depth, --scene, --scene-seed, --scene-file, --save-scene, --seed0, --precision, --rng,
-// --device, --stats, the progressive film's --progressive, --until, --checkpoint, --stop-after
+// --device, --stats, --pick and --probe (one ray query / one pixel's radiance queries instead of a
+// render), the progressive film's --progressive, --until, --checkpoint, --stop-after
 // (include/ykgpu.h "progressive film": the image in chunks of samples, the same bytes as in one
 // call), and --denoise with --denoise-radius, --denoise-patch, --denoise-k2 (include/ykgpu.h "film
 // denoise": the final image and every preview through the film's variance-guided filter),
@@ -111,7 +112,13 @@ const char* kHelp =
     "                            (column, row from the top) at the render's t_min, print\n"
     "                            'pick X Y: id <n> t <t> p (<x>, <y>, <z>) normal (<x>, <y>, <z>)\n"
     "                            front <0|1>' (%.17g) or 'pick X Y: miss', and exit without\n"
-    "                            rendering (no output file needed)\n";
+    "                            rendering (no output file needed)\n"
+    "      --probe arg           arg = X,Y: run the --spp samples of image pixel (X, Y) one by one\n"
+    "                            through the radiance query instead of rendering; per sample\n"
+    "                            'sample <s>: colour (<r>, <g>, <b>) words <n> segments <n> end <how>'\n"
+    "                            (%.17g; how: sky|absorbed|depth|out-of-domain), then 'sum (...)',\n"
+    "                            the samples added in order, and 'rgb <r> <g> <b>', the pixel of the\n"
+    "                            image (fp64 only, needs --seed0; no output file needed)\n";
 
 struct args {
   bool help = false, verbose_flag = false, stats = false;
@@ -142,6 +149,9 @@ struct args {
   // --pick X,Y: one ray query instead of a render
   bool have_pick = false;
   uint32_t pick_x = 0, pick_y = 0;
+  // --probe X,Y: the pixel's samples through the radiance query instead of a render
+  bool have_probe = false;
+  uint32_t probe_x = 0, probe_y = 0;
   bool film() const { return denoise || !aov.empty() || adaptive || have_progressive || have_until || have_stop_after || !checkpoint.empty(); }
 };
 
@@ -239,6 +249,14 @@ args parse(int argc, char** argv) {
         a.pick_y = to_u32(n, v.substr(c + 1));
         a.have_pick = true;
       }
+      else if (n == "probe") {
+        const std::string v = value(i, n, inl);
+        const size_t c = v.find(',');
+        if (c == std::string::npos) throw option_error{"Option 'probe' needs X,Y"};
+        a.probe_x = to_u32(n, v.substr(0, c));
+        a.probe_y = to_u32(n, v.substr(c + 1));
+        a.have_probe = true;
+      }
       else if (n == "checkpoint") {
         a.checkpoint = value(i, n, inl);
         if (a.checkpoint.empty()) throw option_error{"Option 'checkpoint' needs a file name"};
@@ -265,6 +283,10 @@ args parse(int argc, char** argv) {
     }
   }
   if (a.adaptive && !a.have_until) throw option_error{"Option 'adaptive' needs --until"};
+  if (a.have_probe && a.have_pick) throw option_error{"Options 'probe' and 'pick' exclude each other"};
+  if (a.have_probe && !a.have_seed0) throw option_error{"Option 'probe' needs --seed0 (the samples it repeats)"};
+  if (a.have_probe && a.precision != "fp64") throw option_error{"Option 'probe' is fp64 only"};
+  if (a.have_probe && !a.spp) throw option_error{"Option 'probe' needs --spp of at least 1"};
   if (a.have_denoise_params && !a.denoise) throw option_error{"The denoise parameters need --denoise"};
   if (a.have_feature_grid && !a.denoise_features && a.aov.empty())
     throw option_error{"Option 'feature-grid' needs --denoise-features or --aov"};
@@ -292,7 +314,7 @@ int main(int argc, char* argv[]) {
     std::cerr << "raytrace: " << e.what << " (see --help)" << std::endl;
     return 2;
   }
-  if (a.help || (!a.have_output && !a.have_pick)) {
+  if (a.help || (!a.have_output && !a.have_pick && !a.have_probe)) {
     std::cout << kHelp << std::endl;
     std::exit(EXIT_SUCCESS);
   }
@@ -303,6 +325,11 @@ int main(int argc, char* argv[]) {
   const uint32_t W = a.width, H = yk_image_height_for(W);
   if (a.have_pick && (a.pick_x >= W || a.pick_y >= H)) {
     std::cerr << "raytrace: Option 'pick' names a pixel outside the " << W << " x " << H << " image (see --help)"
+              << std::endl;
+    return 2;
+  }
+  if (a.have_probe && (a.probe_x >= W || a.probe_y >= H)) {
+    std::cerr << "raytrace: Option 'probe' names a pixel outside the " << W << " x " << H << " image (see --help)"
               << std::endl;
     return 2;
   }
@@ -383,6 +410,38 @@ int main(int argc, char* argv[]) {
                     a.pick_x, a.pick_y, rec->id, rec->t, rec->p.x, rec->p.y, rec->p.z, rec->normal.x, rec->normal.y,
                     rec->normal.z, rec->front_face ? 1 : 0);
       }
+      return EXIT_SUCCESS;
+    }
+    if (a.have_probe) {
+      // every sample of the pixel as render() starts it (yk_camera_sample_ray), through ray_color
+      const yk_render_params p = ykgpu::renderer::params(W, H, a.spp, a.depth, seed0, ro);
+      std::vector<yk_path_ray> rays(a.spp);
+      for (uint32_t s = 0; s < a.spp; ++s)
+        if (yk_camera_sample_ray(&gpu.camera(), &p, a.probe_y, a.probe_x, s, &rays[s]) != YK_OK)
+          throw ykgpu::error(YK_ERR_INVALID, "yk_camera_sample_ray");
+      const std::vector<yk_radiance> recs = gpu.radiance(rays, a.depth, ro);
+      double sum[3] = {0.0, 0.0, 0.0};
+      for (uint32_t s = 0; s < a.spp; ++s) {
+        const yk_radiance& r = recs[s];
+        const char* how = (r.flags & YK_RAD_SKY) ? "sky" : (r.flags & YK_RAD_ABSORBED) ? "absorbed"
+                          : (r.flags & YK_RAD_DEPTH) ? "depth" : "out-of-domain";
+        std::printf("sample %u: colour (%.17g, %.17g, %.17g) words %u segments %u end %s\n", s, r.colour[0], r.colour[1],
+                    r.colour[2], r.words, r.segments, how);
+        for (int c = 0; c < 3; ++c) sum[c] = sum[c] + r.colour[c];  // transform_reduce's order (source.cpp:137-167)
+      }
+      // to_color3b (source.cpp:73-83): math::sqrt (math.hpp:10-19) of the mean, clamped, times 256
+      uint32_t rgb[3];
+      for (int c = 0; c < 3; ++c) {
+        const double m = sum[c] / a.spp;
+        double x = m / 2.0, prev = 0.0;
+        for (int guard = 0; x != prev && guard < 4096; ++guard) {
+          prev = x;
+          x = (x + m / x) / 2.0;
+        }
+        x = (x < 0.0) ? 0.0 : (0.999 < x) ? 0.999 : x;
+        rgb[c] = (uint8_t)(x * 256);
+      }
+      std::printf("sum (%.17g, %.17g, %.17g)\nrgb %u %u %u\n", sum[0], sum[1], sum[2], rgb[0], rgb[1], rgb[2]);
       return EXIT_SUCCESS;
     }
     std::cout << "rendering..." << std::endl;

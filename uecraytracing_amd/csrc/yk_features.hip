@@ -2,8 +2,8 @@
 // first-hit albedo, normal and depth of every pixel of a film's tile, defined operation by operation
 // in IEEE double so that numpy restates it bit for bit (tests/film_features_ref.py).
 //
-// A unit of its own, like yk_denoise.hip (it also holds the ray queries, yk_cast.hpp, included at
-// the end).  One kernel, yk_film_features, on the context's stream;
+// A unit of its own, like yk_denoise.hip (it also holds the ray queries, yk_cast.hpp, and the
+// radiance queries, yk_radiance.hpp, included at the end).  One kernel, yk_film_features, on the context's stream;
 // its result lives in planes the film owns (ykgpu_film, yk_host_internal.hpp) and is computed once
 // per (film, grid).
 #include <hip/hip_runtime.h>
@@ -267,3 +267,5 @@ int ykgpu_film_features(ykgpu_film* film, uint32_t grid, double* mean_host, doub
 
 // the ray queries (ykgpu_cast_rays ...): the unit's other first-hit query, in a file of its own
 #include "yk_cast.hpp"
+// ... and the radiance queries (ykgpu_radiance_rays ...), whose closest hit is the cast's
+#include "yk_radiance.hpp"

@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/ykgpu.h"
@@ -233,6 +234,80 @@ uint32_t yk_schedule_plan(uint32_t nps, uint32_t spp, uint32_t s_begin, uint64_t
 }
 
 }  // extern "C"
+
+// ---- the start of a camera sample (include/ykgpu.h "radiance queries") --------------------
+namespace {
+// a sample's engine on the host, counting its words: mt19937 (scene_rng is one) or yk::xor128
+// (random.hpp:18-41: x, y, z at their defaults, w = 88675123 ^ seed)
+struct sample_rng {
+  scene_rng mt;
+  uint32_t xs[4];
+  bool x128;
+  uint32_t words = 0;
+  sample_rng(uint32_t seed, bool xor128) : mt(xor128 ? 0u : seed), xs{123456789u, 362436069u, 521288629u, 88675123u ^ seed}, x128(xor128) {}
+  uint32_t next() {
+    ++words;
+    if (!x128) return mt.next();
+    const uint32_t t = xs[0] ^ (xs[0] << 11);
+    xs[0] = xs[1], xs[1] = xs[2], xs[2] = xs[3];
+    return xs[3] = (xs[3] ^ (xs[3] >> 19)) ^ (t ^ (t >> 8));
+  }
+  // generate_canonical<double, 53> (random.hpp:161-183) and uniform_real_distribution (:273-278)
+  double canonical() {
+    double s = (double)next();
+    s = s + (double)next() * 4294967296.0;
+    const double r = s / 18446744073709551616.0;
+    return r >= 1.0 ? 1.0 - 0x1p-53 : r;
+  }
+  double uniform(double a, double b) { return (canonical() * (b - a)) + a; }
+};
+d3 operator+(d3 a, d3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+d3 of(const double* p) { return {p[0], p[1], p[2]}; }
+}  // namespace
+
+extern "C" int yk_camera_sample_ray(const yk_camera* cam, const yk_render_params* p, uint32_t y, uint32_t x, uint32_t s,
+                                    yk_path_ray* out) {
+  if (!cam || !p || !out) return YK_ERR_INVALID;
+  if (y >= p->image_height || x >= p->image_width || s >= p->samples_per_pixel) return YK_ERR_INVALID;
+  if (p->precision != YK_PRECISION_FP64) return YK_ERR_UNSUPPORTED;
+  if (p->rng != YK_RNG_MT19937 && p->rng != YK_RNG_XOR128) return YK_ERR_UNSUPPORTED;
+  if (p->seed_mode != YK_SEED_COUNTER && p->seed_mode != YK_SEED_RANDOM_DEVICE) return YK_ERR_INVALID;
+  // the sample's seed: source.cpp:154-158 in uint32 arithmetic, or the call's key hashed with the
+  // sample's 64-bit linear index (YK_SEED_RANDOM_DEVICE: splitmix64's finaliser, high word)
+  uint32_t seed = p->seed0 + (y * p->image_width + x) * p->samples_per_pixel + s;
+  if (p->seed_mode == YK_SEED_RANDOM_DEVICE) {
+    uint64_t z = p->seed_key + ((((uint64_t)y * p->image_width + x) * p->samples_per_pixel + s) + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    seed = (uint32_t)(z >> 32);
+  }
+  sample_rng g(seed, p->rng == YK_RNG_XOR128);
+  // jitter (source.cpp:160-164) and camera::get_ray (camera.hpp:29-32), then the thin lens' point by
+  // rejection (extension)
+  const double u = (x + g.uniform(0, 1)) / p->image_width;
+  const double v = (p->image_height - y - 1 + g.uniform(0, 1)) / p->image_height;
+  d3 org = of(cam->origin);
+  d3 dir = ((of(cam->lower_left_corner) + of(cam->horizontal) * u) + of(cam->vertical) * v) - org;
+  if (cam->lens_radius > 0) {
+    double px, py;
+    for (;;) {
+      px = g.uniform(-1, 1);
+      py = g.uniform(-1, 1);
+      if (px * px + py * py < 1.0) break;
+    }
+    const double rx = px * cam->lens_radius, ry = py * cam->lens_radius;
+    const d3 off = of(cam->lens_u) * rx + of(cam->lens_v) * ry;
+    org = org + off;
+    dir = dir - off;
+  }
+  std::memset(out, 0, sizeof(*out));
+  put(out->origin, org);
+  put(out->direction, dir);
+  out->seed = seed;
+  out->skip = g.words;
+  return YK_OK;
+}
 
 // ---- scene files -------------------------------------------------------------------------
 // Text, one record per line, numbers as %.17g (every double round-trips exactly):
@@ -498,5 +573,26 @@ int yk_film_load_counts(const char* path, yk_render_params* params, uint64_t* sc
   if (!ok) return YK_ERR_INVALID;
   if (params) *params = p;
   if (scene_hash) *scene_hash = h.scene_hash;
+  return YK_OK;
+}
+
+// The same for n samples (ys[i], xs[i], ss[i]) -> out[i]; large batches are split over a few host
+// threads (every record depends on its own sample alone).  The first error of any sample is returned.
+extern "C" int yk_camera_sample_rays(const yk_camera* cam, const yk_render_params* p, const uint32_t* ys,
+                                     const uint32_t* xs, const uint32_t* ss, uint64_t n, yk_path_ray* out) {
+  if (!cam || !p || (n && (!ys || !xs || !ss || !out))) return YK_ERR_INVALID;
+  const unsigned hw = std::thread::hardware_concurrency();
+  const uint64_t nt = n < 65536 ? 1 : std::min<uint64_t>(16, hw ? hw : 1);
+  std::vector<int> rc(nt, YK_OK);
+  auto work = [&](uint64_t t) {
+    for (uint64_t i = n * t / nt; i < n * (t + 1) / nt && rc[t] == YK_OK; ++i)
+      rc[t] = yk_camera_sample_ray(cam, p, ys[i], xs[i], ss[i], &out[i]);
+  };
+  std::vector<std::thread> th;
+  for (uint64_t t = 1; t < nt; ++t) th.emplace_back(work, t);
+  work(0);
+  for (std::thread& t : th) t.join();
+  for (int r : rc)
+    if (r != YK_OK) return r;
   return YK_OK;
 }

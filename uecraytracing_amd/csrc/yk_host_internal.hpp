@@ -3,7 +3,8 @@
 // ykgpu_film, ykgpu_group) and the host functions that cross units (namespace ykhost).  Not part of
 // the C-ABI, not installed.  Who defines what: yk_context.hip the error slot and the statistics,
 // yk_pipeline.hip the parameter checks, the tile helpers, the processing order and launch(),
-// yk_film.hip film_ready, yk_features.hip the feature pass, yk_cast.hpp the ray queries.
+// yk_film.hip film_ready, yk_features.hip the feature pass, yk_cast.hpp the ray queries,
+// yk_radiance.hpp the radiance queries.
 #ifndef YK_HOST_INTERNAL_HPP
 #define YK_HOST_INTERNAL_HPP
 
@@ -68,6 +69,11 @@ struct DevTree {
 // counters of a synchronous ray query (yk_cast.hpp): rays, hits, out of domain, scan rays, node
 // visits, sphere tests (8 words), in kCastStripes copies that the waves spread their atomics over
 constexpr int kCastCounters = 8, kCastStripes = 64;
+// ... and of a synchronous radiance query (yk_radiance.hpp): rays, out of domain, MT fallbacks,
+// segments, words, scan segments, striped the same way; the fixed buffers of a query: the x_397 of
+// a chunk's kRadChunk seeds and the claim counter
+constexpr int kRadCounters = 8, kRadStripes = 64;
+constexpr uint64_t kRadChunk = 1ull << 22;
 
 struct ykgpu_context {
   int device = 0;
@@ -154,6 +160,22 @@ struct ykgpu_context {
   unsigned long long* d_cast_counters = nullptr;
   hipEvent_t cast_ev = nullptr;
   yk_cast_stats cast_stats{};
+  // Radiance queries (yk_radiance.hpp): the synchronous call's staging buffers (rad_cap rays and as
+  // many records), the x_397 of a chunk's seeds, the path kernel's claim counter, its per-lane
+  // scratch (624 engine words and rad_id_stride attenuation ids per resident lane, rad_lanes of
+  // them), the counters and statistics, and the event after the last query (queries of a context
+  // run one after the other: they share the scratch)
+  void* d_rad_rays = nullptr;
+  void* d_rad_out = nullptr;
+  size_t rad_cap = 0;
+  uint32_t* d_rad_x397 = nullptr;
+  uint32_t* d_rad_claim = nullptr;
+  uint32_t* d_rad_mt = nullptr;
+  uint16_t* d_rad_ids = nullptr;
+  size_t rad_lanes = 0, rad_id_stride = 0, rad_mt_lanes = 0;
+  unsigned long long* d_rad_counters = nullptr;
+  hipEvent_t rad_ev = nullptr;
+  yk_radiance_stats rad_stats{};
 };
 
 // A film (include/ykgpu.h): the accumulation state of one tile, owned by the film — the six planes

@@ -276,8 +276,67 @@ def _np_dtype(names, formats, itemsize):
 RAY_DTYPE = _np_dtype(["origin", "direction", "t_min", "t_max"], [("<f8", 3), ("<f8", 3), "<f8", "<f8"], 64)
 HIT_DTYPE = _np_dtype(["p", "normal", "t", "id", "flags"], [("<f8", 3), ("<f8", 3), "<f8", "<u4", "<u4"], 64)
 
+RAD_SKY = 1  # yk_radiance.flags (include/ykgpu.h "radiance queries"): how the path ended
+RAD_ABSORBED = 2
+RAD_DEPTH = 4
+RAD_OUT_OF_DOMAIN = 8
+RAD_MT_FALLBACK = 16  # beside one of the above: the path drew more than 227 mt19937 words
+RADIANCE_LINEAR_SCAN = 1  # yk_radiance_params.flags
+RADIANCE_COUNT_WORK = 2
+
+
+class PathRay(ctypes.Structure):
+    """yk_path_ray (include/ykgpu.h "radiance queries"): a ray and its path's engine (seed, skip)."""
+    _fields_ = [
+        ("origin", D3),
+        ("direction", D3),
+        ("seed", ctypes.c_uint32),
+        ("skip", ctypes.c_uint32),  # engine words discarded before ray_color's first draw
+        ("reserved", ctypes.c_uint64),
+    ]
+
+
+class RadianceParams(ctypes.Structure):
+    """yk_radiance_params (include/ykgpu.h): ray_color's depth, the engine, t_min and RADIANCE_* flags."""
+    _fields_ = [
+        ("max_depth", ctypes.c_uint32),  # 1..65535
+        ("rng", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("t_min", ctypes.c_double),
+        ("reserved1", ctypes.c_uint64),
+    ]
+
+
+class RadianceStats(ctypes.Structure):
+    """yk_radiance_stats (include/ykgpu.h): what the last synchronous ykgpu_radiance_rays did."""
+    _fields_ = [
+        ("kernel_ms", ctypes.c_double),
+        ("total_ms", ctypes.c_double),
+        ("starts_ms", ctypes.c_double),  # the part of kernel_ms in the starts kernel
+        ("rays", ctypes.c_uint64),
+        ("segments", ctypes.c_uint64),  # RADIANCE_COUNT_WORK only, else 0
+        ("words", ctypes.c_uint64),
+        ("out_of_domain", ctypes.c_uint32),
+        ("mt_fallbacks", ctypes.c_uint32),
+        ("scan_segments", ctypes.c_uint32),  # RADIANCE_COUNT_WORK only
+        ("lanes", ctypes.c_uint32),  # resident lanes of the path kernel's grid
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+assert ctypes.sizeof(PathRay) == 64 and ctypes.sizeof(RadianceParams) == 32 and ctypes.sizeof(RadianceStats) == 64
 assert ctypes.sizeof(Ray) == 64 and ctypes.sizeof(Hit) == 64 and ctypes.sizeof(CastStats) == 64
+# ... and of yk_path_ray and yk_radiance
+PATH_RAY_DTYPE = _np_dtype(["origin", "direction", "seed", "skip", "reserved"],
+                           [("<f8", 3), ("<f8", 3), "<u4", "<u4", "<u8"], 64)
+RADIANCE_DTYPE = _np_dtype(["colour", "t_first", "id_first", "id_last", "words", "segments", "flags", "reserved"],
+                           [("<f8", 3), "<f8", "<u4", "<u4", "<u4", "<u4", "<u4", ("<u4", 3)], 64)
 assert RAY_DTYPE.itemsize == 64 and HIT_DTYPE.itemsize == 64
+assert PATH_RAY_DTYPE.itemsize == 64 and RADIANCE_DTYPE.itemsize == 64
+assert RADIANCE_DTYPE.fields["flags"][1] == 48 and PATH_RAY_DTYPE.fields["seed"][1] == 48
 assert ctypes.sizeof(Sphere) == 80
 assert ctypes.sizeof(FeatureParams) == 48
 assert ctypes.sizeof(GuidedStats) == 32
