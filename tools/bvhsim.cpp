@@ -5,8 +5,12 @@
 // traversal on them (float slabs, ordered descent, U* from the hit bound) and prints per-ray
 // visit statistics plus the expected maximum over random groups of 64 rays — the number of
 // loop trips a wave pays in the while-while loop.
-//   build: make -C tools bvhsim      run: tools/bvhsim final 42 [leaf bins]
+//   build: g++ -std=c++17 -O2 -o tools/bvhsim tools/bvhsim.cpp uecraytracing_amd/csrc/yk_bvh.cpp
+//          uecraytracing_amd/csrc/yk_host.cpp
+//   run:   tools/bvhsim final 42 [leaf bins all_axes expand order|list]
+//          (the FP64 tree: tools/bvhsim final 42 1 16 1 0 list)
 #include <algorithm>
+#include <string>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -111,67 +115,32 @@ struct Sim {
   }
 };
 
-// ---- 4-wide model: the binary tree collapsed (each slot's interior child replaced by its two
-// children, largest surface area first) and the kernel's while-while loop replayed in lockstep
+// ---- 4-wide model: the device's own wide nodes (ykbvh::wide_nodes: the tree, the slots and their
+// order are the shipped ones) and the kernel's while-while loop replayed in lockstep
 struct Wide {
   float lo[4][3], hi[4][3];
-  int32_t code[4];  // >= 0: wide node index; < 0: leaf code; INT32_MIN: empty
-  int n;
+  int32_t code[4];  // >= 0: wide node index; < 0: leaf code
+  int n;            // used slots (they take the low indices)
 };
 
-// the slot chosen for expansion (round 6 exploration): 0 the largest area (the library's rule),
-// 1 the largest area x leaves below, 2 the largest area x (leaves below)^0.5
-static int g_collapse = 0;
-static std::vector<uint32_t> g_leaves;  // leaves under each binary node
-static uint32_t count_leaves(const ykbvh::Built& b, int32_t code) {
-  if (code < 0) return 1;
-  if (g_leaves[code]) return g_leaves[code];
-  return g_leaves[code] = count_leaves(b, b.nodes[code].child[0]) + count_leaves(b, b.nodes[code].child[1]);
-}
-static void collapse(const ykbvh::Built& b, std::vector<Wide>& out, int32_t code, int width) {
-  // code >= 0: binary node index
-  struct E { float lo[3], hi[3]; int32_t code; };
-  std::vector<E> ents;
-  const ykbvh::Node& nd = b.nodes[code];
-  for (int k = 0; k < 2; ++k)
-    ents.push_back({{nd.lo_x[k], nd.lo_y[k], nd.lo_z[k]}, {nd.hi_x[k], nd.hi_y[k], nd.hi_z[k]}, nd.child[k]});
-  auto area = [](const E& e) {
-    float dx = e.hi[0] - e.lo[0], dy = e.hi[1] - e.lo[1], dz = e.hi[2] - e.lo[2];
-    return dx * dy + dy * dz + dz * dx;
-  };
-  auto score = [&](const E& e) {
-    const double a = area(e), nl = e.code >= 0 ? count_leaves(b, e.code) : 1;
-    return g_collapse == 1 ? a * nl : g_collapse == 2 ? a * std::sqrt(nl) : a;
-  };
-  while ((int)ents.size() < width) {
-    int best = -1;
-    for (size_t i = 0; i < ents.size(); ++i)
-      if (ents[i].code >= 0 && (best < 0 || score(ents[i]) > score(ents[best]))) best = (int)i;
-    if (best < 0) break;
-    const ykbvh::Node& c = b.nodes[ents[best].code];
-    E e0{{c.lo_x[0], c.lo_y[0], c.lo_z[0]}, {c.hi_x[0], c.hi_y[0], c.hi_z[0]}, c.child[0]};
-    E e1{{c.lo_x[1], c.lo_y[1], c.lo_z[1]}, {c.hi_x[1], c.hi_y[1], c.hi_z[1]}, c.child[1]};
-    ents[best] = e0;
-    ents.push_back(e1);
-  }
-  const size_t me = out.size();
-  out.push_back(Wide{});
-  Wide w{};
-  w.n = (int)ents.size();
-  for (int k = 0; k < 4; ++k) {
-    if (k < w.n) {
-      for (int a = 0; a < 3; ++a) { w.lo[k][a] = ents[k].lo[a]; w.hi[k][a] = ents[k].hi[a]; }
-      if (ents[k].code >= 0) {
-        w.code[k] = (int32_t)out.size();
-        collapse(b, out, ents[k].code, width);
-      } else {
-        w.code[k] = ents[k].code;
-      }
-    } else {
-      w.code[k] = INT32_MIN;
+static std::vector<Wide> library_wide(const ykbvh::Built& b, const ykbvh::WideOptions& wopt) {
+  int32_t root = 0;
+  uint32_t depth = 0;
+  const std::vector<ykbvh::WideNode> nodes = ykbvh::wide_nodes(b, &root, &depth, wopt);
+  std::vector<Wide> out(nodes.size());
+  for (size_t i = 0; i < nodes.size(); ++i) {
+    const ykbvh::WideNode& s = nodes[i];
+    const float* ax[3] = {s.x, s.y, s.z};
+    Wide& w = out[i];
+    w.n = 0;
+    for (int k = 0; k < 4; ++k) {
+      if (!(s.x[k] <= s.x[4 + k])) continue;  // unused: the empty box
+      for (int a = 0; a < 3; ++a) { w.lo[w.n][a] = ax[a][k]; w.hi[w.n][a] = ax[a][4 + k]; }
+      w.code[w.n] = s.child[k] >= 0 ? s.child[k] / (int32_t)sizeof(ykbvh::WideNode) : s.child[k];
+      ++w.n;
     }
   }
-  out[me] = w;
+  return out;
 }
 
 // per-lane traversal state machine for the lockstep wave model
@@ -195,7 +164,12 @@ int main(int argc, char** argv) {
   if (argc > 3) opt.max_leaf = atoi(argv[3]);
   if (argc > 4) opt.bins = atoi(argv[4]);
   opt.all_axes = argc > 5 ? atoi(argv[5]) != 0 : true;  // (the FP64 tree: all three axes)
-  if (argc > 6) g_collapse = atoi(argv[6]);
+  // the slot expanded next (ykbvh::WideOptions::expand) and the slot order (ykbvh::SlotOrder as
+  // a number, from the scene's camera; "list": the comparison table of the orders and the
+  // expansion rules, kernel model only)
+  const int expand = argc > 6 ? atoi(argv[6]) : 0;
+  const bool list = argc > 7 && std::string(argv[7]) == "list";
+  const int order = argc > 7 && !list ? atoi(argv[7]) : 0;
   Sim sim;
   uint32_t n = 0;
   yk_camera cam;
@@ -287,8 +261,6 @@ int main(int argc, char** argv) {
          sum_max / sum_mean);
   // ---- lockstep wave model: binary vs 4-wide, while-while loop as compiled
   std::vector<Wide> wide;
-  g_leaves.assign(sim.bvh.nodes.size(), 0);
-  if (sim.bvh.root >= 0) collapse(sim.bvh, wide, sim.bvh.root, 4);
   std::vector<size_t> idx(seg.size());
   for (size_t i = 0; i < idx.size(); ++i) idx[i] = i;
   std::shuffle(idx.begin(), idx.end(), rng);
@@ -306,7 +278,8 @@ int main(int argc, char** argv) {
     }
     return cnt;
   };
-  for (int width : {2, 4, 5, 6, 7}) {
+  // one row of the table: the model of `width` over `wide` (width 6 = the kernel's rule)
+  auto model = [&](int width, const char* label) {
     double w_inner = 0, w_leaf = 0, w_outer = 0, l_inner = 0, l_leafiters = 0;
     int max_sp = 0;
     std::vector<size_t> sp_hist(80, 0);
@@ -425,10 +398,50 @@ int main(int argc, char** argv) {
       }
       ++nw;
     }
-    printf("width %d: per wave-segment: inner iters %.1f (lane util %.0f%%), leaf iters %.1f, outer rounds %.1f; wide nodes %zu max sp %d",
-           width, w_inner / nw, 100.0 * l_inner / (64.0 * w_inner), w_leaf / nw, w_outer / nw, wide.size(), max_sp);
-    for (int k = 8; k < 20; ++k) printf(" [%d]%zu", k, sp_hist[k]);
+    printf("%swidth %d: per wave-segment: inner iters %.2f (lane util %.0f%%), leaf iters %.2f, outer rounds %.2f; "
+           "per ray: node visits %.2f, tests %.2f; wide nodes %zu max sp %d",
+           label, width, w_inner / nw, 100.0 * l_inner / (64.0 * w_inner), w_leaf / nw, w_outer / nw,
+           l_inner / (64.0 * nw), l_leafiters / (64.0 * nw), wide.size(), max_sp);
+    if (!*label)
+      for (int k = 8; k < 20; ++k) printf(" [%d]%zu", k, sp_hist[k]);
     printf("\n");
+  };
+  ykbvh::WideOptions wopt;
+  wopt.view = cam.origin;
+  wopt.expand = expand;
+  if (!list) {
+    wopt.order = (ykbvh::SlotOrder)order;
+    wide = library_wide(sim.bvh, wopt);
+    for (int width : {2, 4, 5, 6, 7}) model(width, "");
+    return 0;
+  }
+  // the slot orders under the kernel's rule, then the expansion rules with the best of them
+  const char* names[4] = {"tree order (no view origin)      ", "nearest in the highest slot      ",
+                          "nearest high, spanning leaves low", "nearest high, all leaves low     "};
+  for (int o = 0; o < 4; ++o) {
+    wopt.order = (ykbvh::SlotOrder)o;
+    wide = library_wide(sim.bvh, wopt);
+    char label[96];
+    snprintf(label, sizeof label, "expand %d, %s: ", expand, names[o]);
+    model(6, label);
+  }
+  wopt.order = ykbvh::SlotOrder::kTree;
+  wide = library_wide(sim.bvh, wopt);
+  {
+    char label[96];
+    snprintf(label, sizeof label, "expand %d, per-visit distance sort (not the kernel's): ", expand);
+    model(4, label);
+  }
+  for (int e = 0; e < 3; ++e) {
+    if (e == expand) continue;
+    for (int o : {0, 2}) {
+      wopt.order = (ykbvh::SlotOrder)o;
+      wopt.expand = e;
+      wide = library_wide(sim.bvh, wopt);
+      char label[96];
+      snprintf(label, sizeof label, "expand %d, %s: ", e, names[o]);
+      model(6, label);
+    }
   }
   return 0;
 }

@@ -191,7 +191,9 @@ int main(int argc, char** argv) {
   for (int k = 0; k < 3; ++k) ext = std::max(ext, std::fabs(cam.origin[k]));
   const ykbvh::Built b = ykbvh::build(c.data(), r.data(), n, ext, opt);
   uint32_t wd = 0;
-  M.wide = ykbvh::wide_nodes(b, &M.root, &wd);
+  ykbvh::WideOptions wopt;  // the device's slot order, from the camera (YKSIM_TREE_ORDER: as before it)
+  if (!getenv("YKSIM_TREE_ORDER")) wopt.view = cam.origin;
+  M.wide = ykbvh::wide_nodes(b, &M.root, &wd, wopt);
   M.order = b.order;
   // segment rays of a 192x108x2 path-traced image (approximate shading: the distribution matters)
   std::mt19937_64 rng(1);

@@ -190,52 +190,154 @@ Slot child_slot(const Node& n, int k) {
   return Slot{{n.lo_x[k], n.lo_y[k], n.lo_z[k]}, {n.hi_x[k], n.hi_y[k], n.hi_z[k]}, n.child[k]};
 }
 
-// Emits the wide node for binary inner node `idx` (and its subtree) into out; returns its index.
-uint32_t collapse(const Built& b, int32_t idx, std::vector<WideNode>& out, uint32_t depth, uint32_t& max_depth) {
-  std::vector<Slot> slots = {child_slot(b.nodes[idx], 0), child_slot(b.nodes[idx], 1)};
-  while (slots.size() < 4) {
-    int best = -1;
-    for (size_t i = 0; i < slots.size(); ++i)
-      if (slots[i].code >= 0 && (best < 0 || slot_area(slots[i]) > slot_area(slots[best]))) best = (int)i;
-    if (best < 0) break;
-    const Node& c = b.nodes[slots[best].code];
-    slots[best] = child_slot(c, 0);
-    slots.insert(slots.begin() + best + 1, child_slot(c, 1));  // siblings stay adjacent
+double box_area(const float* lo, const float* hi) {
+  const double dx = (double)hi[0] - lo[0], dy = (double)hi[1] - lo[1], dz = (double)hi[2] - lo[2];
+  return dx * dy + dy * dz + dz * dx;
+}
+
+double box_dist2(const float* lo, const float* hi, const double* p) {
+  double d2 = 0;
+  for (int a = 0; a < 3; ++a) {
+    const double d = p[a] < lo[a] ? lo[a] - p[a] : (p[a] > hi[a] ? p[a] - hi[a] : 0.0);
+    d2 += d * d;
   }
-  max_depth = std::max(max_depth, depth + 1);
-  const uint32_t me = (uint32_t)out.size();
-  out.emplace_back();
-  int32_t codes[4];
-  for (int k = 0; k < 4; ++k) {
-    if (k >= (int)slots.size()) {
-      codes[k] = kEmptyLeaf;
-    } else if (slots[k].code >= 0) {
-      codes[k] = (int32_t)(collapse(b, slots[k].code, out, depth + 1, max_depth) * sizeof(WideNode));
-    } else {
-      codes[k] = slots[k].code;
+  return d2;
+}
+
+bool box_spans(const float* lo, const float* hi, const float* node_lo, const float* node_hi) {
+  return box_area(lo, hi) >= kSpanArea * box_area(node_lo, node_hi);
+}
+
+struct Collapser {
+  const Built& b;
+  const WideOptions& opt;
+  std::vector<WideNode>& out;
+  std::vector<uint32_t> leaves;  // leaves under each binary node (opt.expand 1, 2)
+  uint32_t max_depth = 0;
+
+  uint32_t count_leaves(int32_t code) {
+    if (code < 0) return 1;
+    if (leaves.empty()) leaves.assign(b.nodes.size(), 0);
+    if (leaves[code]) return leaves[code];
+    return leaves[code] = count_leaves(b.nodes[code].child[0]) + count_leaves(b.nodes[code].child[1]);
+  }
+  double score(const Slot& e) {
+    const double a = slot_area(e);
+    if (opt.expand == 0) return a;
+    const double nl = count_leaves(e.code);
+    return opt.expand == 1 ? a * nl : a * std::sqrt(nl);
+  }
+
+  // The used slots in visit order reversed (see SlotOrder): a stable sort, so equal keys keep the
+  // binary tree's order.
+  void order_slots(std::vector<Slot>& slots) const {
+    if (!opt.view || opt.order == SlotOrder::kTree) return;
+    float nlo[3] = {3e38f, 3e38f, 3e38f}, nhi[3] = {-3e38f, -3e38f, -3e38f};
+    for (const Slot& e : slots)
+      for (int a = 0; a < 3; ++a) {
+        nlo[a] = std::min(nlo[a], e.lo[a]);
+        nhi[a] = std::max(nhi[a], e.hi[a]);
+      }
+    struct Key {
+      int low;  // 1: moved to the lowest indices
+      double d2;
+      Slot slot;
+    };
+    auto before = [](const Key& x, const Key& y) { return x.low != y.low ? x.low > y.low : x.d2 > y.d2; };
+    Key keys[4];  // an insertion sort (stable) of at most 4 keys: no allocation per node
+    size_t n = 0;
+    for (const Slot& e : slots) {
+      const bool leaf = e.code < 0;
+      const bool low = opt.order == SlotOrder::kNearLeavesLow
+                           ? leaf
+                           : (opt.order == SlotOrder::kNearSpanLow && leaf && box_spans(e.lo, e.hi, nlo, nhi));
+      const Key key{low ? 1 : 0, box_dist2(e.lo, e.hi, opt.view), e};
+      size_t at = n++;
+      for (; at > 0 && before(key, keys[at - 1]); --at) keys[at] = keys[at - 1];
+      keys[at] = key;
     }
+    for (size_t k = 0; k < n; ++k) slots[k] = keys[k].slot;
   }
-  WideNode& w = out[me];
-  float* ax[3] = {w.x, w.y, w.z};
-  for (int k = 0; k < 4; ++k) {
-    const bool used = k < (int)slots.size();
-    for (int a = 0; a < 3; ++a) {
-      const float lo = used ? slots[k].lo[a] : 3e38f, hi = used ? slots[k].hi[a] : -3e38f;
-      ax[a][k] = lo;
-      ax[a][4 + k] = hi;
-      ax[a][8 + k] = lo;
+
+  // Emits the wide node for binary inner node `idx` (and its subtree) into out; returns its index.
+  uint32_t collapse(int32_t idx, uint32_t depth) {
+    std::vector<Slot> slots = {child_slot(b.nodes[idx], 0), child_slot(b.nodes[idx], 1)};
+    while (slots.size() < 4) {
+      int best = -1;
+      for (size_t i = 0; i < slots.size(); ++i)
+        if (slots[i].code >= 0 && (best < 0 || score(slots[i]) > score(slots[best]))) best = (int)i;
+      if (best < 0) break;
+      const Node& c = b.nodes[slots[best].code];
+      slots[best] = child_slot(c, 0);
+      slots.insert(slots.begin() + best + 1, child_slot(c, 1));  // siblings stay adjacent
     }
-    w.child[k] = codes[k];
+    order_slots(slots);
+    max_depth = std::max(max_depth, depth + 1);
+    const uint32_t me = (uint32_t)out.size();
+    out.emplace_back();
+    int32_t codes[4];
+    for (int k = 0; k < 4; ++k) {
+      if (k >= (int)slots.size()) {
+        codes[k] = kEmptyLeaf;
+      } else if (slots[k].code >= 0) {
+        codes[k] = (int32_t)(collapse(slots[k].code, depth + 1) * sizeof(WideNode));
+      } else {
+        codes[k] = slots[k].code;
+      }
+    }
+    WideNode& w = out[me];
+    float* ax[3] = {w.x, w.y, w.z};
+    for (int k = 0; k < 4; ++k) {
+      const bool used = k < (int)slots.size();
+      for (int a = 0; a < 3; ++a) {
+        const float lo = used ? slots[k].lo[a] : 3e38f, hi = used ? slots[k].hi[a] : -3e38f;
+        ax[a][k] = lo;
+        ax[a][4 + k] = hi;
+        ax[a][8 + k] = lo;
+      }
+      w.child[k] = codes[k];
+    }
+    return me;
   }
-  return me;
+};
+
+void slot_box(const WideNode& w, int k, float* lo, float* hi) {
+  const float* ax[3] = {w.x, w.y, w.z};
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = ax[a][k];
+    hi[a] = ax[a][4 + k];
+  }
 }
 }  // namespace
 
-std::vector<WideNode> wide_nodes(const Built& b, int32_t* root_code, uint32_t* wide_depth) {
+bool slot_spans(const WideNode& w, int k) {
+  float nlo[3] = {3e38f, 3e38f, 3e38f}, nhi[3] = {-3e38f, -3e38f, -3e38f}, lo[3], hi[3];
+  for (int j = 0; j < 4; ++j) {
+    slot_box(w, j, lo, hi);
+    if (!(lo[0] <= hi[0])) continue;  // unused
+    for (int a = 0; a < 3; ++a) {
+      nlo[a] = std::min(nlo[a], lo[a]);
+      nhi[a] = std::max(nhi[a], hi[a]);
+    }
+  }
+  slot_box(w, k, lo, hi);
+  return lo[0] <= hi[0] && box_spans(lo, hi, nlo, nhi);
+}
+
+double slot_dist2(const WideNode& w, int k, const double* p) {
+  float lo[3], hi[3];
+  slot_box(w, k, lo, hi);
+  return box_dist2(lo, hi, p);
+}
+
+std::vector<WideNode> wide_nodes(const Built& b, int32_t* root_code, uint32_t* wide_depth,
+                                 const WideOptions& wopt) {
   std::vector<WideNode> out;
   uint32_t depth = 0;
   if (b.root >= 0) {
-    collapse(b, b.root, out, 0, depth);
+    Collapser c{b, wopt, out, {}, 0};
+    c.collapse(b.root, 0);
+    depth = c.max_depth;
     *root_code = 0;
   } else {
     *root_code = b.root;  // a single leaf

@@ -77,9 +77,38 @@ struct Options {
 // centers: 3 doubles per sphere; radii may be negative (hollow shells: |r| is used).
 Built build(const double* centers, const double* radii, uint32_t n, double camera_extent,
             const Options& opt = Options());
+// The order of the used slots inside a wide node.  The kernels visit the entered slots in
+// DESCENDING slot index (the last slot entered is visited next, the others are pushed in slot
+// order), so the host alone decides the traversal order; the result never depends on it (the
+// BVH only culls).  With a view origin, kNear* sort the slots by the squared
+// distance from that point to the slot's box (0 inside): the farthest gets index 0, the nearest
+// the highest used index, ties keep the binary tree's order.  Then
+//   kNearSpanLow    leaf slots that span their node (slot_spans) move to the lowest indices,
+//   kNearLeavesLow  all leaf slots do,
+// each group still farthest first.  A spanning leaf's box (the ground sphere's) reaches up to the
+// view origin, so it sorts among the nearest slots although its hit is mostly the farthest:
+// visited early it bounds little, visited last the hit bound culls it more often.
+enum class SlotOrder : int { kTree = 0, kNearHigh = 1, kNearSpanLow = 2, kNearLeavesLow = 3 };
+// A slot spans its node when its box has at least kSpanArea of the surface area of the node's own
+// box (the union of the node's used slots): relative to the node, not an absolute size.
+constexpr double kSpanArea = 0.5;
+bool slot_spans(const WideNode& w, int k);
+// Squared distance from p to slot k's box (0 inside).
+double slot_dist2(const WideNode& w, int k, const double* p);
+
+struct WideOptions {
+  const double* view = nullptr;  // three doubles; null: SlotOrder::kTree whatever `order` says
+  SlotOrder order = SlotOrder::kNearSpanLow;
+  // the slot expanded next while a node has fewer than 4 (tools/bvhsim.cpp explores 1 and 2):
+  // 0 the largest area, 1 the largest area x leaves below, 2 the largest area x sqrt(leaves below)
+  int expand = 0;
+};
+
 // 4-wide nodes (DFS order, root first), the root code in that encoding, and the wide depth
-// (inner nodes on the longest root-to-leaf path).
-std::vector<WideNode> wide_nodes(const Built& b, int32_t* root_code, uint32_t* wide_depth);
+// (inner nodes on the longest root-to-leaf path).  Used slots take the low indices; without a view
+// origin they stand in binary-tree order, siblings adjacent.
+std::vector<WideNode> wide_nodes(const Built& b, int32_t* root_code, uint32_t* wide_depth,
+                                 const WideOptions& wopt = WideOptions());
 constexpr uint32_t kMaxDepth = 32;  // traversal stack capacity (device, LDS)
 
 }  // namespace ykbvh
