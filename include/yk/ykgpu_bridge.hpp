@@ -21,6 +21,7 @@
 #include <cstdint>
 #include <cstring>
 #include <iomanip>
+#include <memory>
 #include <optional>
 #include <ostream>
 #include <stdexcept>
@@ -163,11 +164,10 @@ struct render_options {
 // The devices a drop-in render uses, from the environment: YKGPU_DEVICES unset or empty → {0};
 // "all" → every device of the node (ykgpu_device_count); otherwise a comma-separated list of
 // device indices, repeats allowed ("0,1,2,3,4,5,6,7"; "0,0,0" runs three contexts on device 0).
-inline std::vector<int> devices_from_env(const char* var = "YKGPU_DEVICES") {
-  const char* e = std::getenv(var);
+// (devices_from_list: the same grammar for a list from anywhere else, named `var` in its errors)
+inline std::vector<int> devices_from_list(const std::string& v, const char* var) {
   std::vector<int> d;
-  if (!e || !*e) return {0};
-  const std::string v = e;
+  if (v.empty()) return {0};
   if (v == "all") {
     int n = 0;
     check(ykgpu_device_count(&n), "ykgpu_device_count");
@@ -203,6 +203,10 @@ inline std::vector<int> devices_from_env(const char* var = "YKGPU_DEVICES") {
                                       std::to_string(n) + " devices)");
   return d;
 }
+inline std::vector<int> devices_from_env(const char* var = "YKGPU_DEVICES") {
+  const char* e = std::getenv(var);
+  return devices_from_list(e ? e : "", var);
+}
 
 // The drop-in's render modes from the environment (all optional; unset = render() as the
 // constexpr build computes it):
@@ -230,87 +234,160 @@ inline render_options options_from_env() {
   return o;
 }
 
-// A progressive film (ykgpu_film_*, include/ykgpu.h): the resumable accumulation state of one tile
-// on one context.  Any chunking of the samples gives the one-shot render's image.  Destroy it
-// before the renderer whose context it was made on.
-class film {
+// What a film can do, whichever kind it is: renderer::film() returns this view of a ykgpu::film
+// (one context) or a ykgpu::group_film (a device group), whose bytes are the same by definition
+// (include/ykgpu.h "group films").
+class any_film {
  public:
-  film(ykgpu_context* ctx, const yk_render_params& p) {
-    check(ykgpu_film_create(ctx, &p, &f_), "ykgpu_film_create");
-    check(ykgpu_film_params(f_, &p_), "ykgpu_film_params");
+  virtual ~any_film() = default;
+  virtual const yk_render_params& params() const = 0;
+  virtual size_t pixels() const = 0;
+  virtual uint32_t done() const = 0;
+  virtual void accumulate(uint32_t n) = 0;
+  virtual yk_film_pass accumulate_adaptive(double threshold2, uint32_t n) = 0;
+  virtual std::vector<uint32_t> counts() = 0;
+  virtual std::pair<uint32_t, uint32_t> count_range() = 0;
+  virtual void write_counts(const std::vector<double>& s, const std::vector<double>& q, const std::vector<uint32_t>& c) = 0;
+  virtual std::vector<uint8_t> resolve() = 0;
+  virtual std::vector<uint8_t> denoise(const yk_denoise_params& dp) = 0;
+  virtual std::vector<double> features(uint32_t grid) = 0;
+  virtual std::vector<uint8_t> denoise_guided(const yk_denoise_params& dp, const yk_feature_params& fp) = 0;
+  virtual yk_film_stats error_stats(double threshold2) = 0;
+  virtual void save(const std::string& path, uint64_t scene_hash) = 0;
+  virtual void load(const std::string& path, uint64_t scene_hash) = 0;
+};
+
+namespace detail {
+// the two families of entry points a film class is written over
+struct film_api {
+  using handle = ykgpu_film;
+  using owner = ykgpu_context;
+  using denoise_stats = yk_denoise_stats;
+  using guided_stats = yk_guided_stats;
+  static constexpr const char* prefix = "ykgpu_film_";
+  static constexpr auto create = &ykgpu_film_create;
+  static constexpr auto destroy = &ykgpu_film_destroy;
+  static constexpr auto get_params = &ykgpu_film_params;
+  static constexpr auto accumulate = &ykgpu_film_accumulate;
+  static constexpr auto accumulate_adaptive = &ykgpu_film_accumulate_adaptive;
+  static constexpr auto resolve = &ykgpu_film_resolve;
+  static constexpr auto read = &ykgpu_film_read;
+  static constexpr auto counts = &ykgpu_film_counts;
+  static constexpr auto write_counts = &ykgpu_film_write_counts;
+  static constexpr auto error = &ykgpu_film_error;
+  static constexpr auto features = &ykgpu_film_features;
+  static constexpr auto denoise = &ykgpu_film_denoise;
+  static constexpr auto denoise_guided = &ykgpu_film_denoise_guided;
+};
+struct group_film_api {
+  using handle = ykgpu_group_film;
+  using owner = ykgpu_group;
+  using denoise_stats = yk_group_denoise_stats;
+  using guided_stats = yk_group_denoise_stats;
+  static constexpr const char* prefix = "ykgpu_group_film_";
+  static constexpr auto create = &ykgpu_group_film_create;
+  static constexpr auto destroy = &ykgpu_group_film_destroy;
+  static constexpr auto get_params = &ykgpu_group_film_params;
+  static constexpr auto accumulate = &ykgpu_group_film_accumulate;
+  static constexpr auto accumulate_adaptive = &ykgpu_group_film_accumulate_adaptive;
+  static constexpr auto resolve = &ykgpu_group_film_resolve;
+  static constexpr auto read = &ykgpu_group_film_read;
+  static constexpr auto counts = &ykgpu_group_film_counts;
+  static constexpr auto write_counts = &ykgpu_group_film_write_counts;
+  static constexpr auto error = &ykgpu_group_film_error;
+  static constexpr auto features = &ykgpu_group_film_features;
+  static constexpr auto denoise = &ykgpu_group_film_denoise;
+  static constexpr auto denoise_guided = &ykgpu_group_film_denoise_guided;
+};
+}  // namespace detail
+
+// A progressive film (include/ykgpu.h): the resumable accumulation state of one tile.  Any chunking
+// of the samples gives the one-shot render's image.  Destroy it before the renderer whose context
+// or group it was made on.
+template <class Api>
+class basic_film : public any_film {
+ public:
+  basic_film(typename Api::owner* owner, const yk_render_params& p) {
+    ck(Api::create(owner, &p, &f_), "create");
+    ck(Api::get_params(f_, &p_), "params");
   }
-  ~film() { ykgpu_film_destroy(f_); }
-  film(const film&) = delete;
-  film& operator=(const film&) = delete;
+  ~basic_film() override { Api::destroy(f_); }
+  basic_film(const basic_film&) = delete;
+  basic_film& operator=(const basic_film&) = delete;
 
   // the params as the film keeps them (a RANDOM_DEVICE key drawn at create filled in)
-  const yk_render_params& params() const { return p_; }
-  size_t pixels() const { return (size_t)p_.row_count * (p_.col_count ? p_.col_count : p_.image_width); }
-  uint32_t done() const {
+  const yk_render_params& params() const override { return p_; }
+  size_t pixels() const override { return (size_t)p_.row_count * (p_.col_count ? p_.col_count : p_.image_width); }
+  uint32_t done() const override {
     uint32_t n = 0;
-    check(ykgpu_film_read(f_, nullptr, nullptr, &n), "ykgpu_film_read");
+    ck(Api::read(f_, nullptr, nullptr, &n), "read");
     return n;
   }
-  void accumulate(uint32_t n) { check(ykgpu_film_accumulate(f_, n), "ykgpu_film_accumulate"); }
+  void accumulate(uint32_t n) override { ck(Api::accumulate(f_, n), "accumulate"); }
   // one adaptive pass: up to n more samples for every unfinished pixel with fewer than two samples
   // or e2 > threshold2 (include/ykgpu.h "adaptive passes")
-  yk_film_pass accumulate_adaptive(double threshold2, uint32_t n) {
+  yk_film_pass accumulate_adaptive(double threshold2, uint32_t n) override {
     yk_film_pass out{};
-    check(ykgpu_film_accumulate_adaptive(f_, threshold2, n, &out), "ykgpu_film_accumulate_adaptive");
+    ck(Api::accumulate_adaptive(f_, threshold2, n, &out), "accumulate_adaptive");
     return out;
   }
-  std::vector<uint32_t> counts() {
+  std::vector<uint32_t> counts() override {
     std::vector<uint32_t> c(pixels());
-    check(ykgpu_film_counts(f_, c.data(), nullptr, nullptr), "ykgpu_film_counts");
+    ck(Api::counts(f_, c.data(), nullptr, nullptr), "counts");
     return c;
   }
   // (min, max) of the counts, without reading the map
-  std::pair<uint32_t, uint32_t> count_range() {
+  std::pair<uint32_t, uint32_t> count_range() override {
     uint32_t lo = 0, hi = 0;
-    check(ykgpu_film_counts(f_, nullptr, &lo, &hi), "ykgpu_film_counts");
+    ck(Api::counts(f_, nullptr, &lo, &hi), "counts");
     return {lo, hi};
   }
-  void write_counts(const std::vector<double>& s, const std::vector<double>& q, const std::vector<uint32_t>& c) {
+  void write_counts(const std::vector<double>& s, const std::vector<double>& q, const std::vector<uint32_t>& c) override {
     if (s.size() != pixels() * 3 || q.size() != pixels() * 3 || c.size() != pixels())
       throw error(YK_ERR_INVALID, "write_counts: the arrays do not have the film's size");
-    check(ykgpu_film_write_counts(f_, s.data(), q.data(), c.data()), "ykgpu_film_write_counts");
+    ck(Api::write_counts(f_, s.data(), q.data(), c.data()), "write_counts");
   }
-  std::vector<uint8_t> resolve() {
+  std::vector<uint8_t> resolve() override {
     std::vector<uint8_t> img(pixels() * 3);
-    check(ykgpu_film_resolve(f_, img.data()), "ykgpu_film_resolve");
+    ck(Api::resolve(f_, img.data()), "resolve");
     return img;
   }
   // the RGB8 image of the variance-guided non-local-means filter (include/ykgpu.h "film denoise");
   // every pixel needs at least two samples and the tile must be consecutive rows and columns
-  std::vector<uint8_t> denoise(const yk_denoise_params& dp, yk_denoise_stats* stats = nullptr) {
+  std::vector<uint8_t> denoise(const yk_denoise_params& dp) override { return denoise(dp, nullptr); }
+  std::vector<uint8_t> denoise(const yk_denoise_params& dp, typename Api::denoise_stats* stats) {
     std::vector<uint8_t> img(pixels() * 3);
-    check(ykgpu_film_denoise(f_, &dp, nullptr, img.data(), stats), "ykgpu_film_denoise");
+    ck(Api::denoise(f_, &dp, nullptr, img.data(), stats), "denoise");
     return img;
   }
   // the first-hit albedo, normal and depth of the tile (include/ykgpu.h "film features"): 7 doubles
   // per pixel, pixel order; computed once per (film, grid)
-  std::vector<double> features(uint32_t grid) {
+  std::vector<double> features(uint32_t grid) override {
     std::vector<double> mean(pixels() * 7);
-    check(ykgpu_film_features(f_, grid, mean.data(), nullptr, nullptr), "ykgpu_film_features");
+    ck(Api::features(f_, grid, mean.data(), nullptr, nullptr), "features");
     return mean;
   }
   // the RGB8 image of the filter guided by those features; the same preconditions as denoise()
+  std::vector<uint8_t> denoise_guided(const yk_denoise_params& dp, const yk_feature_params& fp) override {
+    return denoise_guided(dp, fp, nullptr);
+  }
   std::vector<uint8_t> denoise_guided(const yk_denoise_params& dp, const yk_feature_params& fp,
-                                      yk_guided_stats* stats = nullptr) {
+                                      typename Api::guided_stats* stats) {
     std::vector<uint8_t> img(pixels() * 3);
-    check(ykgpu_film_denoise_guided(f_, &dp, &fp, nullptr, img.data(), stats), "ykgpu_film_denoise_guided");
+    ck(Api::denoise_guided(f_, &dp, &fp, nullptr, img.data(), stats), "denoise_guided");
     return img;
   }
-  yk_film_stats error_stats(double threshold2) {
+  yk_film_stats error_stats(double threshold2) override {
     yk_film_stats st;
-    check(ykgpu_film_error(f_, threshold2, nullptr, &st), "ykgpu_film_error");
+    ck(Api::error(f_, threshold2, nullptr, &st), "error");
     return st;
   }
-  // checkpoint: the state with the film's params and the scene's hash (yk_scene_hash)
-  void save(const std::string& path, uint64_t scene_hash) {
+  // checkpoint: the state with the film's params and the scene's hash (yk_scene_hash); the files of
+  // a film and of a group film are interchangeable
+  void save(const std::string& path, uint64_t scene_hash) override {
     std::vector<double> s(pixels() * 3), q(pixels() * 3);
     uint32_t n = 0;
-    check(ykgpu_film_read(f_, s.data(), q.data(), &n), "ykgpu_film_read");
+    ck(Api::read(f_, s.data(), q.data(), &n), "read");
     const auto range = count_range();
     // (a v2 file, with the counts, only when they differ: uniform films stay readable by yk_film_load)
     const int rc = range.first != range.second
@@ -319,7 +396,7 @@ class film {
     if (rc != YK_OK) throw error(YK_ERR_INVALID, "cannot write the film file " + path);
   }
   // resume: refuses a file saved with other params or for another scene
-  void load(const std::string& path, uint64_t scene_hash) {
+  void load(const std::string& path, uint64_t scene_hash) override {
     yk_render_params fp;
     uint64_t h = 0;
     if (yk_film_load_counts(path.c_str(), &fp, &h, nullptr, nullptr, nullptr, 0) != YK_OK)
@@ -335,9 +412,18 @@ class film {
   }
 
  private:
-  ykgpu_film* f_ = nullptr;
+  static void ck(int rc, const char* call) {
+    if (rc != YK_OK) check(rc, (std::string(Api::prefix) + call).c_str());
+  }
+  typename Api::handle* f_ = nullptr;
   yk_render_params p_{};
 };
+
+// ykgpu_film_*: a film on one context
+using film = basic_film<detail::film_api>;
+// ykgpu_group_film_*: the same film over a device group (include/ykgpu.h "group films"): only the
+// sample chunks and the filters' work are spread over the group's entries
+using group_film = basic_film<detail::group_film_api>;
 
 // The render loop of source.cpp:122-172 on the GPU: one device context, or — given several
 // devices — a group of contexts over which the image's rows are dealt (tile row t → entry t mod k).
@@ -361,10 +447,15 @@ class renderer {
 
   const std::vector<int>& devices() const { return devices_; }
 
-  // the single context (films are made on it); a renderer over several devices has none
+  // the single context; a renderer over several devices has none
   ykgpu_context* context() const {
-    if (!ctx_ || group_) throw error(YK_ERR_UNSUPPORTED, "a film belongs to one context: not a device group");
+    if (!ctx_ || group_) throw error(YK_ERR_UNSUPPORTED, "one context only: not a device group");
     return ctx_;
+  }
+  // a film of the tile `p` names: a ykgpu::film on the single context, a ykgpu::group_film on a group
+  std::unique_ptr<any_film> film(const yk_render_params& p) {
+    if (group_) return std::make_unique<group_film>(group_, p);
+    return std::make_unique<ykgpu::film>(ctx_, p);
   }
   // the camera last set
   const yk_camera& camera() const { return cam_; }

@@ -344,8 +344,8 @@ int ykgpu_render_devices(const int* devices, uint32_t n_devices, const yk_sphere
  * processing order): other renders on its context between its calls, of any size or mode, do not
  * disturb it, nor it them; several films may share a context.  After ykgpu_set_scene on the
  * context a film's accumulate returns YK_ERR_INVALID (the scene generation it was created with
- * has passed).  A film must be destroyed before its context.  Films belong to one context;
- * a multi-device caller makes one film per tile. */
+ * has passed).  A film must be destroyed before its context.  A film belongs to one context;
+ * a device group has group films ("group films" below). */
 typedef struct ykgpu_film ykgpu_film;
 
 typedef struct yk_film_stats { /* 32 bytes */
@@ -575,6 +575,80 @@ int ykgpu_film_features(ykgpu_film* film, uint32_t grid, double* mean_host, doub
 /* colour / feat NULL: that side of yk_guided_defaults.  Outputs as ykgpu_film_denoise's. */
 int ykgpu_film_denoise_guided(ykgpu_film* film, const yk_denoise_params* colour, const yk_feature_params* feat,
                               double* mean_host, uint8_t* rgb_host, yk_guided_stats* stats);
+
+/* ---- group films: progressive, adaptive and denoised films over a device group -----------------
+ * (Added under ABI 11 like the film: nothing that existed changed size or meaning.  DESIGN.md 6.7.)
+ *
+ * A group film made from params P over the k entries of a group means exactly what
+ * ykgpu_film_create(ctx, P) means on one context holding the same scene: every array below is in
+ * the whole tile's pixel order and layout, and the sums, second moments and counts, resolve's RGB8,
+ * the e2 map with pixels, pixels_over, max_e2, samples_done and samples_target, the feature means
+ * and variances and the filtered mean and RGB8 of both filters are the single-context film's bytes.
+ * So yk_film_save* / yk_film_load* files pass between a group film and a single-context film.  Only
+ * the work is spread: the sample chunks by ykgpu_group_render's dealing, the filters' by bands.
+ *
+ * Dealing.  Entry e holds an ordinary film of ykgpu_group_render's sub-tile: rows row_begin +
+ * e*row_stride with stride row_stride*k, ceil((row_count - e)/k) of them, the column set unchanged;
+ * an entry without rows holds nothing.  row_band_log2 != 0 with k > 1: YK_ERR_UNSUPPORTED, as for the
+ * group render.  Seeds and the camera go by image positions, so nothing else changes.  With
+ * YK_SEED_RANDOM_DEVICE and seed_key == 0 the key is drawn once, at create, and given to every
+ * entry; ykgpu_group_film_params returns it.
+ *
+ * State.  The single film's rules hold for the whole tile.  UNIFORM means all counts equal over all
+ * entries: two entries that are each uniform at different counts make a non-uniform group film, on
+ * which ykgpu_group_film_accumulate returns YK_ERR_INVALID, read's *done is the smallest count and
+ * resolve, error and the filters use each pixel's own count.  After ykgpu_group_set_scene the
+ * accumulates, ykgpu_group_film_features and ykgpu_group_film_denoise_guided return YK_ERR_INVALID
+ * (a stale scene).  If an entry's accumulate fails part-way the group film is torn until a write.
+ * Every error code of the film calls applies (a chunk past the target, n_samples == 0, a count below
+ * 2 for the filters, both outputs NULL ...); YK_ERR_UNSUPPORTED of the filters refers to P's tile,
+ * which must be consecutive image rows and columns, not to the entries' sub-tiles.  The message of a
+ * failing entry names it: "group film entry e: ...".  A group film must be destroyed before its
+ * group.  Calls are synchronous and not reentrant per group.
+ *
+ * Concurrency.  ykgpu_group_film_accumulate enqueues every entry's chunk before it waits for any;
+ * an adaptive pass runs each entry's pass on a host thread of its own, joined before the call
+ * returns.  No entry's work depends on another's progress, and no result on scheduling.
+ * ykgpu_group_get_stats then describes the accumulate as it describes a group render (an entry by
+ * index, -1 the call).  Of yk_film_pass, pixels_selected, samples_added, min_count and max_count are
+ * the single film's; groups and launches are SUMS OVER THE ENTRIES.
+ *
+ * Filters.  "film denoise" is defined on the whole tile and reads, for a pixel, only rows within
+ * R + F of it.  Entry e owns a band of consecutive tile rows (the first row_count % k bands one row
+ * taller) and holds buffers for the band grown by the halo R + F, clipped at the tile.  A call runs
+ * the moments on every entry's own film, moves the rows from the entries that rendered them to the
+ * entries whose band or halo holds them (pitched device-to-device copies, ordered by events across
+ * the entries' streams), runs the unchanged filter kernel on each band+halo as a tile of its own,
+ * keeps the band rows and copies each band into the caller's arrays.  The guided filter computes the
+ * feature pass for its band+halo rows itself (a function of scene and pixel: no exchange), cached
+ * per (group film, grid, halo).  The count and tile checks are made before any kernel runs. */
+typedef struct ykgpu_group_film ykgpu_group_film;
+
+typedef struct yk_group_denoise_stats { /* 40 bytes */
+  double features_ms;              /* each the largest entry's device time; features_ms is 0 for  */
+  double moments_ms;               /* the colour-only filter and when every entry's pass was      */
+  double exchange_ms;              /* cached; exchange_ms the copies between the entries          */
+  double filter_ms;
+  double total_ms;                 /* the call's host wall clock, copies included    */
+} yk_group_denoise_stats;
+
+int ykgpu_group_film_create(ykgpu_group* group, const yk_render_params* params, ykgpu_group_film** out);
+int ykgpu_group_film_destroy(ykgpu_group_film* film);
+int ykgpu_group_film_params(const ykgpu_group_film* film, yk_render_params* out);
+int ykgpu_group_film_accumulate(ykgpu_group_film* film, uint32_t n_samples);
+int ykgpu_group_film_accumulate_adaptive(ykgpu_group_film* film, double threshold2, uint32_t n_samples, yk_film_pass* out);
+int ykgpu_group_film_resolve(ykgpu_group_film* film, uint8_t* rgb_host);
+int ykgpu_group_film_read(ykgpu_group_film* film, double* sums, double* sumsq, uint32_t* done);
+int ykgpu_group_film_write(ykgpu_group_film* film, const double* sums, const double* sumsq, uint32_t done);
+int ykgpu_group_film_counts(ykgpu_group_film* film, uint32_t* counts_host, uint32_t* min_count, uint32_t* max_count);
+int ykgpu_group_film_write_counts(ykgpu_group_film* film, const double* sums, const double* sumsq, const uint32_t* counts);
+int ykgpu_group_film_error(ykgpu_group_film* film, double threshold2, double* e2_host, yk_film_stats* stats);
+int ykgpu_group_film_features(ykgpu_group_film* film, uint32_t grid, double* mean_host, double* var_host, double* ms);
+int ykgpu_group_film_denoise(ykgpu_group_film* film, const yk_denoise_params* params, double* mean_host,
+                             uint8_t* rgb_host, yk_group_denoise_stats* stats);
+int ykgpu_group_film_denoise_guided(ykgpu_group_film* film, const yk_denoise_params* colour,
+                                    const yk_feature_params* feat, double* mean_host, uint8_t* rgb_host,
+                                    yk_group_denoise_stats* stats);
 
 /* ---- ray queries (ABI 11) -------------------------------------------------
  * The reference's public world.hit(r, t_min, t_max) (hittable.hpp:32-34, hittable_list.hpp:32-58,

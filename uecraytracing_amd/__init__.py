@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 from . import records
-from .records import CastStats, Hit, Ray, PathRay, RadianceParams, RadianceStats, Camera, DenoiseParams, DenoiseStats, FeatureParams, FilmPass, GuidedStats, FilmStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
+from .records import CastStats, Hit, Ray, PathRay, RadianceParams, RadianceStats, Camera, DenoiseParams, DenoiseStats, FeatureParams, FilmPass, GroupDenoiseStats, GuidedStats, FilmStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(PKG_DIR, "lib")
@@ -38,6 +38,11 @@ EXPORTS = (
     "yk_film_save_counts", "yk_film_load_counts",
     "yk_denoise_defaults", "ykgpu_film_denoise",
     "yk_guided_defaults", "ykgpu_film_features", "ykgpu_film_denoise_guided",
+    "ykgpu_group_film_create", "ykgpu_group_film_destroy", "ykgpu_group_film_params",
+    "ykgpu_group_film_accumulate", "ykgpu_group_film_accumulate_adaptive", "ykgpu_group_film_resolve",
+    "ykgpu_group_film_read", "ykgpu_group_film_write", "ykgpu_group_film_counts", "ykgpu_group_film_write_counts",
+    "ykgpu_group_film_error", "ykgpu_group_film_features", "ykgpu_group_film_denoise",
+    "ykgpu_group_film_denoise_guided",
     "ykgpu_cast_rays", "ykgpu_cast_rays_async", "ykgpu_cast_get_stats",
     "ykgpu_radiance_rays", "ykgpu_radiance_rays_async", "ykgpu_radiance_get_stats", "yk_camera_sample_ray",
     "yk_camera_sample_rays",
@@ -139,6 +144,14 @@ def load_library():
         "yk_camera_sample_rays": ([P(Camera), P(RenderParams), c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64,
                                    c.c_void_p], c.c_int),
     }
+    # the group film calls take the film calls' arguments (include/ykgpu.h "group films"); the two
+    # filters report yk_group_denoise_stats
+    for name in ("create", "destroy", "params", "accumulate", "accumulate_adaptive", "resolve", "read", "write",
+                 "counts", "write_counts", "error", "features", "denoise", "denoise_guided"):
+        args, res = sig["ykgpu_film_" + name]
+        if name.startswith("denoise"):
+            args = args[:-1] + [P(GroupDenoiseStats)]
+        sig["ykgpu_group_film_" + name] = (args, res)
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
         f.argtypes, f.restype = args, res
@@ -297,19 +310,29 @@ class Film:
     tile.  Made by Renderer.film(params); any chunking of the samples yields the one-shot render's
     sums and image bit for bit."""
 
+    _PREFIX = "ykgpu_film_"  # (GroupFilm: the same calls on a group)
+    _DENOISE_STATS, _GUIDED_STATS = DenoiseStats, GuidedStats
+
     def __init__(self, renderer: "Renderer", params: RenderParams):
         self._lib = renderer._lib
         self._ren = renderer
         self._f = ctypes.c_void_p()
-        _check(self._lib.ykgpu_film_create(renderer._ctx, ctypes.byref(params), ctypes.byref(self._f)))
+        _check(self._fn("create")(self._owner_handle(renderer), ctypes.byref(params), ctypes.byref(self._f)))
         self.params = RenderParams()
-        _check(self._lib.ykgpu_film_params(self._f, ctypes.byref(self.params)))
+        _check(self._fn("params")(self._f, ctypes.byref(self.params)))
         self._shape = (self.params.row_count, self.params.tile_width())
         renderer._films.add(self)
 
+    def _fn(self, name):
+        return getattr(self._lib, self._PREFIX + name)
+
+    @staticmethod
+    def _owner_handle(owner):
+        return owner._ctx
+
     def close(self):
         if self._f:
-            self._lib.ykgpu_film_destroy(self._f)
+            self._fn("destroy")(self._f)
             self._f = ctypes.c_void_p()
 
     def __del__(self):
@@ -331,31 +354,31 @@ class Film:
     @property
     def done(self) -> int:
         n = ctypes.c_uint32(0)
-        _check(self._lib.ykgpu_film_read(self._f, None, None, ctypes.byref(n)))
+        _check(self._fn("read")(self._f, None, None, ctypes.byref(n)))
         return n.value
 
     def accumulate(self, n_samples: int) -> int:
         """Renders samples [done, done + n_samples) into the film; returns the new done."""
-        _check(self._lib.ykgpu_film_accumulate(self._f, n_samples))
+        _check(self._fn("accumulate")(self._f, n_samples))
         return self.done
 
     def accumulate_adaptive(self, threshold2: float, n_samples: int) -> FilmPass:
         """One adaptive pass (ykgpu_film_accumulate_adaptive): up to n_samples more samples for every
         pixel below the target that has fewer than two samples or e2 > threshold2."""
         out = FilmPass()
-        _check(self._lib.ykgpu_film_accumulate_adaptive(self._f, threshold2, n_samples, ctypes.byref(out)))
+        _check(self._fn("accumulate_adaptive")(self._f, threshold2, n_samples, ctypes.byref(out)))
         return out
 
     def counts(self) -> np.ndarray:
         """uint32[row_count, tile width]: the samples each pixel holds."""
         out = np.empty(self._shape, np.uint32)
-        _check(self._lib.ykgpu_film_counts(self._f, out.ctypes.data, None, None))
+        _check(self._fn("counts")(self._f, out.ctypes.data, None, None))
         return out
 
     def count_range(self):
         """(min, max) of counts(), without reading the map."""
         lo, hi = ctypes.c_uint32(0), ctypes.c_uint32(0)
-        _check(self._lib.ykgpu_film_counts(self._f, None, ctypes.byref(lo), ctypes.byref(hi)))
+        _check(self._fn("counts")(self._f, None, ctypes.byref(lo), ctypes.byref(hi)))
         return lo.value, hi.value
 
     def write_counts(self, sums, sumsq, counts):
@@ -365,20 +388,20 @@ class Film:
         k = np.ascontiguousarray(counts, dtype=np.uint32)
         if a.shape != self._shape + (3,) or b.shape != self._shape + (3,) or k.shape != self._shape:
             raise YkError(f"Film.write_counts: sums and sumsq must have shape {self._shape + (3,)}, counts {self._shape}")
-        _check(self._lib.ykgpu_film_write_counts(self._f, a.ctypes.data, b.ctypes.data, k.ctypes.data))
+        _check(self._fn("write_counts")(self._f, a.ctypes.data, b.ctypes.data, k.ctypes.data))
 
     def resolve(self) -> np.ndarray:
         """uint8[row_count, tile width, 3]: to_color3b of the sums at the divisor done (each
         pixel's own count once they differ)."""
         out = np.empty(self._shape + (3,), np.uint8)
-        _check(self._lib.ykgpu_film_resolve(self._f, out.ctypes.data))
+        _check(self._fn("resolve")(self._f, out.ctypes.data))
         return out
 
     def read(self):
         """(sums, sumsq, done): float64[row_count, tile width, 3] each."""
         sums, sumsq = np.empty(self._shape + (3,), np.float64), np.empty(self._shape + (3,), np.float64)
         n = ctypes.c_uint32(0)
-        _check(self._lib.ykgpu_film_read(self._f, sums.ctypes.data, sumsq.ctypes.data, ctypes.byref(n)))
+        _check(self._fn("read")(self._f, sums.ctypes.data, sumsq.ctypes.data, ctypes.byref(n)))
         return sums, sumsq, n.value
 
     def write(self, sums, sumsq, done: int):
@@ -387,14 +410,14 @@ class Film:
         b = np.ascontiguousarray(sumsq, dtype=np.float64)
         if a.shape != self._shape + (3,) or b.shape != self._shape + (3,):
             raise YkError(f"Film.write: sums and sumsq must have shape {self._shape + (3,)}")
-        _check(self._lib.ykgpu_film_write(self._f, a.ctypes.data, b.ctypes.data, done))
+        _check(self._fn("write")(self._f, a.ctypes.data, b.ctypes.data, done))
 
     def error(self, threshold2: float = 0.0, want_map: bool = True):
         """(e2 float64[row_count, tile width] | None, stats dict): the squared standard error of
         each pixel's mean, worst channel, and the pixels with e2 > threshold2."""
         e2 = np.empty(self._shape, np.float64) if want_map else None
         st = FilmStats()
-        _check(self._lib.ykgpu_film_error(self._f, threshold2, e2.ctypes.data if want_map else None,
+        _check(self._fn("error")(self._f, threshold2, e2.ctypes.data if want_map else None,
                                           ctypes.byref(st)))
         return e2, st.as_dict()
 
@@ -405,8 +428,8 @@ class Film:
         the film's tile.  Reads the film only; every pixel needs at least two samples."""
         mean = np.empty(self._shape + (3,), np.float64) if want_mean else None
         rgb = np.empty(self._shape + (3,), np.uint8) if want_rgb else None
-        dp, st = DenoiseParams(radius, patch, k2, alpha, eps), DenoiseStats()
-        _check(self._lib.ykgpu_film_denoise(self._f, ctypes.byref(dp), mean.ctypes.data if want_mean else None,
+        dp, st = DenoiseParams(radius, patch, k2, alpha, eps), self._DENOISE_STATS()
+        _check(self._fn("denoise")(self._f, ctypes.byref(dp), mean.ctypes.data if want_mean else None,
                                             rgb.ctypes.data if want_rgb else None, ctypes.byref(st)))
         return mean, rgb, st.as_dict()
 
@@ -418,7 +441,7 @@ class Film:
         mean = np.empty(self._shape + (7,), np.float64)
         var = np.empty(self._shape + (7,), np.float64)
         ms = ctypes.c_double(0.0)
-        _check(self._lib.ykgpu_film_features(self._f, grid, mean.ctypes.data, var.ctypes.data, ctypes.byref(ms)))
+        _check(self._fn("features")(self._f, grid, mean.ctypes.data, var.ctypes.data, ctypes.byref(ms)))
         return mean, var, ms.value
 
     def denoise_guided(self, colour: DenoiseParams = None, feat: FeatureParams = None, want_mean: bool = True,
@@ -428,8 +451,8 @@ class Film:
         of guided_defaults()."""
         mean = np.empty(self._shape + (3,), np.float64) if want_mean else None
         rgb = np.empty(self._shape + (3,), np.uint8) if want_rgb else None
-        st = GuidedStats()
-        _check(self._lib.ykgpu_film_denoise_guided(
+        st = self._GUIDED_STATS()
+        _check(self._fn("denoise_guided")(
             self._f, ctypes.byref(colour) if colour is not None else None,
             ctypes.byref(feat) if feat is not None else None, mean.ctypes.data if want_mean else None,
             rgb.ctypes.data if want_rgb else None, ctypes.byref(st)))
@@ -473,6 +496,18 @@ class Film:
         else:
             self.write_counts(sums, sumsq, counts)
         return int(counts.min())
+
+
+class GroupFilm(Film):
+    """A group film (ykgpu_group_film, include/ykgpu.h "group films"): Film's methods and Film's bytes,
+    with the sample chunks and the filters' work spread over the entries of a Group.  Made by
+    Group.film(params).  The filters' stats are GroupDenoiseStats (exchange_ms beside the others)."""
+    _PREFIX = "ykgpu_group_film_"
+    _DENOISE_STATS = _GUIDED_STATS = GroupDenoiseStats
+
+    @staticmethod
+    def _owner_handle(owner):
+        return owner._g
 
 
 class Renderer:
@@ -668,11 +703,18 @@ class Group:
     def __init__(self, devices):
         self._lib = load_library()
         self._g = ctypes.c_void_p()
+        self._films = weakref.WeakSet()
         devs = (ctypes.c_int * len(devices))(*devices)
         _check(self._lib.ykgpu_group_create(devs, len(devices), ctypes.byref(self._g)))
         self.devices = list(devices)
 
+    def film(self, params: RenderParams) -> GroupFilm:
+        """A group film of the tile `params` names: the single-context film's meaning and bytes."""
+        return GroupFilm(self, params)
+
     def close(self):
+        for f in list(self._films):  # films go before their group
+            f.close()
         if self._g:
             self._lib.ykgpu_group_destroy(self._g)
             self._g = ctypes.c_void_p()
@@ -720,5 +762,5 @@ def render_devices(devices, spheres, camera: Camera, params: RenderParams) -> np
     return out
 
 
-__all__ = ["Renderer", "Film", "Ray", "Hit", "CastStats", "PathRay", "RadianceParams", "RadianceStats", "camera_sample_rays", "FilmPass", "DenoiseParams", "DenoiseStats", "denoise_defaults", "FeatureParams", "GuidedStats", "guided_defaults", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
+__all__ = ["Renderer", "Film", "GroupFilm", "GroupDenoiseStats", "Ray", "Hit", "CastStats", "PathRay", "RadianceParams", "RadianceStats", "camera_sample_rays", "FilmPass", "DenoiseParams", "DenoiseStats", "denoise_defaults", "FeatureParams", "GuidedStats", "guided_defaults", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
            "make_params", "load_library", "records", "EXPORTS", "LIB_PATH", "CLI_PATH"]

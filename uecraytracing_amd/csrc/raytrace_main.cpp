@@ -18,7 +18,8 @@
 //
 // Added (render parameters are compile-time macros in the reference): --width, --spp,
 // --depth, --scene, --scene-seed, --scene-file, --save-scene, --seed0, --precision, --rng,
-// --device, --stats, --pick and --probe (one ray query / one pixel's radiance queries instead of a
+// --device, --devices (a device list as the bridge's YKGPU_DEVICES takes it: the rows dealt over a
+// group, films as group films, include/ykgpu.h "group films"), --stats, --pick and --probe (one ray query / one pixel's radiance queries instead of a
 // render), the progressive film's --progressive, --until, --checkpoint, --stop-after
 // (include/ykgpu.h "progressive film": the image in chunks of samples, the same bytes as in one
 // call), and --denoise with --denoise-radius, --denoise-patch, --denoise-k2 (include/ykgpu.h "film
@@ -84,6 +85,10 @@ const char* kHelp =
     "      --precision arg       fp64|fp32: the T of render<T> (default: fp64)\n"
     "      --rng arg             mt19937|xor128: the per-sample engine (default: mt19937)\n"
     "      --device arg          GPU index (default: 0)\n"
+    "      --devices arg         a device list instead: 0,1,2,3 or all (repeats allowed: 0,0,0 runs\n"
+    "                            three contexts on device 0); the image's rows are dealt over the\n"
+    "                            list, and every film option runs through a group film (the same\n"
+    "                            bytes as on one device)\n"
     "      --stats               print kernel time and throughput\n"
     "      --progressive arg     render in chunks of arg samples per pixel, rewriting the image\n"
     "                            after each chunk (the same image as in one call)\n"
@@ -127,6 +132,9 @@ struct args {
   bool have_output = false;
   uint32_t width = YK_IMAGE_WIDTH, spp = YK_SPP, depth = YK_MAX_DEPTH, scene_seed = 42;
   int device = 0;
+  bool have_device = false;
+  std::string devices;  // --devices: the list as given (parsed once the library is there)
+  bool have_devices = false;
   bool have_seed0 = false;
   uint32_t seed0 = 0;
   std::string precision = "fp64";
@@ -220,7 +228,12 @@ args parse(int argc, char** argv) {
       else if (n == "spp") a.spp = to_u32(n, value(i, n, inl));
       else if (n == "depth") a.depth = to_u32(n, value(i, n, inl));
       else if (n == "scene-seed") a.scene_seed = to_u32(n, value(i, n, inl));
-      else if (n == "device") a.device = (int)to_u32(n, value(i, n, inl));
+      else if (n == "device") { a.device = (int)to_u32(n, value(i, n, inl)); a.have_device = true; }
+      else if (n == "devices") {
+        a.devices = value(i, n, inl);
+        a.have_devices = true;
+        if (a.devices.empty()) throw option_error{"Option 'devices' needs a device list"};
+      }
       else if (n == "scene") a.scene = value(i, n, inl);
       else if (n == "scene-file") a.scene_file = value(i, n, inl);
       else if (n == "save-scene") a.save_scene = value(i, n, inl);
@@ -282,6 +295,7 @@ args parse(int argc, char** argv) {
       }
     }
   }
+  if (a.have_device && a.have_devices) throw option_error{"Options 'device' and 'devices' exclude each other"};
   if (a.adaptive && !a.have_until) throw option_error{"Option 'adaptive' needs --until"};
   if (a.have_probe && a.have_pick) throw option_error{"Options 'probe' and 'pick' exclude each other"};
   if (a.have_probe && !a.have_seed0) throw option_error{"Option 'probe' needs --seed0 (the samples it repeats)"};
@@ -350,7 +364,8 @@ int main(int argc, char* argv[]) {
   }
   std::vector<uint8_t> image;
   try {
-    ykgpu::renderer gpu(a.device);
+    // one context, or with --devices a group (a list of one device is one context)
+    ykgpu::renderer gpu(a.have_devices ? ykgpu::devices_from_list(a.devices, "--devices") : std::vector<int>{a.device});
     if (!a.scene_file.empty()) {
       uint32_t n = 0;
       yk_camera cam;
@@ -467,7 +482,9 @@ int main(int argc, char* argv[]) {
             p.seed_key = fp.seed_key;
         }
       }
-      ykgpu::film film(gpu.context(), p);
+      // a film on the one context, a group film on a device list: the same bytes either way
+      const std::unique_ptr<ykgpu::any_film> film_owner = gpu.film(p);
+      ykgpu::any_film& film = *film_owner;
       if (resume) {
         try {
           film.load(a.checkpoint, scene);

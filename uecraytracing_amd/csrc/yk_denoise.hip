@@ -307,6 +307,110 @@ size_t nlm_lds_bytes(uint32_t R, uint32_t F) {
   return (6 * (kBlockW + 2 * H) * (kBlockH + 2 * H) + 2 * (kBlockW + 2 * F) * (kBlockH + 2 * F)) * sizeof(double);
 }
 
+NlmArgs nlm_args(const double* mv, double* out, uint32_t rows, uint32_t wt, const yk_denoise_params& dp) {
+  NlmArgs a{};
+  a.mv = mv;
+  a.out = out;
+  a.rows = rows;
+  a.wt = wt;
+  a.npix = rows * wt;
+  a.radius = dp.radius;
+  a.patch = dp.patch;
+  a.k2 = dp.k2;
+  a.alpha = dp.alpha;
+  a.eps = dp.eps;
+  a.npatch = (double)(3 * (2 * dp.patch + 1) * (2 * dp.patch + 1));
+  return a;
+}
+
+GuidedArgs guided_args(const NlmArgs& a, const double* feat, const yk_feature_params& fp) {
+  GuidedArgs g{};
+  g.c = a;
+  g.feat = feat;
+  g.k2 = fp.k2;
+  g.alpha = fp.alpha;
+  g.tau[0] = fp.tau_albedo;
+  g.tau[1] = fp.tau_normal;
+  g.tau[2] = fp.tau_depth;
+  return g;
+}
+
+}  // namespace
+
+int ykhost::denoise_params_check(const yk_denoise_params& dp) {
+  if (dp.radius > kMaxRadius) return fail(YK_ERR_INVALID, "denoise: radius must be <= 10");
+  if (dp.patch > kMaxPatch) return fail(YK_ERR_INVALID, "denoise: patch must be <= 3");
+  if (!(dp.k2 > 0) || !std::isfinite(dp.k2)) return fail(YK_ERR_INVALID, "denoise: k2 must be finite and > 0");
+  if (!(dp.alpha >= 0) || !std::isfinite(dp.alpha)) return fail(YK_ERR_INVALID, "denoise: alpha must be finite and >= 0");
+  if (!(dp.eps > 0) || !std::isfinite(dp.eps)) return fail(YK_ERR_INVALID, "denoise: eps must be finite and > 0");
+  return YK_OK;
+}
+
+int ykhost::feature_params_check(const yk_feature_params& fp) {
+  if (fp.grid < 1 || fp.grid > 4) return fail(YK_ERR_INVALID, "features: grid must be 1..4");
+  if (fp.reserved) return fail(YK_ERR_INVALID, "features: reserved must be 0");
+  if (!(fp.k2 > 0) || !std::isfinite(fp.k2)) return fail(YK_ERR_INVALID, "features: k2 must be finite and > 0");
+  if (!(fp.alpha >= 0) || !std::isfinite(fp.alpha)) return fail(YK_ERR_INVALID, "features: alpha must be finite and >= 0");
+  for (double tau : {fp.tau_albedo, fp.tau_normal, fp.tau_depth})
+    if (!(tau > 0)) return fail(YK_ERR_INVALID, "features: tau must be > 0 (+inf switches a group off)");
+  return YK_OK;
+}
+
+// [m, v planes: 6 npix doubles][out: 3 npix doubles][rgb: 3 npix bytes][low]
+int ykhost::denoise_buffers(ykgpu_film* film, DenoiseBufs* out) {
+  const size_t npix = (size_t)film->p.row_count * tile_width(&film->p);
+  const size_t off_out = align256(6 * npix * sizeof(double)), off_rgb = off_out + align256(3 * npix * sizeof(double));
+  const size_t off_low = off_rgb + align256(3 * npix), bytes = off_low + 256;
+  if (!film->d_denoise) YK_HIP(hipMalloc(&film->d_denoise, bytes));  // (a film's tile never changes size)
+  char* const base = (char*)film->d_denoise;
+  out->mv = (double*)base;
+  out->out = (double*)(base + off_out);
+  out->rgb = (uint8_t*)(base + off_rgb);
+  out->low = (unsigned long long*)(base + off_low);
+  return YK_OK;
+}
+
+// ---- the steps of a group film's filter (yk_group.hip) -------------------------
+hipError_t ykhost::denoise_moments_enqueue(ykgpu_film* film, const DenoiseBufs& b) {
+  const hipStream_t stream = film->ctx->stream;
+  hipError_t e = hipMemsetAsync(b.low, 0, sizeof(unsigned long long), stream);
+  if (e != hipSuccess) return e;
+  const uint32_t blocks = std::max(1u, std::min((film->nps + 255) / 256, 2048u));
+  hipLaunchKernelGGL(yk_film_moments, dim3(blocks), dim3(256), 0, stream, film->d_plane, film->d_order,
+                     film_counts(film), b.mv, b.low, film->nps, (uint32_t)film->npix, film->done);
+  return hipGetLastError();
+}
+
+// The band entry: the band film's tile is the band grown by the halo, and the kernels run on it as
+// on a tile of their own (the clamps fire only where the band's edge is the tile's edge).
+hipError_t ykhost::denoise_band_enqueue(ykgpu_film* band, const DenoiseBufs& b, const yk_denoise_params& dp,
+                                        const yk_feature_params* fp, const double* feat, uint32_t r0, uint32_t n,
+                                        bool want_rgb) {
+  const hipStream_t stream = band->ctx->stream;
+  const uint32_t rows = band->p.row_count, wt = tile_width(&band->p);
+  const NlmArgs a = nlm_args(b.mv, b.out, rows, wt, dp);
+  const dim3 grid((wt + kBlockW - 1) / kBlockW, (rows + kBlockH - 1) / kBlockH);
+  const size_t lds = nlm_lds_bytes(dp.radius, dp.patch);
+  // (per call: the attribute belongs to the current device)
+  hipError_t e = hipFuncSetAttribute(fp ? (const void*)yk_film_nlm_guided : (const void*)yk_film_nlm,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)nlm_lds_bytes(kMaxRadius, kMaxPatch));
+  if (e != hipSuccess) return e;
+  if (fp)
+    hipLaunchKernelGGL(yk_film_nlm_guided, grid, dim3(kThreads), lds, stream, guided_args(a, feat, *fp));
+  else
+    hipLaunchKernelGGL(yk_film_nlm, grid, dim3(kThreads), lds, stream, a);
+  e = hipGetLastError();
+  if (e == hipSuccess && want_rgb && n) {
+    const size_t off = (size_t)r0 * wt * 3, cnt = (size_t)n * wt * 3;
+    const uint32_t blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>((cnt + 255) / 256, 2048));
+    hipLaunchKernelGGL(yk_film_rgb8, dim3(blocks), dim3(256), 0, stream, b.out + off, b.rgb + off, (uint64_t)cnt);
+    e = hipGetLastError();
+  }
+  return e;
+}
+
+namespace {
+
 // The body of both denoise entry points: the checks, the film's denoise buffers, the moments, the
 // caller's filter, the RGB8 conversion and the read-back.  `name` is the entry point's, for the
 // error text.  The callers differ in three steps:
@@ -322,11 +426,7 @@ int denoise_call(ykgpu_film* film, const char* name, const yk_denoise_params& dp
                  yk_denoise_stats* stats, Checks&& feature_checks, Prepare&& prepare, Filter&& filter) {
   const auto t0 = std::chrono::steady_clock::now();
   if (int rc = film_ready(film)) return rc;
-  if (dp.radius > kMaxRadius) return fail(YK_ERR_INVALID, "denoise: radius must be <= 10");
-  if (dp.patch > kMaxPatch) return fail(YK_ERR_INVALID, "denoise: patch must be <= 3");
-  if (!(dp.k2 > 0) || !std::isfinite(dp.k2)) return fail(YK_ERR_INVALID, "denoise: k2 must be finite and > 0");
-  if (!(dp.alpha >= 0) || !std::isfinite(dp.alpha)) return fail(YK_ERR_INVALID, "denoise: alpha must be finite and >= 0");
-  if (!(dp.eps > 0) || !std::isfinite(dp.eps)) return fail(YK_ERR_INVALID, "denoise: eps must be finite and > 0");
+  if (int rc = denoise_params_check(dp)) return rc;
   if (int rc = feature_checks()) return rc;
   if (!mean_host && !rgb_host) return fail(YK_ERR_INVALID, "denoise: mean_host and rgb_host are both null");
   if (!film_consecutive(film))
@@ -339,15 +439,12 @@ int denoise_call(ykgpu_film* film, const char* name, const yk_denoise_params& dp
   const uint32_t rows = film->p.row_count, wt = tile_width(&film->p);
   const hipStream_t stream = film->ctx->stream;  // (film calls are synchronous on it)
   const size_t npix = (size_t)rows * wt;
-  // the film's denoise buffers: [m, v planes: 6 npix doubles][out: 3 npix doubles][rgb: 3 npix bytes][low]
-  const size_t off_out = align256(6 * npix * sizeof(double)), off_rgb = off_out + align256(3 * npix * sizeof(double));
-  const size_t off_low = off_rgb + align256(3 * npix), bytes = off_low + 256;
-  if (!film->d_denoise) YK_HIP(hipMalloc(&film->d_denoise, bytes));  // (a film's tile never changes size)
-  char* const base = (char*)film->d_denoise;
-  double* const d_mv = (double*)base;
-  double* const d_out = (double*)(base + off_out);
-  uint8_t* const d_rgb = (uint8_t*)(base + off_rgb);
-  unsigned long long* const d_low = (unsigned long long*)(base + off_low);
+  DenoiseBufs bufs{};
+  if (int rc = denoise_buffers(film, &bufs)) return rc;
+  double* const d_mv = bufs.mv;
+  double* const d_out = bufs.out;
+  uint8_t* const d_rgb = bufs.rgb;
+  unsigned long long* const d_low = bufs.low;
 
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   hipError_t e = hipSuccess;
@@ -368,18 +465,7 @@ int denoise_call(ykgpu_film* film, const char* name, const yk_denoise_params& dp
   // (the filter does not depend on the verdict: it is enqueued behind the moments, and its result
   // is dropped if a count turns out to be below 2)
   if (e == hipSuccess) {
-    NlmArgs a{};
-    a.mv = d_mv;
-    a.out = d_out;
-    a.rows = rows;
-    a.wt = wt;
-    a.npix = (uint32_t)npix;
-    a.radius = dp.radius;
-    a.patch = dp.patch;
-    a.k2 = dp.k2;
-    a.alpha = dp.alpha;
-    a.eps = dp.eps;
-    a.npatch = (double)(3 * (2 * dp.patch + 1) * (2 * dp.patch + 1));
+    const NlmArgs a = nlm_args(d_mv, d_out, rows, wt, dp);
     const dim3 grid((wt + kBlockW - 1) / kBlockW, (rows + kBlockH - 1) / kBlockH);
     e = filter(a, grid, nlm_lds_bytes(dp.radius, dp.patch), stream);
   }
@@ -476,12 +562,7 @@ int ykgpu_film_denoise_guided(ykgpu_film* film, const yk_denoise_params* params,
   const int rc = denoise_call(
       film, "ykgpu_film_denoise_guided", dp, mean_host, rgb_host, stats ? &ds : nullptr,
       [&]() -> int {
-        if (fp.grid < 1 || fp.grid > 4) return fail(YK_ERR_INVALID, "features: grid must be 1..4");
-        if (fp.reserved) return fail(YK_ERR_INVALID, "features: reserved must be 0");
-        if (!(fp.k2 > 0) || !std::isfinite(fp.k2)) return fail(YK_ERR_INVALID, "features: k2 must be finite and > 0");
-        if (!(fp.alpha >= 0) || !std::isfinite(fp.alpha)) return fail(YK_ERR_INVALID, "features: alpha must be finite and >= 0");
-        for (double tau : {fp.tau_albedo, fp.tau_normal, fp.tau_depth})
-          if (!(tau > 0)) return fail(YK_ERR_INVALID, "features: tau must be > 0 (+inf switches a group off)");
+        if (int rc = feature_params_check(fp)) return rc;
         if (film->scene_gen != film->ctx->scene_gen)
           return fail(YK_ERR_INVALID, "the context's scene was set after the film was created");
         return YK_OK;
@@ -493,14 +574,7 @@ int ykgpu_film_denoise_guided(ykgpu_film* film, const yk_denoise_params* params,
         return YK_OK;
       },
       [&](const NlmArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-        GuidedArgs g{};
-        g.c = a;
-        g.feat = d_feat;
-        g.k2 = fp.k2;
-        g.alpha = fp.alpha;
-        g.tau[0] = fp.tau_albedo;
-        g.tau[1] = fp.tau_normal;
-        g.tau[2] = fp.tau_depth;
+        const GuidedArgs g = guided_args(a, d_feat, fp);
         hipLaunchKernelGGL(yk_film_nlm_guided, grid, dim3(kThreads), lds, st, g);
         return hipGetLastError();
       });

@@ -216,6 +216,37 @@ int ykhost::film_ready(const ykgpu_film* film) {
   if (film->torn) return fail(YK_ERR_INVALID, "the film's last accumulate failed part-way: restore it with ykgpu_film_write");
   return YK_OK;
 }
+// ykgpu_film_accumulate in two halves (a group film enqueues every entry's chunk before it waits
+// for any): the checks and the launches on the context's stream ...
+int ykhost::film_accumulate_enqueue(ykgpu_film* film, uint32_t n_samples) {
+  int rc = film_ready(film);
+  if (rc) return rc;
+  ykgpu_context* ctx = film->ctx;
+  if (film->scene_gen != ctx->scene_gen)
+    return fail(YK_ERR_INVALID, "the context's scene was set after the film was created");
+  if (!film->uniform())
+    return fail(YK_ERR_INVALID, "the film's pixels hold different sample counts: use ykgpu_film_accumulate_adaptive");
+  if (n_samples == 0) return fail(YK_ERR_INVALID, "n_samples must be > 0");
+  if (n_samples > film->p.samples_per_pixel - film->done)
+    return fail(YK_ERR_INVALID, "the chunk passes the film's target (samples_per_pixel)");
+  YK_HIP(hipSetDevice(ctx->device));
+  film->torn = true;  // (until the chunk is whole)
+  return launch(ctx, &film->p, nullptr, nullptr, ctx->stream, film->done, film->done + n_samples, film);
+}
+// ... and the wait, the statistics (total_ms from t0) and the film's new state
+int ykhost::film_accumulate_finish(ykgpu_film* film, uint32_t n_samples, std::chrono::steady_clock::time_point t0) {
+  ykgpu_context* ctx = film->ctx;
+  YK_HIP(hipSetDevice(ctx->device));
+  YK_HIP(hipStreamSynchronize(ctx->stream));
+  int rc = finish_stats(ctx);
+  if (rc) return rc;
+  ctx->stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  film->done += n_samples;
+  film->hist.clear();
+  film->hist[film->done] = film->npix;
+  film->torn = false;
+  return YK_OK;
+}
 namespace {
 uint32_t film_blocks(const ykgpu_film* film) { return std::max(1u, std::min((film->nps + 255) / 256, (uint32_t)film->ctx->cus * 8)); }
 }  // namespace
@@ -283,30 +314,9 @@ int ykgpu_film_params(const ykgpu_film* film, yk_render_params* out) {
 }
 
 int ykgpu_film_accumulate(ykgpu_film* film, uint32_t n_samples) {
-  int rc = film_ready(film);
-  if (rc) return rc;
-  ykgpu_context* ctx = film->ctx;
-  if (film->scene_gen != ctx->scene_gen)
-    return fail(YK_ERR_INVALID, "the context's scene was set after the film was created");
-  if (!film->uniform())
-    return fail(YK_ERR_INVALID, "the film's pixels hold different sample counts: use ykgpu_film_accumulate_adaptive");
-  if (n_samples == 0) return fail(YK_ERR_INVALID, "n_samples must be > 0");
-  if (n_samples > film->p.samples_per_pixel - film->done)
-    return fail(YK_ERR_INVALID, "the chunk passes the film's target (samples_per_pixel)");
-  YK_HIP(hipSetDevice(ctx->device));
   const auto t0 = std::chrono::steady_clock::now();
-  film->torn = true;  // (until the chunk is whole)
-  rc = launch(ctx, &film->p, nullptr, nullptr, ctx->stream, film->done, film->done + n_samples, film);
-  if (rc) return rc;
-  YK_HIP(hipStreamSynchronize(ctx->stream));
-  rc = finish_stats(ctx);
-  if (rc) return rc;
-  ctx->stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  film->done += n_samples;
-  film->hist.clear();
-  film->hist[film->done] = film->npix;
-  film->torn = false;
-  return YK_OK;
+  if (int rc = film_accumulate_enqueue(film, n_samples)) return rc;
+  return film_accumulate_finish(film, n_samples, t0);
 }
 
 int ykgpu_film_resolve(ykgpu_film* film, uint8_t* rgb_host) {

@@ -9,13 +9,49 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cstring>
+#include <limits>
+#include <map>
+#include <random>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/ykgpu.h"
+#include "yk_group_plan.hpp"
 #include "yk_host_internal.hpp"
 
 using namespace ykhost;
+
+namespace {
+// an entry's statistics into the call's (ykgpu_group_get_stats, index -1): work summed, times the
+// largest entry's; dev_extra and call_extra: the group's own buffers for that entry
+void add_entry_stats(yk_render_stats& tot, const yk_render_stats& s, size_t dev_extra, size_t call_extra) {
+  tot.samples += s.samples;
+  tot.segments += s.segments;
+  tot.sphere_tests += s.sphere_tests;
+  tot.sqrt_calls += s.sqrt_calls;
+  tot.mt_fallbacks += s.mt_fallbacks;
+  tot.node_visits += s.node_visits;
+  tot.linear_scans += s.linear_scans;
+  tot.newton_calls += s.newton_calls;
+  tot.newton_iters += s.newton_iters;
+  for (int q = 0; q < 8; ++q) tot.work[q] += s.work[q];
+  tot.launches += s.launches;
+  tot.grid_blocks = std::max(tot.grid_blocks, s.grid_blocks);
+  tot.kernel_ms = std::max(tot.kernel_ms, s.kernel_ms);
+  tot.render_busy_ms = std::max(tot.render_busy_ms, s.render_busy_ms);
+  tot.warmup_ms = std::max(tot.warmup_ms, s.warmup_ms);
+  tot.resolve_ms = std::max(tot.resolve_ms, s.resolve_ms);
+  tot.seed_key = s.seed_key;
+  tot.device_bytes += s.device_bytes + dev_extra;
+  tot.call_bytes += s.call_bytes + call_extra;
+  tot.sclk_mhz = std::max(tot.sclk_mhz, s.sclk_mhz);
+  // (ABI 11) the largest launch of any entry, and every entry's memory-pressure shrinks
+  tot.launch_spp = std::max(tot.launch_spp, s.launch_spp);
+  tot.mem_shrinks += s.mem_shrinks;
+}
+}  // namespace
 
 extern "C" {
 
@@ -121,30 +157,7 @@ int ykgpu_group_render(ykgpu_group* g, const yk_render_params* p, uint8_t* rgb_h
     YK_HIP(hipStreamSynchronize(c->stream));
     if ((rc = finish_stats(c))) return rc;
     g->st[e] = c->stats;
-    const yk_render_stats& s = c->stats;
-    tot.samples += s.samples;
-    tot.segments += s.segments;
-    tot.sphere_tests += s.sphere_tests;
-    tot.sqrt_calls += s.sqrt_calls;
-    tot.mt_fallbacks += s.mt_fallbacks;
-    tot.node_visits += s.node_visits;
-    tot.linear_scans += s.linear_scans;
-    tot.newton_calls += s.newton_calls;
-    tot.newton_iters += s.newton_iters;
-    for (int q = 0; q < 8; ++q) tot.work[q] += s.work[q];
-    tot.launches += s.launches;
-    tot.grid_blocks = std::max(tot.grid_blocks, s.grid_blocks);
-    tot.kernel_ms = std::max(tot.kernel_ms, s.kernel_ms);
-    tot.render_busy_ms = std::max(tot.render_busy_ms, s.render_busy_ms);
-    tot.warmup_ms = std::max(tot.warmup_ms, s.warmup_ms);
-    tot.resolve_ms = std::max(tot.resolve_ms, s.resolve_ms);
-    tot.seed_key = s.seed_key;
-    tot.device_bytes += s.device_bytes + g->tile_cap[e];
-    tot.call_bytes += s.call_bytes + rows[e] * row_bytes;
-    tot.sclk_mhz = std::max(tot.sclk_mhz, s.sclk_mhz);
-    // (ABI 11) the largest launch of any entry, and every entry's memory-pressure shrinks
-    tot.launch_spp = std::max(tot.launch_spp, s.launch_spp);
-    tot.mem_shrinks += s.mem_shrinks;
+    add_entry_stats(tot, c->stats, g->tile_cap[e], rows[e] * row_bytes);
   }
   tot.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   g->total = tot;
@@ -177,3 +190,6 @@ int ykgpu_render_devices(const int* devices, uint32_t n_devices, const yk_sphere
 }
 
 }  // extern "C"
+
+// group films (ykgpu_group_film_*): the unit's other half, in a file of its own
+#include "yk_group_film.hpp"

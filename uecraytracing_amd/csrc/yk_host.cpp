@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/ykgpu.h"
+#include "yk_group_plan.hpp"
 #include "yk_schedule.hpp"
 
 namespace {
@@ -231,6 +232,23 @@ uint32_t yk_schedule_plan(uint32_t nps, uint32_t spp, uint32_t s_begin, uint64_t
     if (take) take[i] = sched[i].second;
   }
   return (uint32_t)sched.size();
+}
+
+// The band and exchange plan of a group film's filter (yk_group_plan.hpp), for the CPU tests: not
+// part of the C-ABI.  bands (may be null) receives k records of 4 words (begin, count, lo, hi),
+// copies (may be null) the first `cap` records of 6 words (source entry, first source row, rows,
+// destination entry, first destination row, destination pitch in rows).  Returns the number of copies.
+uint32_t yk_group_film_plan(uint32_t rows, uint32_t k, uint32_t halo, uint32_t* bands, uint32_t* copies, uint32_t cap) {
+  std::vector<ykplan::Band> b;
+  std::vector<ykplan::Copy> c;
+  ykplan::group_film_plan(rows, k, halo, b, c);
+  for (uint32_t e = 0; bands && e < b.size(); ++e)
+    bands[4 * e] = b[e].begin, bands[4 * e + 1] = b[e].count, bands[4 * e + 2] = b[e].lo, bands[4 * e + 3] = b[e].hi;
+  for (uint32_t i = 0; copies && i < c.size() && i < cap; ++i) {
+    uint32_t* o = copies + 6 * i;
+    o[0] = c[i].src, o[1] = c[i].src_row, o[2] = c[i].rows, o[3] = c[i].dst, o[4] = c[i].dst_row, o[5] = c[i].dst_pitch;
+  }
+  return (uint32_t)c.size();
 }
 
 }  // extern "C"

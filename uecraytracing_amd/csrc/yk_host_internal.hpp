@@ -1,9 +1,10 @@
 // yk_host_internal.hpp — what more than one host unit of the library needs, defined once: the error
 // slot and the YK_HIP macro, the structs behind the C-ABI's opaque handles (ykgpu_context,
-// ykgpu_film, ykgpu_group) and the host functions that cross units (namespace ykhost).  Not part of
+// ykgpu_film, ykgpu_group, ykgpu_group_film) and the host functions that cross units (namespace ykhost).  Not part of
 // the C-ABI, not installed.  Who defines what: yk_context.hip the error slot and the statistics,
 // yk_pipeline.hip the parameter checks, the tile helpers, the processing order and launch(),
-// yk_film.hip film_ready, yk_features.hip the feature pass, yk_cast.hpp the ray queries,
+// yk_film.hip film_ready and the accumulate halves, yk_denoise.hip the steps of a group film's filter
+// (yk_group_film.hpp in yk_group.hip runs them), yk_features.hip the feature pass, yk_cast.hpp the ray queries,
 // yk_radiance.hpp the radiance queries.
 #ifndef YK_HOST_INTERNAL_HPP
 #define YK_HOST_INTERNAL_HPP
@@ -223,6 +224,23 @@ struct ykgpu_group {
   yk_render_stats total{};          // ... and of the whole call
 };
 
+// A group film (include/ykgpu.h "group films"): per entry an ordinary film of the group render's
+// sub-tile (null: the entry has no rows) and, for the filters, a band film: a film record without
+// sample planes over the entry's band grown by the halo (yk_group_plan.hpp), which owns the
+// band's denoise buffers and feature planes the way a film owns its own.
+struct ykgpu_group_film {
+  ykgpu_group* g = nullptr;
+  yk_render_params p{};            // the whole tile's, with the seed key drawn at create
+  uint32_t k = 0, wt = 0;
+  std::vector<ykgpu_film*> film;   // per entry, the render side
+  std::vector<uint32_t> rows;      // ... and its rows
+  std::vector<uint64_t> gen;       // each context's scene generation at create
+  std::vector<ykgpu_film*> band;   // per entry, the filter side, for `halo`
+  uint32_t halo = 0;
+  bool have_bands = false;
+  bool torn = false;  // an entry's accumulate failed part-way (until a write)
+};
+
 // the render units' instances (yk_render_f64.hip, yk_render_f32.hip), by (scene in LDS, kMode).
 // (Inline here, not in yk_pipeline.hip: KernelArgs lives in the anonymous namespace, so a function
 // that returns a RenderKernel has internal linkage and cannot be declared across units.)
@@ -249,6 +267,28 @@ uint64_t device_bytes(const ykgpu_context* ctx);
 int finish_stats(ykgpu_context* ctx);
 // yk_film.hip: null or torn film: YK_ERR_INVALID with the last error set, like every film call
 int film_ready(const ykgpu_film* film);
+// ... and ykgpu_film_accumulate's two halves: the checks and the launches, then the wait, the
+// statistics (total_ms counted from t0) and the film's new state
+int film_accumulate_enqueue(ykgpu_film* film, uint32_t n_samples);
+int film_accumulate_finish(ykgpu_film* film, uint32_t n_samples, std::chrono::steady_clock::time_point t0);
+// yk_denoise.hip: the steps of a group film's filter.  The parameter checks of both filters;
+int denoise_params_check(const yk_denoise_params& dp);
+int feature_params_check(const yk_feature_params& fp);
+// a film's denoise buffers, sized by its tile and allocated at first use: the m / v planes, the
+// filtered mean, its RGB8 image and the counter of pixels whose count is below 2;
+struct DenoiseBufs {
+  double *mv, *out;
+  uint8_t* rgb;
+  unsigned long long* low;
+};
+int denoise_buffers(ykgpu_film* film, DenoiseBufs* out);
+// yk_film_moments of the film into b.mv, enqueued on its context's stream (b.low is cleared first);
+hipError_t denoise_moments_enqueue(ykgpu_film* film, const DenoiseBufs& b);
+// the filter over the band film's whole tile, from b.mv into b.out, on its context's stream: the
+// guided one when fp is given (feat: the band's feature planes), then the RGB8 image of the tile's
+// rows [r0, r0 + n) when want_rgb.  The current device is the band's.
+hipError_t denoise_band_enqueue(ykgpu_film* band, const DenoiseBufs& b, const yk_denoise_params& dp,
+                                const yk_feature_params* fp, const double* feat, uint32_t r0, uint32_t n, bool want_rgb);
 // yk_features.hip: the feature planes of the film at grid g (1..4) on the device, computed on the
 // context's stream unless the film already holds them; *ms (may be null) receives the pass's device
 // time, 0 when the cached planes were reused.  Synchronous.  YK_ERR_INVALID on a stale scene or a

@@ -207,6 +207,21 @@ class FeatureParams(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved"}
 
 
+class GroupDenoiseStats(ctypes.Structure):
+    """yk_group_denoise_stats (include/ykgpu.h "group films"): where one group film filter call spent
+    its time, each device time the largest entry's."""
+    _fields_ = [
+        ("features_ms", ctypes.c_double),  # 0 for the colour-only filter and when the pass was cached
+        ("moments_ms", ctypes.c_double),
+        ("exchange_ms", ctypes.c_double),
+        ("filter_ms", ctypes.c_double),
+        ("total_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class GuidedStats(ctypes.Structure):
     """yk_guided_stats (include/ykgpu.h): where one ykgpu_film_denoise_guided call spent its time."""
     _fields_ = [
