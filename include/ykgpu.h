@@ -103,13 +103,27 @@ enum {
   YK_ERR_NO_SCENE = 5     /* render before ykgpu_set_scene                                   */
 };
 
-/* One sphere<T, M> of the world tuple (sphere.hpp:16-23), in tuple order. 80 bytes. */
+/* One sphere<T, M> of the world tuple (sphere.hpp:16-23), in tuple order. 80 bytes.
+ * Every field is finite and the radius is not zero (math::sqrt need not end on a NaN or an
+ * infinity); within that the kernels take every value as the reference's arithmetic does, pinned
+ * bit for bit by tests/test_gpu_edge_materials.py:
+ *   radius  may be negative for any material: the outward normal (p - c) / radius then points
+ *           inwards, so the outside is the back face (a hollow shell inside a dielectric)
+ *   albedo  any finite value: 0, above 1, negative and subnormal components are multiplied as
+ *           they are.  (A pixel whose sum comes out negative is outside to_color3b's domain: the
+ *           reference's math::sqrt need not end on a negative mean.)
+ *   fuzz    any finite value, above 1 included; at or below 0 it means none (the reference's
+ *           metal, no random draw).  It is tested as a double: a fuzz that is positive in double
+ *           and 0 as a float still draws its four words under YK_PRECISION_FP32, as
+ *           render<float> would, and adds nothing
+ *   ior     any finite positive value, below 1 included (total internal reflection then happens
+ *           on the front face) */
 typedef struct yk_sphere {
   double center[3];
-  double radius;    /* may be negative (hollow dielectric shell, extension)              */
+  double radius;    /* may be negative (any material; see above)                          */
   double albedo[3]; /* lambertian / metal albedo (material.hpp:39,57)                    */
-  double fuzz;      /* metal only; 0 = the reference's metal (no random draw)            */
-  double ior;       /* dielectric only                                                    */
+  double fuzz;      /* metal only; <= 0: the reference's metal (no random draw)          */
+  double ior;       /* dielectric only; > 0                                               */
   uint32_t material;/* YK_MATERIAL_*                                                      */
   uint32_t reserved;
 } yk_sphere;

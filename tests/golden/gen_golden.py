@@ -90,6 +90,9 @@ SCENE_FILES = {
     "final48.yks": ("uecraytracing_amd/scenes/final_seed42.yks", 48),
     "glass48.yks": ("uecraytracing_amd/scenes/glass_seed42.yks", 48),
 }
+# edge materials (tests/edge_materials.py): scenes written in Python, fixtures written from the
+# builders; refractive indices, fuzz, albedos and radii at the values the kernels' shortcuts depend on
+PY_SCENE_FILES = ("matedge24.yks", "inside_glass5.yks", "room5.yks", "glasswalls5.yks")
 CASES_FILE = [
     ("rtiow5.yks", 96, 54, 16, 50, 404, True, False, False),
     ("rtiow5.yks", 200, 112, 8, 50, 404, False, False, False),   # config 1 shape on config 2's scene
@@ -99,6 +102,19 @@ CASES_FILE = [
     ("final48.yks", 96, 54, 8, 50, 404, True, False, True),
     ("glass48.yks", 64, 36, 8, 200, 404, True, False, False),     # config 5: depth 200, glass-heavy
     ("glass48.yks", 64, 36, 8, 200, 404, True, True, False),
+    ("matedge24.yks", 32, 18, 4, 50, 404, True, False, False),
+    ("matedge24.yks", 32, 18, 4, 50, 404, True, True, False),
+    ("matedge24.yks", 32, 18, 4, 50, 404, True, False, True),
+    ("matedge24.yks", 32, 18, 4, 50, 404, True, True, True),
+    ("inside_glass5.yks", 32, 18, 4, 50, 404, True, False, False),
+    ("inside_glass5.yks", 32, 18, 4, 50, 404, True, True, False),
+    ("inside_glass5.yks", 32, 18, 4, 50, 404, True, False, True),
+    ("room5.yks", 16, 9, 2, 50, 404, True, False, False),       # a closed room: every sum is +0.0
+    ("room5.yks", 16, 9, 2, 50, 404, True, True, False),
+    ("room5.yks", 16, 9, 2, 50, 404, True, False, True),
+    ("glasswalls5.yks", 32, 18, 4, 450, 404, True, False, False),  # glass met past 220 engine words
+    ("glasswalls5.yks", 32, 18, 4, 450, 404, True, True, False),
+    ("glasswalls5.yks", 32, 18, 4, 450, 404, True, False, True),
 ]
 
 # verbose level 3 (-l 3): the loop's console lines with every ray printed by the reference's own
@@ -228,6 +244,11 @@ def main():
     # 2b. configs 2-5 content through the reference's integrator (scene files, *_file modes)
     for fname, (src, n) in SCENE_FILES.items():
         print("scene file", fname, make_scene_fixture(fname, src, n), "spheres")
+    import edge_materials
+    for fname in PY_SCENE_FILES:
+        sph = edge_materials.scene(fname[:-4])
+        write_scene_file(os.path.join(HERE, fname), sph, edge_materials.CAM)
+        print("scene file", fname, len(sph), "spheres")
     for fname, W, H, spp, depth, seed0, keep_sums, f32, x128 in CASES_FILE:
         scene = fname[:-4]
         name = case_name(scene, W, H, spp, depth, seed0, f32, x128)
@@ -278,8 +299,14 @@ def main():
                                                ("ref4", 200, 112, 8, 50, True, False),
                                                ("walls2", 64, 36, 8, 200, True, False),
                                                ("mixed12", 96, 54, 16, 50, False, True),
-                                               ("walls2", 64, 36, 8, 200, False, True)]:
-        is_file = scene in ("final48", "glass48")
+                                               ("walls2", 64, 36, 8, 200, False, True),
+                                               ("matedge24", 32, 18, 4, 50, False, False),
+                                               ("matedge24", 32, 18, 4, 50, False, True),
+                                               ("matedge24", 32, 18, 4, 50, True, False),
+                                               ("glasswalls5", 32, 18, 4, 450, False, False),
+                                               ("glasswalls5", 32, 18, 4, 450, False, True),
+                                               ("glasswalls5", 32, 18, 4, 450, True, False)]:
+        is_file = scene in ("final48", "glass48", "matedge24", "glasswalls5")
         if is_file:
             sph, cam = golden_data.read_scene_file(os.path.join(HERE, scene + ".yks"))
         else:

@@ -3,7 +3,7 @@ queries" / DESIGN.md §6.6 restated in Python — not the code under test.
 
 One path at a time, as the reference runs it: raytracer<double,double>::ray_color(ray, world,
 max_depth, gen) with gen = Engine(seed) after discard(skip).  Every segment's hit is the ray queries'
-ordered scan (cast_ref.scan, t_max = +inf), the engine's words are the CPU oracle's
+ordered scan (cast_ref.scan, t_max = +inf; _hit runs its statements on Python floats), the engine's words are the CPU oracle's
 (oracle_lib.mt19937 / xor128), math::sqrt is oracle_lib.newton_sqrt, and every other statement is one
 IEEE double operation on Python floats (which never fuse), so the GPU must equal these bytes exactly:
   canonical = (u0 + u1 * 2^32) / 2^64 clamped to 1 - 2^-53;  uniform(a, b) = canonical * (b - a) + a
@@ -120,15 +120,45 @@ def _reflectance(cosine, ratio):
     return r0 + (1.0 - r0) * ((((x * x) * x) * x) * x)
 
 
-def _hit(spheres, o, d, t_min):
+def _hit_scan(spheres, o, d, t_min):
+    """The hit of one ray by cast_ref.scan itself (one-element arrays)."""
     closest, hit = cast_ref.scan(spheres, np.array([o], np.float64), np.array([d], np.float64),
                                  np.array([t_min], np.float64), np.array([INF], np.float64))
     return float(closest[0]), int(hit[0])
 
 
-def ray_color(spheres, E, o, d, seed, skip=0, max_depth=50, t_min=records.T_MIN, rng=records.RNG_MT19937, trace=None):
+def _hit(spheres, o, d, t_min):
+    """cast_ref.scan's statements for one ray on Python floats (t_max = +inf): the same IEEE double
+    operations in the same order, some twenty times as fast as one-element arrays.  Pinned to
+    _hit_scan by tests/test_edge_materials.py."""
+    a = _dot(d, d)
+    closest, hit = INF, -1
+    for i, sp in enumerate(spheres):
+        c, radius = sp.center, sp.radius
+        oc = (o[0] - c[0], o[1] - c[1], o[2] - c[2])
+        half_b = _dot(oc, d)
+        cc = _dot(oc, oc) - radius * radius
+        disc = half_b * half_b - a * cc
+        if disc < 0:
+            continue
+        sq = _sqrt(disc)
+        root = _div(-half_b - sq, a)
+        if root < t_min or closest < root:
+            root = _div(-half_b + sq, a)
+            if root < t_min or closest < root:
+                continue
+        closest, hit = root, i
+    return closest, hit
+
+
+def ray_color(spheres, E, o, d, seed, skip=0, max_depth=50, t_min=records.T_MIN, rng=records.RNG_MT19937, trace=None,
+              events=None):
     """One yk_radiance record, as a dict, for the ray (o, d) with Engine(seed) after discard(skip);
-    E = cast_ref.extent(spheres).  trace: a list that receives every segment's (o, d)."""
+    E = cast_ref.extent(spheres).  trace: a list that receives every segment's (o, d).  events: a
+    list that receives, per scatter, (sphere id, front face, branch, engine position before the
+    scatter's draws); the branch is "lambertian", "metal", "absorbed" (a metal that does not
+    scatter), or a dielectric's "tir" (total internal reflection: nothing drawn), "reflected" or
+    "refracted" (both after the reflect-or-refract uniform was drawn)."""
     o, d = tuple(float(v) for v in o), tuple(float(v) for v in d)
     rec = dict(colour=(0.0, 0.0, 0.0), t_first=0.0, id_first=NO_ID, id_last=NO_ID, words=0, segments=0, flags=0)
     g = None
@@ -160,6 +190,7 @@ def ray_color(spheres, E, o, d, seed, skip=0, max_depth=50, t_min=records.T_MIN,
             rec["t_first"], rec["id_first"] = t, hid
         rec["id_last"] = hid
         scattered, att = True, tuple(sp.albedo)
+        pos0, branch = g.pos, "lambertian"
         if sp.material == records.MATERIAL_LAMBERTIAN:
             ru = g.random_vec()
             ru = _divs(ru, _sqrt(_dot(ru, ru)))
@@ -174,6 +205,7 @@ def ray_color(spheres, E, o, d, seed, skip=0, max_depth=50, t_min=records.T_MIN,
                 ru = _divs(ru, _sqrt(_dot(ru, ru)))
                 nd = _add(nd, _mul(_mul(ru, k), sp.fuzz))
             scattered = _dot(nd, n) > 0
+            branch = "metal" if scattered else "absorbed"
         else:
             att = None  # (1, 1, 1): the product with 1.0 is exact
             ratio = (1.0 / sp.ior) if front else sp.ior
@@ -185,10 +217,14 @@ def ray_color(spheres, E, o, d, seed, skip=0, max_depth=50, t_min=records.T_MIN,
             cannot = ratio * st > 1.0
             if cannot or _reflectance(ct, ratio) > g.uniform(0.0, 1.0):
                 nd = _reflect(unit, n)
+                branch = "tir" if cannot else "reflected"
             else:
+                branch = "refracted"
                 perp = _mul(_add(unit, _mul(n, ct)), ratio)
                 pl = 1.0 - _dot(perp, perp)
                 nd = _add(perp, _mul(n, -_sqrt(-pl if pl < 0 else pl)))
+        if events is not None:
+            events.append((hid, front, branch, pos0))
         if not scattered:
             rec["flags"] = ABSORBED
             break
