@@ -1,5 +1,9 @@
-// yk_bvh.cpp — binned-SAH BVH builder (host).  See yk_bvh.hpp for the culling contract.
+// yk_bvh.cpp — binned-SAH BVH builder (host).  See yk_bvh.hpp for the culling contract.  Below it,
+// the other culling structure built from the scene and the camera: the sky-block classifier
+// (yk_sky.hpp).
 #include "yk_bvh.hpp"
+
+#include "yk_sky.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -347,3 +351,206 @@ std::vector<WideNode> wide_nodes(const Built& b, int32_t* root_code, uint32_t* w
 }
 
 }  // namespace ykbvh
+
+// =========================================================================================
+// The sky-block classifier (yk_sky.hpp has the ray family, the bound and what is never flagged)
+// =========================================================================================
+namespace yksky {
+namespace {
+
+struct V {
+  double x, y, z;
+};
+inline V vsub(V a, V b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+inline V vadd(V a, V b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+inline V vmul(V a, double s) { return {a.x * s, a.y * s, a.z * s}; }
+inline double vdot(V a, V b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+inline V vcross(V a, V b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+inline double vlen(V a) { return std::sqrt(vdot(a, a)); }
+inline V v3(const double* p) { return {p[0], p[1], p[2]}; }
+
+// The margins.  kRel widens the block's rectangle (in u, v: 1e-9 of the image, against roundings of
+// 1e-16) and every length the bound is made of; the camera's arithmetic moves a ray point by a few
+// ulps of the camera's own magnitudes times (1 + t), and the reference's discriminant
+// hb^2 - a c, evaluated in double, can accept a ray that misses the sphere by up to about
+// 4 eps |oc|^2 / |r|: both are covered a thousandfold and more (cam_scale, kDisc).
+constexpr double kRel = 1e-9;
+constexpr double kDisc = 0x1p-40;  // >= 4096 eps
+
+// The plane set of a rectangle of the focus plane: unit inward normals of the four sides, the unit
+// axis, and f_min; ok == false: nothing may be excluded with it
+struct Pyramid {
+  V n[5];
+  double fmin = 0;
+  double cone = 0;  // every direction of the family is within this angle of the axis n[4]
+  V corner[4];      // the rectangle's own corner directions F - O
+  bool ok = false;
+};
+
+struct Cam {
+  V o, llc, hor, ver;
+  double L = 0;      // bound of the lens offset's length
+  double scale = 0;  // |O| + |llc| + |hor| + |ver|: what the camera's roundings are relative to
+};
+
+Cam make_cam(const yk_camera& c) {
+  Cam k;
+  k.o = v3(c.origin), k.llc = v3(c.lower_left_corner), k.hor = v3(c.horizontal), k.ver = v3(c.vertical);
+  if (c.lens_radius > 0) {  // (the kernels' own test for "has a lens")
+    const V lu = v3(c.lens_u), lv = v3(c.lens_v);
+    k.L = c.lens_radius * std::sqrt(vdot(lu, lu) + vdot(lv, lv)) * (1 + kRel);
+  }
+  k.scale = vlen(k.o) + vlen(k.llc) + vlen(k.hor) + vlen(k.ver);
+  return k;
+}
+
+// the four corner directions F - O of the rectangle [u0, u1] x [v0, v1] of the focus plane
+void corners(const Cam& c, double u0, double u1, double v0, double v1, V (&e)[4]) {
+  const double us[4] = {u0, u1, u1, u0}, vs[4] = {v0, v0, v1, v1};
+  for (int k = 0; k < 4; ++k) e[k] = vsub(vadd(vadd(c.llc, vmul(c.hor, us[k])), vmul(c.ver, vs[k])), c.o);
+}
+
+Pyramid make_pyramid(const Cam& c, double u0, double u1, double v0, double v1) {
+  Pyramid p;
+  // the block's own corner directions (the rectangle widened against the roundings of u and v)
+  V in[4];
+  corners(c, u0 - kRel / 2, u1 + kRel / 2, v0 - kRel / 2, v1 + kRel / 2, in);
+  const double need = c.L * (1 + kRel);
+  // the axis: every focus point in front of the camera by more than the lens is wide
+  V w = vadd(vadd(in[0], in[1]), vadd(in[2], in[3]));
+  const double wl = vlen(w);
+  if (!(wl > 0) || !std::isfinite(wl)) return p;
+  w = vmul(w, 1.0 / wl);
+  double fmin = INFINITY;
+  for (int k = 0; k < 4; ++k) fmin = std::min(fmin, vdot(w, in[k]));
+  if (!(fmin * (1 - kRel) > need) || !std::isfinite(fmin)) return p;
+  // the cone of the directions: the corners' angles from the axis bound the rectangle's (a
+  // circular cone is convex), and the lens turns a direction F - O by at most asin(L / |F - O|)
+  double cmin = 1.0;
+  for (int k = 0; k < 4; ++k) cmin = std::min(cmin, vdot(w, in[k]) / vlen(in[k]));
+  p.cone = std::acos(std::max(-1.0, std::min(1.0, cmin))) + std::asin(need / (fmin * (1 - kRel))) + kRel;
+  if (!std::isfinite(p.cone)) return p;
+  // the sides: planes through O and the edges of the rectangle widened by g L in the focus plane,
+  // g raised until every one of the block's own corners is `need` inside every plane (the
+  // condition itself is what the bound rests on; the widening is only a way to meet it, and the
+  // least g that does excludes the most: a plane's tilt is about L / |F - O| over the pinhole's)
+  const double hl = vlen(c.hor), vl = vlen(c.ver);
+  for (double g = 1.0 + 0x1p-20; g <= 32.0; g *= (need > 0 ? 1.0625 : 64.0)) {
+    const double du = kRel + g * c.L / hl, dv = kRel + g * c.L / vl;
+    if (!std::isfinite(du) || !std::isfinite(dv)) return p;
+    V e[4];
+    corners(c, u0 - du, u1 + du, v0 - dv, v1 + dv, e);
+    bool good = true;
+    for (int k = 0; k < 4 && good; ++k) {
+      V n = vcross(e[k], e[(k + 1) & 3]);
+      const double len = vlen(n);
+      if (!(len > 0) || !std::isfinite(len)) return p;
+      n = vmul(n, 1.0 / len);
+      if (vdot(n, w) < 0) n = vmul(n, -1.0);  // inward
+      for (int j = 0; j < 4 && good; ++j) good = vdot(n, in[j]) >= need && vdot(n, in[j]) > 0;
+      p.n[k] = n;
+    }
+    if (!good) continue;
+    p.n[4] = w;
+    p.fmin = fmin * (1 - kRel);
+    for (int k = 0; k < 4; ++k) p.corner[k] = in[k];
+    p.ok = true;
+    return p;
+  }
+  return p;
+}
+
+// true: no ray of the pyramid's family can hit the sphere (C, r)
+bool excluded(const Cam& c, const Pyramid& p, V C, double r) {
+  if (!p.ok) return false;
+  const V oc = vsub(C, c.o);
+  const double D = vlen(oc), ar = std::fabs(r);
+  const double reach = D + ar + c.L;
+  const double tmax = reach / (p.fmin - c.L);  // (only the roundings grow with t)
+  const double rho = (ar + c.L) * (1 + kRel) + kRel * (reach + (1 + tmax) * c.scale) + kDisc * reach * reach / ar;
+  if (!(rho >= 0) || !std::isfinite(rho)) return false;
+  for (int k = 0; k < 5; ++k)
+    if (vdot(p.n[k], oc) < -rho) return true;
+  // the cone test (what the planes miss beside a sphere that is large on the screen): from a lens
+  // point A the sphere, grown to rho - L for the roundings, lies within asin((rho - L) / |C - A|)
+  // of C - A, |C - A| >= D - L, and C - A within asin(L / D) of C - O; a direction farther from
+  // C - O than both and the cone's own angle together cannot hit
+  if (D - c.L > rho - c.L && D > c.L) {
+    const double theta = std::acos(std::max(-1.0, std::min(1.0, vdot(p.n[4], oc) / D)));
+    const double need = p.cone + std::asin(c.L / D) + std::asin((rho - c.L) / (D - c.L)) + kRel;
+    if (theta > need) return true;
+  }
+  return false;
+}
+
+// true: the pinhole ray through every point of the pyramid's rectangle hits the sphere (C, r) in
+// front of the camera, so no block inside the rectangle is a sky block (the lens point 0 belongs to
+// every family).  The directions from O that hit a sphere form a convex cone, so the four corners
+// decide; 1e-6 keeps the test clear of its own roundings.  Only saves work: such blocks would fail
+// `excluded` one by one.
+bool covered(const Cam& c, const Pyramid& p, V C, double r) {
+  if (!p.ok) return false;
+  const V oc = vsub(C, c.o);
+  const double tan2 = vdot(oc, oc) - r * r;  // (distance to the tangent points)^2
+  if (!(tan2 > 0)) return false;
+  for (int k = 0; k < 4; ++k) {
+    const double a = vdot(p.corner[k], oc);
+    if (!(a > 0) || !(a * a > tan2 * vdot(p.corner[k], p.corner[k]) * (1 + 1e-6))) return false;
+  }
+  return true;
+}
+
+// image row of tile row t, image column of tile column j (yk_render_params' banded sets)
+inline uint64_t banded(uint32_t begin, uint32_t stride, uint32_t L, uint32_t t) {
+  return (uint64_t)begin + ((((uint64_t)(t >> L)) * stride) << L) + (t & ((1u << L) - 1u));
+}
+
+}  // namespace
+
+std::vector<uint8_t> sky_blocks(const yk_camera& cam, const double* centers, const double* radii, uint32_t n,
+                                const Tile& t, uint32_t tw, uint32_t th) {
+  const uint32_t bx = (t.col_count + tw - 1) / tw, by = (t.row_count + th - 1) / th;
+  std::vector<uint8_t> flag((size_t)bx * by, 0);
+  if (!bx || !by || !t.W || !t.H) return flag;
+  const Cam c = make_cam(cam);
+  const double W = (double)t.W, H = (double)t.H;
+  // the pyramid of tile columns [j0, j1) x tile rows [r0, r1): both maps increase, so the first
+  // and last entries bound the pixels' rectangle in the image
+  auto pyramid = [&](uint32_t j0, uint32_t j1, uint32_t r0, uint32_t r1) {
+    const double x0 = (double)banded(t.col_begin, t.col_stride, t.col_band_log2, j0);
+    const double x1 = (double)banded(t.col_begin, t.col_stride, t.col_band_log2, j1 - 1);
+    const double y0 = (double)banded(t.row_begin, t.row_stride, t.row_band_log2, r0);
+    const double y1 = (double)banded(t.row_begin, t.row_stride, t.row_band_log2, r1 - 1);
+    return make_pyramid(c, x0 / W, (x1 + 1) / W, (H - 1 - y1) / H, (H - y0) / H);
+  };
+  constexpr uint32_t kSuper = 8;
+  std::vector<uint32_t> left;
+  for (uint32_t sj = 0; sj < by; sj += kSuper)
+    for (uint32_t si = 0; si < bx; si += kSuper) {
+      const uint32_t ei = std::min(bx, si + kSuper), ej = std::min(by, sj + kSuper);
+      const Pyramid sp = pyramid(si * tw, std::min(t.col_count, ei * tw), sj * th, std::min(t.row_count, ej * th));
+      left.clear();
+      bool hidden = false;  // some sphere fills the whole super-block: its blocks stay unflagged
+      for (uint32_t s = 0; s < n && !hidden; ++s) {
+        if (excluded(c, sp, v3(centers + 3 * (size_t)s), radii[s])) continue;
+        left.push_back(s);
+        hidden = covered(c, sp, v3(centers + 3 * (size_t)s), radii[s]);
+      }
+      if (hidden) continue;
+      for (uint32_t j = sj; j < ej; ++j)
+        for (uint32_t i = si; i < ei; ++i) {
+          bool sky = sp.ok;  // (an undecidable super-block: every sphere is in `left`)
+          if (!left.empty()) {
+            const Pyramid bp =
+                pyramid(i * tw, std::min(t.col_count, (i + 1) * tw), j * th, std::min(t.row_count, (j + 1) * th));
+            sky = bp.ok;
+            for (size_t k = 0; sky && k < left.size(); ++k)
+              sky = excluded(c, bp, v3(centers + 3 * (size_t)left[k]), radii[left[k]]);
+          }
+          flag[(size_t)j * bx + i] = sky ? 1 : 0;
+        }
+    }
+  return flag;
+}
+
+}  // namespace yksky

@@ -52,6 +52,7 @@ uint64_t device_bytes(const ykgpu_context* ctx) {
   b += ctx->retry_cap * sizeof(uint4);
   b += (uint64_t)ctx->order_slots * sizeof(uint32_t) + (uint64_t)ctx->counter_cap * sizeof(uint32_t);
   b += kCounters * sizeof(unsigned long long);
+  b += sky_bytes(ctx);
   if (ctx->d_mt) b += 2ull * ctx->scratch_lanes * ykd::kMtN * sizeof(uint32_t);
   if (ctx->d_ids) b += 2ull * ctx->id_lanes * ctx->id_stride * sizeof(uint16_t);
   b += ctx->rgb_cap + ctx->sums_cap * sizeof(double);
@@ -322,6 +323,12 @@ int ykgpu_context_destroy(ykgpu_context* ctx) {
   (void)hipFree(ctx->d_order);
   (void)hipFree(ctx->d_col);
   (void)hipFree(ctx->d_acc);
+  (void)hipFree(ctx->d_sky_path);
+  (void)hipFree(ctx->d_sky_list);
+  (void)hipFree(ctx->d_sky_acc);
+  (void)hipFree(ctx->d_sky_mt);
+  (void)hipFree(ctx->d_sky_off);
+  if (ctx->sky_ev) (void)hipEventDestroy(ctx->sky_ev);
   ctx->t64.release();
   ctx->t32.release();
   (void)hipFree(ctx->d_mt);
@@ -478,6 +485,9 @@ int ykgpu_set_scene(ykgpu_context* ctx, const yk_sphere* spheres, uint32_t count
   YK_HIP(hipStreamSynchronize(ctx->stream));
   ctx->nspheres = count;
   ctx->cam = *camera;
+  // the sky-block classifier's view of the scene; its cached blocks are keyed by scene_gen
+  ctx->sky_centers = centers;
+  ctx->sky_radii = radii;
   // the ray queries' domain rule (include/ykgpu.h): E = max_i(max(|cx|, |cy|, |cz|) + |r|)
   double ext = 0;
   for (uint32_t i = 0; i < count; ++i) {

@@ -282,6 +282,13 @@ __device__ __forceinline__ uint32_t mt_seed_from(uint32_t x, uint32_t i) {  // x
   }
   return x;
 }
+// M_gen_rand (random.hpp:114-131): the 624 words of the state, in place
+__device__ __forceinline__ void mt_twist(uint32_t* st) {
+  uint32_t k = 0;
+  for (; k < kMtN - kMtM; ++k) st[k] = st[k + kMtM] ^ mt_mix(st[k], st[k + 1]);
+  for (; k < kMtN - 1; ++k) st[k] = st[k + kMtM - kMtN] ^ mt_mix(st[k], st[k + 1]);
+  st[kMtN - 1] = st[kMtM - 1] ^ mt_mix(st[kMtN - 1], st[0]);
+}
 __device__ __noinline__ uint32_t mt_slow(uint32_t* st, uint32_t x227, uint32_t j) {
   const uint32_t idx = j % kMtN;
   if (j == kLazyDraws) {
@@ -292,13 +299,33 @@ __device__ __noinline__ uint32_t mt_slow(uint32_t* st, uint32_t x227, uint32_t j
       st[i] = x;
     }
   }
-  if (j == kLazyDraws || idx == 0) {
-    uint32_t k = 0;
-    for (; k < kMtN - kMtM; ++k) st[k] = st[k + kMtM] ^ mt_mix(st[k], st[k + 1]);
-    for (; k < kMtN - 1; ++k) st[k] = st[k + kMtM - kMtN] ^ mt_mix(st[k], st[k + 1]);
-    st[kMtN - 1] = st[kMtM - 1] ^ mt_mix(st[kMtN - 1], st[0]);
-  }
+  if (j == kLazyDraws || idx == 0) mt_twist(st);
   return st[idx];
+}
+
+// A whole engine in global memory from its first draw (yk_sky_samples' cold path, yk_pipeline.hip):
+// seed() (random.hpp:69-81), then a twist before draw 0 and after every 624 draws.  n: words drawn.
+struct MtFull {
+  uint32_t* st;
+  uint32_t idx, n;
+};
+__device__ inline void mt_full_seed(MtFull& g, uint32_t seed) {
+  uint32_t x = seed;
+  g.st[0] = x;
+  for (uint32_t i = 1; i < kMtN; ++i) {
+    x = mt_seed_step(x, i);
+    g.st[i] = x;
+  }
+  g.idx = kMtN;
+  g.n = 0;
+}
+__device__ inline uint32_t mt_full_next(MtFull& g) {
+  if (g.idx >= kMtN) {
+    mt_twist(g.st);
+    g.idx = 0;
+  }
+  ++g.n;
+  return mt_temper(g.st[g.idx++]);
 }
 
 // The lazy cursors' draw without the check for the scratch engine: only for callers that know
@@ -379,6 +406,8 @@ template <bool kLazy = false>
 __device__ __forceinline__ uint32_t rng_next(MtLane& g) { return kLazy ? mt_next_lazy(g) : mt_next(g); }
 template <bool kLazy = false>
 __device__ __forceinline__ uint32_t rng_next(X128Lane& g) { return x128_next(g); }
+template <bool kLazy = false>
+__device__ __forceinline__ uint32_t rng_next(MtFull& g) { return mt_full_next(g); }
 
 // generate_canonical<double,53> (random.hpp:161-183): two draws (both engines have
 // min 0, max 2^32-1, so r = 2^32 and m = 2), sum = u0 + u1*2^32 rounded once, divided by 2^64

@@ -90,6 +90,22 @@ struct ykgpu_context {
   uint32_t* d_order = nullptr;  // processing slot → tile pixel, for (order_w, order_rows)
   uint32_t order_w = 0, order_rows = 0, order_slots = 0, order_stride = 0, order_mode = 0;
   size_t warm_cap = 0;
+  // Sky blocks (yk_sky.hpp): the scene on the host for the classifier, and for the
+  // key — scene generation, image and tile geometry, block shape — the processing order over the
+  // blocks that can hit something (the path pipeline's), the slots of the sky blocks
+  // (yk_sky_samples'), that kernel's running sums (3 x sky_slots) and yk_sky_redo's list and
+  // engines (a count, a word per sky slot, kSkyEngines x 624 words).  Built at most once per key
+  // (ensure_sky).
+  std::vector<double> sky_centers, sky_radii;
+  std::vector<uint64_t> sky_key;
+  uint32_t* d_sky_path = nullptr;
+  uint32_t* d_sky_list = nullptr;
+  double* d_sky_acc = nullptr;
+  uint32_t* d_sky_mt = nullptr;
+  uint32_t* d_sky_off = nullptr;  // a word per block: its place in its order (yk_sky_split)
+  size_t sky_cap = 0;             // slots of the whole order the five buffers were allocated for
+  uint32_t sky_path_slots = 0, sky_slots = 0, sky_full_slots = 0;
+  hipEvent_t sky_ev = nullptr;  // the end of a call of sky blocks only (no reduce follows its samples)
   hipStream_t stream = nullptr;
   hipStream_t aux = nullptr;  // the MT warm-ups run here, beside the render launches
   hipStream_t red = nullptr;  // the ordered reduces run here, beside the next render launch
@@ -262,6 +278,14 @@ std::vector<uint32_t> build_order(uint32_t W, uint32_t rows, uint32_t stride, ui
 hipError_t create_render_stream(hipStream_t* s);
 int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, double* sums_dev, hipStream_t st,
            uint32_t s_begin, uint32_t s_end, ykgpu_film* film);
+// the sky blocks' device memory: both orders, the running sums, yk_sky_redo's list and engines
+constexpr uint32_t kSkyEngines = 64;  // (one per thread of yk_sky_redo's block)
+inline uint64_t sky_bytes(const ykgpu_context* ctx) {
+  if (!ctx->sky_cap) return 0;
+  const uint64_t full = ctx->sky_cap;  // (allocated for the whole tile, whatever the view flags)
+  return (full + 256 + full + full / 64 + 1 + full + (uint64_t)kSkyEngines * ykd::kMtN) * sizeof(uint32_t) +
+         full * 3 * sizeof(double);
+}
 // yk_context.hip
 uint64_t device_bytes(const ykgpu_context* ctx);
 int finish_stats(ykgpu_context* ctx);

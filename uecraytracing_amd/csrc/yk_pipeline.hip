@@ -16,6 +16,9 @@
 //     streams), then yk_reduce_samples (here: the reference's strictly sequential per-pixel sum
 //     and to_color3b, third stream) or, for a film, yk_film_reduce / yk_film_reduce_masked.
 //     Back-to-back calls overlap (launches numbered across calls).
+//   * the blocks of the tile whose camera rays can hit nothing (sky blocks, yk_sky.hpp) are not in
+//     the order those three kernels run over: yk_sky_samples (here, reduce stream) renders and
+//     folds their samples, launch by launch (the production instance's one-shot calls only).
 //   * a path kernel is one persistent grid of 768-thread workgroups, one per CU (12 waves,
 //     3 per SIMD at 112 VGPRs, beside three 48-VGPR warm-up waves), with
 //     the scene (BVH, geometry and material tables) in LDS, over SAMPLE SLOTS: a lane runs one path at a
@@ -45,6 +48,7 @@
 #include "yk_film_internal.hpp"
 #include "yk_host_internal.hpp"
 #include "yk_schedule.hpp"
+#include "yk_sky.hpp"
 
 namespace {
 
@@ -321,6 +325,19 @@ struct ReduceArgs {
   uint32_t npix_slots, nsl, ks, spp;
   uint32_t first, last, pad0, pad1;
 };
+// tile pixel q's sums after its last sample: the sums themselves when asked for, and to_color3b
+__device__ __forceinline__ void pixel_store(double* sums, uint8_t* rgb, uint32_t q, const double (&a)[3],
+                                            uint32_t spp_u) {
+  const size_t o3 = (size_t)q * 3;
+  const double spp = (double)spp_u;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    if (sums) sums[o3 + c] = a[c];
+    double v = ykd::nsqrt(a[c] / spp);
+    v = (v < 0.0) ? 0.0 : (0.999 < v) ? 0.999 : v;
+    rgb[o3 + c] = (uint8_t)(uint32_t)(v * 256);
+  }
+}
 __device__ __forceinline__ void reduce_slot(const ReduceArgs& ra, uint32_t p) {
   const uint32_t q = ra.order[p];
   if (q == kNoPixel) return;
@@ -337,19 +354,157 @@ __device__ __forceinline__ void reduce_slot(const ReduceArgs& ra, uint32_t p) {
     for (int c = 0; c < 3; ++c) ra.acc[(size_t)c * ra.npix_slots + p] = a[c];
     return;
   }
-  const size_t o3 = (size_t)q * 3;
-  const double spp = (double)ra.spp;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    if (ra.sums) ra.sums[o3 + c] = a[c];
-    double v = ykd::nsqrt(a[c] / spp);
-    v = (v < 0.0) ? 0.0 : (0.999 < v) ? 0.999 : v;
-    ra.rgb[o3 + c] = (uint8_t)(uint32_t)(v * 256);
-  }
+  pixel_store(ra.sums, ra.rgb, q, a, ra.spp);
 }
 __global__ __launch_bounds__(256) void yk_reduce_samples(ReduceArgs ra) {
   for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < ra.npix_slots; p += gridDim.x * blockDim.x)
     reduce_slot(ra, p);
+}
+
+// The samples of a launch for the pixels of the SKY BLOCKS (yk_sky.hpp): no camera ray
+// of such a pixel can hit a sphere, so a sample is the sky of its camera ray (raytracer.hpp:35-36)
+// and needs neither a start record, a slot of the path kernel nor a colour record.  One thread per
+// sky slot runs the pixel's samples [s0, s0 + ks) in sample order: the warm-up's seed and walk
+// (kWalkIlp consecutive samples of the pixel interleaved), the two jitter canonicals, the lens
+// rejection loop, camera_ray, then the path kernel's own sky expression (yk_render_f64.hip: the
+// shared normalisation's nsqrt and range-checked division, t = (un.y + 1) / 2, the three lerps) and
+// the fold a = a + c that yk_reduce_samples performs, carried from launch to launch in acc; after
+// the last launch pixel_store.  A pixel with a lens loop that outruns the lazy cursors (never seen:
+// ~55 rejections) is left to yk_sky_redo.  Counter seeds only.  The warm-up's register budget: its waves share the SIMDs
+// with the render's the same way.
+struct SkyArgs {
+  uint32_t W, H, spp, seed0, row_begin, row_stride, band_log2;
+  uint32_t Wt, col_begin, col_stride, col_band;
+  uint32_t w_m, w_sh;  // fdiv magic numbers of the tile width
+  uint32_t lens, s0, ks, first, last;
+  uint32_t n;  // sky slots
+  yk_camera cam;
+  double w_d, h_d, inv_w, inv_h;
+  const uint32_t* list;  // sky slot → tile pixel (kNoPixel: empty slot of an edge block)
+  double* acc;           // running sums, acc[c * n + p]
+  uint8_t* rgb;
+  double* sums;
+  uint32_t* engines;             // [0]: slots listed for yk_sky_redo, [1, 1 + n): the list, then its 64 engines
+  unsigned long long* counters;  // [3]: MT fallbacks
+};
+// the sky of the camera ray of pixel (xx, y) for the start's draws, added to the pixel's sums
+__device__ __forceinline__ void sky_add(const SkyArgs& sa, uint32_t xx, uint32_t y, double uc, double vc, double px,
+                                        double py, double (&a)[3]) {
+  v3 o, d;
+  camera_ray(sa.cam, sa.w_d, sa.inv_w, sa.h_d, sa.inv_h, sa.H, xx, y, uc, vc, sa.lens != 0, px, py, o, d);
+  // sky (raytracer.hpp:35-36), as the path kernel's shade block computes it
+  const double len = ykd::nsqrt(ykd::len2(d));
+  const v3 un = ykd::divs_fast(d, len);
+  const double t = (un.y + 1.0) / 2;
+  a[0] = a[0] + ((1.0 - t) * 1.0 + t * 0.5);
+  a[1] = a[1] + ((1.0 - t) * 1.0 + t * 0.7);
+  a[2] = a[2] + ((1.0 - t) * 1.0 + t * 1.0);
+}
+// words the lens loop may draw from the lazy cursors (test builds lower it: the full engine then runs)
+#ifndef YK_SKY_LAZY_WORDS
+#define YK_SKY_LAZY_WORDS ykd::kLazyDraws
+#endif
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(YK_DEFER_VGPRS / 2))) void yk_sky_samples(SkyArgs sa) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= sa.n) return;
+  const uint32_t q = sa.list[p];
+  if (q == kNoPixel) return;
+  const uint32_t tr = fdiv(q, sa.w_m, sa.w_sh);
+  const uint32_t xx = tile_col_x(sa.col_begin, sa.col_stride, sa.col_band, q - tr * sa.Wt);
+  const uint32_t y = tile_row_y(sa.row_begin, sa.row_stride, sa.band_log2, tr);
+  // (the counter seed of sample s0; sample s0 + k is this + k in uint32 arithmetic)
+  const uint32_t seed_s0 = ykd::sample_seed(0u, 0ull, sa.seed0, y, xx, sa.W, sa.spp, sa.s0);
+  double a[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) a[c] = sa.first ? 0.0 : sa.acc[(size_t)c * sa.n + p];
+  for (uint32_t k = 0; k < sa.ks; k += kWalkIlp) {
+    uint32_t x[kWalkIlp];
+#pragma unroll
+    for (uint32_t j = 0; j < kWalkIlp; ++j) x[j] = seed_s0 + k + j;  // (past ks: walked, not used)
+    ykd::mt_walk397xn<kWalkIlp>(x);
+#pragma unroll
+    for (uint32_t j = 0; j < kWalkIlp; ++j) {
+      if (k + j >= sa.ks) break;
+      ykd::MtLane g;
+      g.state = nullptr;
+      ykd::mt_start_from(g, seed_s0 + k + j, x[j]);
+      const double uc = ykd::canonical<true>(g);  // source.cpp:162
+      const double vc = ykd::canonical<true>(g);  // source.cpp:163
+      double px = 0.0, py = 0.0;
+      if (sa.lens) {
+        for (;;) {  // thin-lens extension: random_in_unit_disk by rejection, x then y
+          if (g.j + 4 > YK_SKY_LAZY_WORDS) {
+            // (never seen) the lens loop outran the lazy cursors: the pixel keeps its carried sums
+            // and yk_sky_redo runs this launch's samples of it from a whole engine
+            sa.engines[1 + atomicAdd(sa.engines, 1u)] = p;
+            return;
+          }
+          px = ykd::uniform<true>(g, -1, 1);
+          py = ykd::uniform<true>(g, -1, 1);
+          if (px * px + py * py < 1.0) break;
+        }
+      }
+      sky_add(sa, xx, y, uc, vc, px, py, a);
+    }
+  }
+  if (!sa.last) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) sa.acc[(size_t)c * sa.n + p] = a[c];
+    return;
+  }
+  pixel_store(sa.sums, sa.rgb, q, a, sa.spp);
+}
+// The sky slots yk_sky_samples listed (never seen: a lens loop of ~55 rejections): this launch's
+// samples of each from the carried sums, every draw from a whole engine in global memory, seeded
+// and twisted as random.hpp:69-81, 114-131 do, one engine per thread of the one block.  A sample
+// that drew past the lazy cursors' words counts as an MT fallback, as a start the render makes
+// itself would.  Clears the list.  (The same register budget: its one wave, which almost always
+// finds the list empty, must fit beside the render's and the warm-up's waves without waiting.)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(YK_DEFER_VGPRS / 2))) void yk_sky_redo(SkyArgs sa) {
+  const uint32_t count = sa.engines[0];
+  uint32_t fallbacks = 0;
+  ykd::MtFull g;
+  g.st = sa.engines + 1 + sa.n + (size_t)threadIdx.x * ykd::kMtN;
+  for (uint32_t e = threadIdx.x; e < count; e += 64u) {
+    const uint32_t p = sa.engines[1 + e], q = sa.list[p];
+    const uint32_t tr = fdiv(q, sa.w_m, sa.w_sh);
+    const uint32_t xx = tile_col_x(sa.col_begin, sa.col_stride, sa.col_band, q - tr * sa.Wt);
+    const uint32_t y = tile_row_y(sa.row_begin, sa.row_stride, sa.band_log2, tr);
+    double a[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a[c] = sa.first ? 0.0 : sa.acc[(size_t)c * sa.n + p];
+    for (uint32_t k = 0; k < sa.ks; ++k) {
+      ykd::mt_full_seed(g, ykd::sample_seed(0u, 0ull, sa.seed0, y, xx, sa.W, sa.spp, sa.s0 + k));
+      const double uc = ykd::canonical(g);
+      const double vc = ykd::canonical(g);
+      double px, py;
+      do {  // (only a lens loop comes here)
+        px = ykd::uniform(g, -1, 1);
+        py = ykd::uniform(g, -1, 1);
+      } while (!(px * px + py * py < 1.0));
+      if (g.n > ykd::kLazyDraws) ++fallbacks;
+      sky_add(sa, xx, y, uc, vc, px, py, a);
+    }
+    if (sa.last) {
+      pixel_store(sa.sums, sa.rgb, q, a, sa.spp);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) sa.acc[(size_t)c * sa.n + p] = a[c];
+    }
+  }
+  if (fallbacks) atomicAdd(&sa.counters[3], (unsigned long long)fallbacks);
+  __syncthreads();
+  if (threadIdx.x == 0) sa.engines[0] = 0u;
+}
+
+// The whole processing order split into the path's and the sky list (ensure_sky): block b's per
+// slots go to place off[b] of the order its bit 31 names.
+__global__ __launch_bounds__(256) void yk_sky_split(const uint32_t* order, const uint32_t* off, uint32_t* path,
+                                                    uint32_t* list, uint32_t n, uint32_t per) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t b = i / per, o = off[b];
+  ((o & 0x80000000u) ? list : path)[(size_t)(o & 0x7fffffffu) * per + (i - b * per)] = order[i];
 }
 
 // A launch's sample colours folded into a film: s = s + c (the reference's left fold, continued
@@ -549,8 +704,8 @@ std::vector<uint32_t> build_order(uint32_t W, uint32_t rows, uint32_t stride, ui
     ord.resize((size_t)W * rows);
     for (size_t i = 0; i < ord.size(); ++i) ord[i] = (uint32_t)i;
   } else {
-    const uint32_t th = stride <= 1 ? kTile : (stride <= 4 ? std::max(1u, kTile / 2) : std::max(1u, kTile / 4));
-    const uint32_t tw = kTile * kTile / th;
+    uint32_t tw, th;
+    order_block(stride, tw, th);
     const uint32_t bx = (W + tw - 1) / tw, by = (rows + th - 1) / th;
     ord.reserve((size_t)bx * by * tw * th);
     for (uint32_t jj = 0; jj < by; ++jj)
@@ -580,6 +735,88 @@ static int ensure_order(ykgpu_context* ctx, uint32_t W, uint32_t rows, uint32_t 
   ctx->order_stride = stride;
   ctx->order_mode = mode;
   ctx->order_slots = (uint32_t)ord.size();
+  return YK_OK;
+}
+
+// Sky blocks (yk_sky.hpp).  The production instance alone takes them: FP64, mt19937,
+// counter seeds, no flags, a scene in LDS, a one-shot call (every launch() of the render entry
+// points and of a device group renders its whole tile).  Everything else — the counting, trace,
+// linear-scan and one-lane instances, random-device seeds, xor128, FP32, films, max_depth 0 (a
+// black image, not sky) — keeps the whole processing order.  (A/B knob: YKGPU_SKY=0.)
+static bool sky_eligible(const yk_render_params* p, const ykgpu_film* film, const DevTree::Plan& plan) {
+  if (const char* e = ab_knob("YKGPU_SKY"))
+    if (std::atoi(e) == 0) return false;
+  return kTile != 0 && !film && p->precision == YK_PRECISION_FP64 && p->rng == YK_RNG_MT19937 &&
+         p->seed_mode == YK_SEED_COUNTER && p->flags == 0 && p->max_depth > 0 && plan.in_lds;
+}
+// The two orders of the call's tile: ctx->d_sky_path, the processing order over the blocks that can
+// hit something (padded to whole warm-up blocks of 256 slots), and ctx->d_sky_list, the slots of
+// the sky blocks.  A function of the scene, the camera and the geometry: built once per key and
+// kept; without a sky block both stay empty and the call runs on ctx->d_order as ever.
+static int ensure_sky(ykgpu_context* ctx, const yk_render_params* p) {
+  const uint32_t Wt = tile_width(p), rows = p->row_count, stride = order_stride(p), mode = order_mode();
+  const uint32_t col_begin = p->col_count ? p->col_begin : 0, col_stride = p->col_count ? p->col_stride : 1;
+  const uint32_t col_band = p->col_count ? p->col_band_log2 : 0;
+  const std::vector<uint64_t> key = {ctx->scene_gen, p->image_width, p->image_height, p->row_begin, rows,
+                                     p->row_stride,  p->row_band_log2, col_begin,     Wt,           col_stride,
+                                     col_band,       stride,           mode};
+  if (ctx->sky_key == key) return YK_OK;
+  // the whole order stays the geometry's (kept across scenes, as ever); the two orders are split
+  // from it on the device, so a new scene or camera costs the classifier (~2 ms for the frame), a
+  // word per block uploaded and one small kernel — no allocation while the tile's size stays
+  if (int rc = ensure_order(ctx, Wt, rows, stride)) return rc;
+  uint32_t tw, th;
+  order_block(stride, tw, th);
+  const yksky::Tile tile{p->image_width, p->image_height, p->row_begin, rows,       p->row_stride,
+                         p->row_band_log2, col_begin,      Wt,           col_stride, col_band};
+  const std::vector<uint8_t> flag = yksky::sky_blocks(ctx->cam, ctx->sky_centers.data(), ctx->sky_radii.data(),
+                                                      ctx->nspheres, tile, tw, th);
+  const uint32_t bx = (Wt + tw - 1) / tw, by = (rows + th - 1) / th, per = tw * th;
+  // each block's place in its order (bit 31: the sky list), in the whole order's block sequence
+  std::vector<uint32_t> off((size_t)bx * by);
+  uint32_t npath = 0, nlist = 0;
+  for (uint32_t jj = 0; jj < by; ++jj)
+    for (uint32_t i = 0; i < bx; ++i) {
+      const uint32_t j = mode == 1 ? by - 1 - jj : jj;  // (build_order's block rows)
+      off[(size_t)jj * bx + i] = flag[(size_t)j * bx + i] ? (0x80000000u | nlist++) : npath++;
+    }
+  ctx->sky_key.clear();
+  ctx->sky_path_slots = ctx->sky_slots = ctx->sky_full_slots = 0;
+  if (nlist) {
+    const size_t full = ctx->order_slots;  // == bx * by * per
+    // (earlier calls may still read the orders about to be rewritten; after ykgpu_set_scene nothing runs)
+    if (int rc = quiesce(ctx)) return rc;
+    if (full > ctx->sky_cap) {
+      for (void* q : {(void*)ctx->d_sky_path, (void*)ctx->d_sky_list, (void*)ctx->d_sky_acc, (void*)ctx->d_sky_mt,
+                      (void*)ctx->d_sky_off})
+        (void)hipFree(q);
+      ctx->d_sky_path = ctx->d_sky_list = ctx->d_sky_mt = ctx->d_sky_off = nullptr;
+      ctx->d_sky_acc = nullptr;
+      ctx->sky_cap = 0;
+      YK_HIP(hipMalloc(&ctx->d_sky_path, (full + 256) * sizeof(uint32_t)));
+      YK_HIP(hipMalloc(&ctx->d_sky_list, full * sizeof(uint32_t)));
+      YK_HIP(hipMalloc(&ctx->d_sky_acc, full * 3 * sizeof(double)));
+      // yk_sky_redo's list (a count, then a word per sky slot) and its engines
+      YK_HIP(hipMalloc(&ctx->d_sky_mt, (1 + full + (size_t)kSkyEngines * ykd::kMtN) * sizeof(uint32_t)));
+      YK_HIP(hipMalloc(&ctx->d_sky_off, off.size() * sizeof(uint32_t)));
+      ctx->sky_cap = full;
+    }
+    if (!ctx->sky_ev) YK_HIP(hipEventCreateWithFlags(&ctx->sky_ev, hipEventDisableTiming));
+    const size_t path_slots = ((size_t)npath * per + 255) / 256 * 256;  // (whole warm-up blocks)
+    YK_HIP(hipMemcpy(ctx->d_sky_off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(yk_sky_split, dim3((uint32_t)((full + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_order,
+                       ctx->d_sky_off, ctx->d_sky_path, ctx->d_sky_list, (uint32_t)full, per);
+    YK_HIP(hipGetLastError());
+    if (path_slots > (size_t)npath * per)
+      YK_HIP(hipMemsetAsync(ctx->d_sky_path + (size_t)npath * per, 0xff, (path_slots - (size_t)npath * per) * 4,
+                            ctx->stream));  // kNoPixel
+    YK_HIP(hipMemsetAsync(ctx->d_sky_mt, 0, sizeof(uint32_t), ctx->stream));
+    YK_HIP(hipStreamSynchronize(ctx->stream));  // (the call's kernels run on other streams)
+    ctx->sky_path_slots = (uint32_t)path_slots;
+    ctx->sky_slots = nlist * per;
+    ctx->sky_full_slots = (uint32_t)full;
+  }
+  ctx->sky_key = key;
   return YK_OK;
 }
 
@@ -627,7 +864,19 @@ static uint32_t warm_per_cu(bool f32) {
 // A warm-up's blocks for n slots, at most cap: each thread walks n / grid slots, at least
 // kWarmSlots; with ilp walks per lane the grid is trimmed so that a thread's slot count is a
 // multiple of ilp (no lane walks a chain for a slot it does not have, but in the last blocks)
-inline uint32_t warm_blocks_for(uint64_t n, uint64_t cap, uint32_t ilp) {
+// (align: the slots per sample of a culled order, a multiple of 256, or 0.  The frame's launches
+// have a grid whose stride is the slot count per sample — 8100 blocks x 256 = 1920 x 1080 — so a
+// lane's ilp walks are consecutive samples of one pixel and their processing-order reads coincide;
+// likewise the 8-way tile's, 8160 blocks = 8 x its slots; a culled order keeps that with a grid of
+// j x align / 256 blocks, the largest below the cap whose threads walk a multiple of ilp slots:
+// few blocks per CU — 897 for that tile's 256-spp launches at j = 1 — share the CUs unevenly, and
+// the warm-up is close to the critical path: the tile's synced call +1.6%, profiles/r18_sky_blocks/)
+inline uint32_t warm_blocks_for(uint64_t n, uint64_t cap, uint32_t ilp, uint64_t align = 0) {
+  if (align && align / 256 <= cap && n % align == 0) {
+    const uint64_t m = align / 256, ks = n / align;
+    for (uint64_t j = std::min(cap / m, ks / ilp); j >= 1; --j)
+      if (ks % (j * ilp) == 0 && ks / j >= kWarmSlots) return (uint32_t)(j * m);
+  }
   uint64_t wb = std::min<uint64_t>((n + 256 * kWarmSlots - 1) / (256 * kWarmSlots), cap);
   if (ilp > 1 && wb > 0) {
     const uint64_t per = 256ull * ilp, it = (n + wb * per - 1) / (wb * per);
@@ -650,6 +899,11 @@ inline uint32_t warm_blocks_for(uint64_t n, uint64_t cap, uint32_t ilp) {
 struct LaunchPlan {
   bool f32, x128;  // x128: no warm-ups, no MT scratch
   bool group;      // a group of an adaptive pass: the film's compacted order of the pixels that take this window
+  // the tile has sky blocks: the path pipeline runs over ctx->d_sky_path and yk_sky_samples renders
+  // the sky slots, launch by launch (sky_sched: the path's schedule, or the call's own when no
+  // block is left for the path kernel); warm_align: warm_blocks_for's `align`
+  bool culled;
+  uint64_t warm_align;
   const DevTree* tree;
   const DevTree::Plan* plan;
   int grid, block;
@@ -667,8 +921,8 @@ struct LaunchPlan {
 };
 
 // slots per warm-up wave of an FP64 launch of nl slots
-static uint64_t warm_wave_slots(const ykgpu_context* ctx, uint64_t nl) {
-  const uint64_t wb = warm_blocks_for(nl, (uint64_t)ctx->cus * warm_per_cu(false), kWalkIlp);
+static uint64_t warm_wave_slots(const ykgpu_context* ctx, uint64_t nl, uint64_t align) {
+  const uint64_t wb = warm_blocks_for(nl, (uint64_t)ctx->cus * warm_per_cu(false), kWalkIlp, align);
   return (nl + wb * 256 - 1) / (wb * 256) * 64;
 }
 
@@ -691,10 +945,17 @@ static int plan_launch(ykgpu_context* ctx, const yk_render_params* p, uint32_t s
     }
   }
   // (a film brings its own order, and leaves the context's alone)
-  if (!film && (rc = ensure_order(ctx, tile_width(p), p->row_count, order_stride(p)))) return rc;
+  // (... and a tile with sky blocks runs the path pipeline over the other blocks only; a tile
+  // without one runs on the context's order exactly as a call that never looked)
+  bool& culled = lp.culled = false;
+  if (sky_eligible(p, film, plan)) {
+    if ((rc = ensure_sky(ctx, p))) return rc;
+    culled = ctx->sky_slots != 0;
+  }
+  if (!film && !culled && (rc = ensure_order(ctx, tile_width(p), p->row_count, order_stride(p)))) return rc;
   // (a group of an adaptive pass: the film's compacted order of the pixels that take this window)
   const bool group = lp.group = film && film->g_slots != 0;
-  lp.order = group ? film->d_gorder : film ? film->d_order : ctx->d_order;
+  lp.order = group ? film->d_gorder : film ? film->d_order : culled ? ctx->d_sky_path : ctx->d_order;
   // Launch schedule (samples per pixel per launch; the rule is yk_schedule.hpp's): a ramp up to
   // kmax (kLaunchSpp = 32, or more for a small tile), also capped by the colour budget (32 B per
   // sample slot, kLaunchBytes per launch); a short remainder is folded into the launches before
@@ -702,11 +963,18 @@ static int plan_launch(ykgpu_context* ctx, const yk_render_params* p, uint32_t s
   // launches alternate between two streams, so that drain overlaps the next launch: many mid-sized
   // launches beat a few large ones.  Independent of the image size, which matters
   // for the per-rank tiles of N GPUs.
-  const uint32_t nps = lp.nps = group ? film->g_slots : film ? film->nps : ctx->order_slots;  // processing slots (>= pixels)
+  const uint32_t nps = lp.nps = group    ? film->g_slots
+                                : film   ? film->nps
+                                : culled ? ctx->sky_path_slots
+                                         : ctx->order_slots;  // processing slots (>= pixels)
+  lp.warm_align = culled ? nps : 0;
   // samples per pixel of this call (p->samples_per_pixel stays the stride of the seeds)
   const uint32_t spp = lp.spp = s_end - s_begin;
-  // the rings' launch size (an in-flight call's launches) and a synced call's, <= it
-  const yksched::LaunchSizes sizes = yksched::launch_sizes(nps, spp, (uint64_t)grid * block);
+  // the rings' launch size (an in-flight call's launches) and a synced call's, <= it.  A culled
+  // call keeps the launch sizes of its whole tile (the samples per launch were tuned per image
+  // size, and yk_sky_samples runs the same launches); its rings hold the path's slots only.
+  const yksched::LaunchSizes sizes =
+      yksched::launch_sizes(culled ? ctx->sky_full_slots : nps, spp, (uint64_t)grid * block);
   const uint32_t kideal = sizes.kideal, ksynced = sizes.ksynced, kfloor = sizes.kfloor;
   // A device short of memory (other contexts, other processes) makes the call slower, not fatal:
   // the rings are sized for launches of kmax samples per pixel, and when the device cannot hold
@@ -754,6 +1022,7 @@ static int plan_launch(ykgpu_context* ctx, const yk_render_params* p, uint32_t s
     // a launch buffer of the rings holds kmax samples per pixel (every launch fits: above)
     K = kmax;
     nlaunch = (uint32_t)sched.size();
+    if (nps == 0) break;  // (every block is a sky block: no path launch, no rings; launch())
     // rings as deep as kWarmRingDepth / col_ring() whatever the call's launch count (a call of two
     // launches reuses the buffers of the call before it, launch() `ov`); one buffer each for a
     // single-launch call
@@ -764,8 +1033,12 @@ static int plan_launch(ykgpu_context* ctx, const yk_render_params* p, uint32_t s
     // colour buffers: render c writes buffer c % ring and waits for the reduce of launch c - ring;
     // reduce c (stream red) overlaps the renders after it
     kColRing = nlaunch > 1 ? std::min(col_ring(), kDepRing - 1) : 1;
-    const size_t need_warm = x128 ? 0 : (size_t)kWarmRing * nps * K * welem;
-    const size_t need_col = (size_t)kColRing * nps * K * kColStride * sizeof(double);
+    // (a culled call's rings are the whole tile's: the path's slots change with every view, and a
+    // ring that grew or shrank with them would be freed and allocated again at each new camera —
+    // gigabytes, at times over a second; the launches use the front of each buffer)
+    const size_t nps_ring = culled ? ctx->sky_full_slots : nps;
+    const size_t need_warm = x128 ? 0 : (size_t)kWarmRing * nps_ring * K * welem;
+    const size_t need_col = (size_t)kColRing * nps_ring * K * kColStride * sizeof(double);
     if (kmax > kfloor && (need_warm > ctx->warm_cap || need_col > ctx->col_cap * sizeof(double))) {
       // the rings must grow: does the device have room for them?
       size_t free_b = 0, total_b = 0;
@@ -778,7 +1051,7 @@ static int plan_launch(ykgpu_context* ctx, const yk_render_params* p, uint32_t s
       }
     }
     rc = x128 ? YK_OK : grow(ctx->d_warm, ctx->warm_cap, need_warm, 1);
-    if (!rc) rc = grow(ctx->d_col, ctx->col_cap, (size_t)kColRing * nps * K * kColStride, sizeof(double));
+    if (!rc) rc = grow(ctx->d_col, ctx->col_cap, (size_t)kColRing * nps_ring * K * kColStride, sizeof(double));
     if (rc == YK_ERR_NOMEM && kmax > kfloor) {
       (void)hipGetLastError();  // (the failed hipMalloc's error must not surface at a later launch)
       shrink();
@@ -787,18 +1060,20 @@ static int plan_launch(ykgpu_context* ctx, const yk_render_params* p, uint32_t s
     if (rc) return rc;
     break;
   }
-  if (!film && sched.size() > 1 && (rc = grow(ctx->d_acc, ctx->acc_cap, (size_t)nps * 3, sizeof(double)))) return rc;
+  if (!film && nps && sched.size() > 1 && (rc = grow(ctx->d_acc, ctx->acc_cap, (size_t)(culled ? ctx->sky_full_slots : nps) * 3, sizeof(double))))
+    return rc;
   // The FP64 lens warm-ups of launches with at most kDeferSlots slots per warm-up wave draw their
   // lens retries after the walks (yk_mt_warmup_defer) from a ring per wave, sized to the largest
   // such launch (the frame's 32-spp launches: 640 records, 1.0 GB); longer launches run the
   // rejection loop in line (config 5's 128-spp launches: 8100 slots per wave; at 121 spp, 7600 per
   // wave, the deferral measured 0.7% slower)
-  const bool lens_defer = !x128 && !f32 && ctx->cam.lens_radius > 0;
+  const bool lens_defer = !x128 && !f32 && nps && ctx->cam.lens_radius > 0;
   uint32_t& retry_cap = lp.retry_cap = 0;  // records per wave
   if (lens_defer)
     for (const auto& l : sched)
-      if (warm_wave_slots(ctx, (uint64_t)nps * l.second) <= kDeferSlots)
-        retry_cap = std::max(retry_cap, retry_cap_for(warm_wave_slots(ctx, (uint64_t)nps * l.second)));
+      if (warm_wave_slots(ctx, (uint64_t)nps * l.second, lp.warm_align) <= kDeferSlots)
+        retry_cap =
+            std::max(retry_cap, retry_cap_for(warm_wave_slots(ctx, (uint64_t)nps * l.second, lp.warm_align)));
   // a call whose launches were shrunk for want of memory runs the rejection loop in line: the
   // shrink loop above budgets the start-record and colour rings only, so the plan it settled on
   // is the plan the call runs (no ring allocated afterwards out of the reserve it kept)
@@ -828,6 +1103,7 @@ struct LaunchArgs {
   ReduceArgs ra;
   FilmReduceArgs fa;
   FilmMaskedArgs fm;
+  SkyArgs sa;  // (a culled call's)
 };
 
 static int fill_args(const ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, double* sums_dev,
@@ -930,7 +1206,7 @@ static int fill_args(const ykgpu_context* ctx, const yk_render_params* p, uint8_
   wa.inv_w = ka.inv_w;
   wa.inv_h = ka.inv_h;
   wa.npix_slots = nps;
-  fastdiv(nps, wa.nps_m, wa.nps_sh);
+  fastdiv(std::max(nps, 1u), wa.nps_m, wa.nps_sh);  // (0: a call of sky blocks only, no path launch)
   fastdiv(ka.Wt, wa.w_m, wa.w_sh);
   wa.seed_mode = p->seed_mode;
   wa.seed_key = seed_key;
@@ -962,6 +1238,72 @@ static int fill_args(const ykgpu_context* ctx, const yk_render_params* p, uint8_
     fa.order = order;
     fa.npix_slots = nps;
   }
+  SkyArgs& sa = la.sa = SkyArgs{};
+  if (lp.culled) {
+    sa.W = ka.W, sa.H = ka.H, sa.spp = ka.spp, sa.seed0 = ka.seed0;
+    sa.row_begin = ka.row_begin, sa.row_stride = ka.row_stride, sa.band_log2 = ka.band_log2;
+    sa.Wt = ka.Wt, sa.col_begin = ka.col_begin, sa.col_stride = ka.col_stride, sa.col_band = ka.col_band;
+    sa.w_m = ka.w_m, sa.w_sh = ka.w_sh;
+    sa.lens = wa.lens;
+    sa.n = ctx->sky_slots;
+    sa.cam = ctx->cam;
+    sa.w_d = ka.w_d, sa.h_d = ka.h_d, sa.inv_w = ka.inv_w, sa.inv_h = ka.inv_h;
+    sa.list = ctx->d_sky_list;
+    sa.acc = ctx->d_sky_acc;
+    sa.rgb = rgb_dev;
+    sa.sums = sums_dev;
+    sa.engines = ctx->d_sky_mt;
+    sa.counters = ctx->d_stats;
+  }
+  return YK_OK;
+}
+
+// yk_sky_samples for samples [s0, s0 + ks) of the sky slots, on stream s.  The launch that ends the
+// call writes the caller's image: a call that overlaps the one before it (wait_caller) has not made
+// its streams wait for the caller's yet.
+static int enqueue_sky(ykgpu_context* ctx, hipStream_t s, SkyArgs& sa, uint32_t s0, uint32_t ks, uint32_t s_end,
+                       bool wait_caller) {
+  sa.s0 = s0;
+  sa.ks = ks;
+  sa.first = s0 == 0;
+  sa.last = s0 + ks == s_end;
+  if (sa.last && wait_caller) YK_HIP(hipStreamWaitEvent(s, ctx->ev0, 0));
+  hipLaunchKernelGGL(yk_sky_samples, dim3((sa.n + 255) / 256), dim3(256), 0, s, sa);
+  YK_HIP(hipGetLastError());
+  // (the lens: without one no sample can outrun the lazy cursors, and nothing is ever listed)
+  if (sa.lens) {
+    hipLaunchKernelGGL(yk_sky_redo, dim3(1), dim3(kSkyEngines), 0, s, sa);
+    YK_HIP(hipGetLastError());
+  }
+  return YK_OK;
+}
+
+// A call whose every block is a sky block: no path launch, no rings, one yk_sky_samples over the
+// call's samples, behind whatever the context still runs and the caller's stream.
+static int enqueue_sky_only(ykgpu_context* ctx, hipStream_t st, uint32_t s_begin, uint32_t s_end, LaunchArgs& la) {
+  int rc = YK_OK;
+  // (yk_sky_redo adds to d_stats[3], the MT-fallback count, on ctx->red: a later call that clears
+  // d_stats from another caller stream, or on ctx->aux when it overlaps this one, is not ordered
+  // behind that add — the one counter, for samples never seen, may then miss them; images never)
+  if (ctx->dirty && (rc = quiesce(ctx))) return rc;
+  if (ctx->prev_enqueued && ctx->prev_n > 0)
+    YK_HIP(hipStreamWaitEvent(st, ctx->lev[6 * (ctx->prev_n - 1) + 5], 0));
+  ctx->prev_ok = false;
+  ctx->dirty = true;
+  YK_HIP(hipMemsetAsync(ctx->d_stats, 0, kCounters * sizeof(unsigned long long), st));
+  YK_HIP(hipMemsetAsync(ctx->d_stats + 16, 0xff, 2 * sizeof(unsigned long long), st));  // minima
+  YK_HIP(hipEventRecord(ctx->ev0, st));
+  YK_HIP(hipStreamWaitEvent(ctx->red, ctx->ev0, 0));
+  if ((rc = enqueue_sky(ctx, ctx->red, la.sa, s_begin, s_end - s_begin, s_end, false))) return rc;
+  YK_HIP(hipEventRecord(ctx->sky_ev, ctx->red));
+  YK_HIP(hipStreamWaitEvent(st, ctx->sky_ev, 0));
+  YK_HIP(hipEventRecord(ctx->ev1, st));
+  // (no launch events: the next call waits for this one through the caller's stream and ctx->red)
+  ctx->lev_used = 0;
+  ctx->prev_n = 0;
+  ctx->run_len = 0;
+  ctx->prev_enqueued = false;
+  ctx->dirty = false;
   return YK_OK;
 }
 
@@ -1081,8 +1423,10 @@ static int enqueue_launches(ykgpu_context* ctx, hipStream_t st, uint32_t s_end, 
     wa.n = (uint64_t)nps * sched[c].second;
     wa.out = ctx->d_warm + (size_t)((g0 + c) % kWarmRing) * nps * K * welem;
     wa.counter = ctx->d_counter + (g0 + c) % kWarmRing;
-    const bool defer = !x128 && !f32 && wa.lens && wa.retry_cap && warm_wave_slots(ctx, wa.n) <= kDeferSlots;
-    const uint32_t wblocks = warm_blocks_for(wa.n, (uint64_t)ctx->cus * warm_per_cu(f32), defer ? kWalkIlp : 1u);
+    const bool defer =
+        !x128 && !f32 && wa.lens && wa.retry_cap && warm_wave_slots(ctx, wa.n, lp.warm_align) <= kDeferSlots;
+    const uint32_t wblocks =
+        warm_blocks_for(wa.n, (uint64_t)ctx->cus * warm_per_cu(f32), defer ? kWalkIlp : 1u, lp.warm_align);
     YK_HIP(hipEventRecord(ev[0], ctx->aux));
     if (!x128) {
       if (f32 && wa.lens)
@@ -1151,6 +1495,12 @@ static int enqueue_launches(ykgpu_context* ctx, hipStream_t st, uint32_t s_end, 
     ra.ks = ks;
     ra.first = s0 == 0;
     ra.last = s0 + ks == s_end;
+    // the launch's samples of the sky blocks, on the reduce stream ahead of the launch's reduce:
+    // they run beside the render, in the gap the short reduces leave on that stream (behind the
+    // warm-ups on ctx->aux, which is busy 97% of a step, they delayed every warm-up after them:
+    // bench +1.2%, profiles/r18_sky_blocks/); the last one writes the caller's image, and the
+    // call's last reduce, which the caller waits for, follows it
+    if (lp.culled && (rc = enqueue_sky(ctx, ctx->red, la.sa, s0, ks, s_end, ov))) return rc;
     YK_HIP(hipStreamWaitEvent(ctx->red, ev[3], 0));
     if (ov && !film && ra.last) YK_HIP(hipStreamWaitEvent(ctx->red, ctx->ev0, 0));  // the caller's image
     YK_HIP(hipEventRecord(ev[4], ctx->red));
@@ -1213,6 +1563,8 @@ static void call_stats(ykgpu_context* ctx, const yk_render_params* p, const doub
           (uint64_t)nps * sizeof(uint32_t);
     cb += nlaunch * sizeof(uint32_t) + kCounters * sizeof(unsigned long long);
     if (retry_cap) cb += retry_n * sizeof(uint4);
+    // (a culled call: the sky slots' order, sums and engines; its path order is counted above)
+    if (lp.culled) cb += sky_bytes(ctx) - (uint64_t)nps * sizeof(uint32_t);
     if (!x128) cb += 2 * lanes * ykd::kMtN * sizeof(uint32_t);
     cb += 2 * lanes * std::max(1u, p->max_depth > kStackRegs ? p->max_depth : 1u) * sizeof(uint16_t);
     const uint64_t npix = (uint64_t)p->row_count * tile_width(p);
@@ -1229,7 +1581,10 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
   uint32_t launches = 0;
   int rc = plan_launch(ctx, p, s_begin, s_end, film, lp);
   if (!rc) rc = fill_args(ctx, p, rgb_dev, sums_dev, film, lp, la);
-  if (!rc) rc = enqueue_launches(ctx, st, s_end, film, lp, la, &launches);
+  if (!rc && lp.culled && lp.nps == 0)
+    rc = enqueue_sky_only(ctx, st, s_begin, s_end, la);
+  else if (!rc)
+    rc = enqueue_launches(ctx, st, s_end, film, lp, la, &launches);
   if (!rc) call_stats(ctx, p, sums_dev, film, lp, launches);
   return rc;
 }

@@ -102,6 +102,12 @@ static_assert(YK_FIRST_LAUNCH >= 1 && YK_LAUNCH_SPP >= 1, "launch sizes must be 
 #define YK_TILE 8
 #endif
 constexpr uint32_t kTile = YK_TILE;  // processing blocks of kTile x kTile pixels (0: row-major)
+// the shape of a processing block, tw x th tile pixels (kTile x kTile of them), for a tile of every
+// stride-th image row (build_order, yk_pipeline.hip; the sky-block classifier tests these blocks)
+inline void order_block(uint32_t stride, uint32_t& tw, uint32_t& th) {
+  th = stride <= 1 ? kTile : (stride <= 4 ? std::max(1u, kTile / 2) : std::max(1u, kTile / 4));
+  tw = kTile * kTile / std::max(1u, th);
+}
 // colour buffers in flight (col_ring())
 #ifndef YK_COL_RING
 #define YK_COL_RING 2
