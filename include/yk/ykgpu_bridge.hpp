@@ -252,6 +252,9 @@ class any_film {
   virtual std::vector<uint8_t> denoise(const yk_denoise_params& dp) = 0;
   virtual std::vector<double> features(uint32_t grid) = 0;
   virtual std::vector<uint8_t> denoise_guided(const yk_denoise_params& dp, const yk_feature_params& fp) = 0;
+  virtual std::vector<double> features_sampled(uint32_t n_samples) = 0;
+  virtual std::vector<uint8_t> denoise_guided_sampled(const yk_denoise_params& dp, const yk_feature_params& fp,
+                                                      uint32_t n_samples) = 0;
   virtual yk_film_stats error_stats(double threshold2) = 0;
   virtual void save(const std::string& path, uint64_t scene_hash) = 0;
   virtual void load(const std::string& path, uint64_t scene_hash) = 0;
@@ -278,6 +281,8 @@ struct film_api {
   static constexpr auto features = &ykgpu_film_features;
   static constexpr auto denoise = &ykgpu_film_denoise;
   static constexpr auto denoise_guided = &ykgpu_film_denoise_guided;
+  static constexpr auto features_sampled = &ykgpu_film_features_sampled;
+  static constexpr auto denoise_guided_sampled = &ykgpu_film_denoise_guided_sampled;
 };
 struct group_film_api {
   using handle = ykgpu_group_film;
@@ -298,6 +303,8 @@ struct group_film_api {
   static constexpr auto features = &ykgpu_group_film_features;
   static constexpr auto denoise = &ykgpu_group_film_denoise;
   static constexpr auto denoise_guided = &ykgpu_group_film_denoise_guided;
+  static constexpr auto features_sampled = &ykgpu_group_film_features_sampled;
+  static constexpr auto denoise_guided_sampled = &ykgpu_group_film_denoise_guided_sampled;
 };
 }  // namespace detail
 
@@ -375,6 +382,19 @@ class basic_film : public any_film {
                                       typename Api::guided_stats* stats) {
     std::vector<uint8_t> img(pixels() * 3);
     ck(Api::denoise_guided(f_, &dp, &fp, nullptr, img.data(), stats), "denoise_guided");
+    return img;
+  }
+  // both with the sampled feature pass of the film's first n_samples samples (include/ykgpu.h
+  // "sampled film features"); fp.grid is ignored
+  std::vector<double> features_sampled(uint32_t n_samples) override {
+    std::vector<double> mean(pixels() * 7);
+    ck(Api::features_sampled(f_, n_samples, mean.data(), nullptr, nullptr), "features_sampled");
+    return mean;
+  }
+  std::vector<uint8_t> denoise_guided_sampled(const yk_denoise_params& dp, const yk_feature_params& fp,
+                                              uint32_t n_samples) override {
+    std::vector<uint8_t> img(pixels() * 3);
+    ck(Api::denoise_guided_sampled(f_, &dp, &fp, n_samples, nullptr, img.data(), nullptr), "denoise_guided_sampled");
     return img;
   }
   yk_film_stats error_stats(double threshold2) override {

@@ -517,7 +517,8 @@ int ykgpu_film_denoise(ykgpu_film* film, const yk_denoise_params* params, double
  *   u = ((double)x + a) / (double)W            v = ((double)(H - y - 1) + b) / (double)H
  *   o = origin,  d = ((lower_left_corner + horizontal*u) + vertical*v) - origin
  * That is the camera's pinhole ray: THE LENS IS IGNORED even when lens_radius > 0, so the features
- * are sharp where the colour is defocused (a guided filter keeps edges the defocus has blurred).
+ * are sharp where the colour is defocused (a guided filter keeps edges the defocus has blurred;
+ * "sampled film features" below makes the planes from the render's own lens samples instead).
  * The closest hit is the reference's ordered scan over the spheres in tuple order, always in
  * double whatever the film's precision (features are guides, not the reference's arithmetic), with
  * t_min = params.t_min and t_max = +inf.  Per sphere (centre c, radius r), closest = t_max at first:
@@ -663,6 +664,64 @@ int ykgpu_group_film_denoise(ykgpu_group_film* film, const yk_denoise_params* pa
 int ykgpu_group_film_denoise_guided(ykgpu_group_film* film, const yk_denoise_params* colour,
                                     const yk_feature_params* feat, double* mean_host, uint8_t* rgb_host,
                                     yk_group_denoise_stats* stats);
+
+/* ---- sampled film features: the guides from the film's own lens samples --------------------
+ * (Added under ABI 11 like the film: nothing that existed changed size or meaning.  DESIGN.md 6.8.)
+ *
+ * A second way to fill a film's 17 feature planes ("film features" above): from the first hits of
+ * the film's own first n samples instead of pinhole sub-rays, so that under a thin lens the guides
+ * are defocused where the colour is.  For pixel (x, y) of the film's tile and n in
+ * 1 .. min(256, samples_per_pixel), for s = 0 .. n-1 in order:
+ *   ray       (o, d) = what yk_camera_sample_ray(camera, the film's params, y, x, s) returns: the
+ *             sample's seed (counter, or keyed with the film's seed_key; stride = the film's target),
+ *             the engine the film's rng names, the two jitter canonicals, the lens rejection loop
+ *             and get_ray.  In double whatever the film's precision (features are guides): for an
+ *             FP64 film exactly the primary rays its samples 0..n-1 were or will be rendered with.
+ *   hit       "ray queries" below, closest mode, t_min = params.t_min, t_max = +inf; a ray outside
+ *             that section's domain rule is a miss and does no arithmetic.
+ *   f0..f6    the pinhole pass's rule, unchanged: albedo or (1, 1, 1) for a dielectric; the
+ *             face-forward normal; t; a miss gives (1, 1, 1, 0, 0, 0, 0).
+ *   folds     s = s + f, q = q + (f*f); with G = (double)n:  F = s / G,
+ *             U = max(0, (q - (s*s)/G) / (G*(G - 1)))   (n = 1: U = 0), the group sums as before.
+ * Every + - * / is one IEEE double operation, never fused.  The layout is the pinhole pass's, so
+ * the guided filter runs unchanged on either.
+ *
+ * A film still holds ONE set of planes, keyed by (pinhole grid | sampled n): either kind of pass
+ * replaces the other, a repeat call with the same key reuses the planes (ms = 0; samples, hits and
+ * redo_pixels are those of the pass that made them).  ykgpu_film_features and
+ * ykgpu_film_denoise_guided return the bytes they always returned, before and after a sampled call.
+ * ykgpu_film_features_sampled works on any tile, strided ones included, and changes nothing of the
+ * film's state; outputs as ykgpu_film_features'.  ykgpu_film_denoise_guided_sampled is
+ * ykgpu_film_denoise_guided on the sampled planes: feat->grid is ignored and not validated,
+ * feat->reserved must still be 0.  yk_guided_sampled_defaults (host only) is the point chosen by
+ * tools/features_sampled_tune.py; any of its pointers may be NULL, not all.  The group calls mean
+ * what the single film's mean, byte for byte; each entry's band+halo computes its own pass, cached
+ * per (group film, key, halo); of yk_sampled_features_stats a group reports the largest entry's ms
+ * and the sums of the entries' counts.
+ * Errors, with nothing written:
+ *   YK_ERR_INVALID      n_samples == 0, n_samples > 256, n_samples > the film's target; the
+ *                       context's scene was set after the film was created; the guided calls add
+ *                       ykgpu_film_denoise_guided's (a count below 2, both outputs NULL, the
+ *                       parameter ranges)
+ *   YK_ERR_UNSUPPORTED  the guided calls on a tile that is not consecutive rows and columns */
+typedef struct yk_sampled_features_stats { /* 32 bytes */
+  double ms;              /* device time of the pass; 0 when the cached pass was reused */
+  uint64_t samples;       /* pixels * n, of the pass that made the planes */
+  uint64_t hits;          /* of those, samples whose ray hit a sphere */
+  uint32_t redo_pixels;   /* pixels finished by the whole-engine redo */
+  uint32_t reserved;
+} yk_sampled_features_stats;
+
+int yk_guided_sampled_defaults(yk_denoise_params* colour, yk_feature_params* feat, uint32_t* n_samples);
+int ykgpu_film_features_sampled(ykgpu_film* film, uint32_t n_samples, double* mean_host, double* var_host,
+                                yk_sampled_features_stats* stats);
+int ykgpu_film_denoise_guided_sampled(ykgpu_film* film, const yk_denoise_params* colour, const yk_feature_params* feat,
+                                      uint32_t n_samples, double* mean_host, uint8_t* rgb_host, yk_guided_stats* stats);
+int ykgpu_group_film_features_sampled(ykgpu_group_film* film, uint32_t n_samples, double* mean_host, double* var_host,
+                                      yk_sampled_features_stats* stats);
+int ykgpu_group_film_denoise_guided_sampled(ykgpu_group_film* film, const yk_denoise_params* colour,
+                                            const yk_feature_params* feat, uint32_t n_samples, double* mean_host,
+                                            uint8_t* rgb_host, yk_group_denoise_stats* stats);
 
 /* ---- ray queries (ABI 11) -------------------------------------------------
  * The reference's public world.hit(r, t_min, t_max) (hittable.hpp:32-34, hittable_list.hpp:32-58,

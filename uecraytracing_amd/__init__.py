@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 from . import records
-from .records import CastStats, Hit, Ray, PathRay, RadianceParams, RadianceStats, Camera, DenoiseParams, DenoiseStats, FeatureParams, FilmPass, GroupDenoiseStats, GuidedStats, FilmStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
+from .records import CastStats, Hit, Ray, PathRay, RadianceParams, RadianceStats, Camera, DenoiseParams, DenoiseStats, FeatureParams, FilmPass, GroupDenoiseStats, GuidedStats, FilmStats, SampledFeaturesStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(PKG_DIR, "lib")
@@ -43,6 +43,8 @@ EXPORTS = (
     "ykgpu_group_film_read", "ykgpu_group_film_write", "ykgpu_group_film_counts", "ykgpu_group_film_write_counts",
     "ykgpu_group_film_error", "ykgpu_group_film_features", "ykgpu_group_film_denoise",
     "ykgpu_group_film_denoise_guided",
+    "yk_guided_sampled_defaults", "ykgpu_film_features_sampled", "ykgpu_film_denoise_guided_sampled",
+    "ykgpu_group_film_features_sampled", "ykgpu_group_film_denoise_guided_sampled",
     "ykgpu_cast_rays", "ykgpu_cast_rays_async", "ykgpu_cast_get_stats",
     "ykgpu_radiance_rays", "ykgpu_radiance_rays_async", "ykgpu_radiance_get_stats", "yk_camera_sample_ray",
     "yk_camera_sample_rays",
@@ -133,6 +135,11 @@ def load_library():
         "ykgpu_film_features": ([c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, P(c.c_double)], c.c_int),
         "ykgpu_film_denoise_guided": ([c.c_void_p, P(DenoiseParams), P(FeatureParams), c.c_void_p, c.c_void_p,
                                        P(GuidedStats)], c.c_int),
+        "yk_guided_sampled_defaults": ([P(DenoiseParams), P(FeatureParams), P(c.c_uint32)], c.c_int),
+        "ykgpu_film_features_sampled": ([c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, P(SampledFeaturesStats)],
+                                        c.c_int),
+        "ykgpu_film_denoise_guided_sampled": ([c.c_void_p, P(DenoiseParams), P(FeatureParams), c.c_uint32, c.c_void_p,
+                                               c.c_void_p, P(GuidedStats)], c.c_int),
         "ykgpu_cast_rays": ([c.c_void_p, c.c_void_p, c.c_uint64, c.c_uint32, c.c_void_p], c.c_int),
         "ykgpu_cast_rays_async": ([c.c_void_p, c.c_void_p, c.c_uint64, c.c_uint32, c.c_void_p, c.c_void_p], c.c_int),
         "ykgpu_cast_get_stats": ([c.c_void_p, P(CastStats)], c.c_int),
@@ -147,7 +154,8 @@ def load_library():
     # the group film calls take the film calls' arguments (include/ykgpu.h "group films"); the two
     # filters report yk_group_denoise_stats
     for name in ("create", "destroy", "params", "accumulate", "accumulate_adaptive", "resolve", "read", "write",
-                 "counts", "write_counts", "error", "features", "denoise", "denoise_guided"):
+                 "counts", "write_counts", "error", "features", "denoise", "denoise_guided", "features_sampled",
+                 "denoise_guided_sampled"):
         args, res = sig["ykgpu_film_" + name]
         if name.startswith("denoise"):
             args = args[:-1] + [P(GroupDenoiseStats)]
@@ -155,6 +163,8 @@ def load_library():
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
         f.argtypes, f.restype = args, res
+    # (a test hook, not part of the C-ABI: _feature_lazy_words below)
+    lib.yk_features_sampled_lazy_words.argtypes, lib.yk_features_sampled_lazy_words.restype = [c.c_uint32], None
     if lib.ykgpu_abi_version() != ABI_VERSION:
         raise YkError("ABI version mismatch")
     _lib = lib
@@ -285,6 +295,37 @@ def guided_defaults():
     dp, fp = DenoiseParams(), FeatureParams()
     _check(load_library().yk_guided_defaults(ctypes.byref(dp), ctypes.byref(fp)))
     return dp, fp
+
+
+def guided_sampled_defaults():
+    """yk_guided_sampled_defaults (host only): the (DenoiseParams, FeatureParams, n_samples) point
+    chosen for the sampled feature pass."""
+    dp, fp, n = DenoiseParams(), FeatureParams(), ctypes.c_uint32(0)
+    _check(load_library().yk_guided_sampled_defaults(ctypes.byref(dp), ctypes.byref(fp), ctypes.byref(n)))
+    return dp, fp, n.value
+
+
+class _feature_lazy_words:
+    """YKGPU_FEATURE_LAZY_WORDS, read at each sampled feature call: the mt19937
+    words a sample's start may draw before the sampled pass hands its pixel to the whole-engine
+    redo, clamped to 4..227.  A diagnostic for tests (the planes do not depend on it); the package
+    reads it, not the library, and hands it over for the one call."""
+
+    def __init__(self, lib):
+        self._lib = lib
+        v = os.environ.get("YKGPU_FEATURE_LAZY_WORDS")
+        try:
+            self._words = min(227, max(4, int(v))) if v else 0
+        except ValueError:
+            self._words = 0
+
+    def __enter__(self):
+        if self._words:
+            self._lib.yk_features_sampled_lazy_words(self._words)
+
+    def __exit__(self, *exc):
+        if self._words:
+            self._lib.yk_features_sampled_lazy_words(0)
 
 
 def camera_sample_rays(camera: Camera, params: RenderParams, ys, xs, ss) -> np.ndarray:
@@ -456,6 +497,35 @@ class Film:
             self._f, ctypes.byref(colour) if colour is not None else None,
             ctypes.byref(feat) if feat is not None else None, mean.ctypes.data if want_mean else None,
             rgb.ctypes.data if want_rgb else None, ctypes.byref(st)))
+        return mean, rgb, st.as_dict()
+
+    def features_sampled(self, n_samples: int):
+        """(mean float64[row_count, tile width, 7], var likewise, stats dict): the feature planes of
+        include/ykgpu.h "sampled film features", from the first hits of the film's own first
+        n_samples samples (lens and jitter included).  Computed once per (film, n_samples): ms is 0
+        when the film's cached pass was reused."""
+        mean = np.empty(self._shape + (7,), np.float64)
+        var = np.empty(self._shape + (7,), np.float64)
+        st = SampledFeaturesStats()
+        with _feature_lazy_words(self._lib):
+            _check(self._fn("features_sampled")(self._f, n_samples, mean.ctypes.data, var.ctypes.data, ctypes.byref(st)))
+        return mean, var, st.as_dict()
+
+    def denoise_guided_sampled(self, colour: DenoiseParams = None, feat: FeatureParams = None, n_samples: int = None,
+                               want_mean: bool = True, want_rgb: bool = True):
+        """denoise_guided() with the sampled feature planes of the film's first n_samples samples as
+        guides (feat.grid is ignored).  colour / feat / n_samples None: that part of
+        guided_sampled_defaults()."""
+        mean = np.empty(self._shape + (3,), np.float64) if want_mean else None
+        rgb = np.empty(self._shape + (3,), np.uint8) if want_rgb else None
+        st = self._GUIDED_STATS()
+        if n_samples is None:
+            n_samples = guided_sampled_defaults()[2]
+        with _feature_lazy_words(self._lib):
+            _check(self._fn("denoise_guided_sampled")(
+                self._f, ctypes.byref(colour) if colour is not None else None,
+                ctypes.byref(feat) if feat is not None else None, n_samples, mean.ctypes.data if want_mean else None,
+                rgb.ctypes.data if want_rgb else None, ctypes.byref(st)))
         return mean, rgb, st.as_dict()
 
     def render_until(self, threshold: float, chunk: int) -> dict:
@@ -762,5 +832,5 @@ def render_devices(devices, spheres, camera: Camera, params: RenderParams) -> np
     return out
 
 
-__all__ = ["Renderer", "Film", "GroupFilm", "GroupDenoiseStats", "Ray", "Hit", "CastStats", "PathRay", "RadianceParams", "RadianceStats", "camera_sample_rays", "FilmPass", "DenoiseParams", "DenoiseStats", "denoise_defaults", "FeatureParams", "GuidedStats", "guided_defaults", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
+__all__ = ["Renderer", "Film", "GroupFilm", "GroupDenoiseStats", "Ray", "Hit", "CastStats", "PathRay", "RadianceParams", "RadianceStats", "camera_sample_rays", "FilmPass", "DenoiseParams", "DenoiseStats", "denoise_defaults", "FeatureParams", "GuidedStats", "guided_defaults", "SampledFeaturesStats", "guided_sampled_defaults", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
            "make_params", "load_library", "records", "EXPORTS", "LIB_PATH", "CLI_PATH"]

@@ -110,6 +110,10 @@ const char* kHelp =
     "                            at the pair of defaults tuned together (k2 2, grid 2); the\n"
     "                            --denoise-* options still set the colour side\n"
     "      --feature-grid arg    sub-rays per pixel side of the feature pass, 1..4 (default: 2)\n"
+    "      --feature-samples arg the features of --denoise-features and --aov from the first hits of\n"
+    "                            the render's own first arg samples, 1..256 and at most --spp (lens\n"
+    "                            and jitter included: defocused where the image is) instead of\n"
+    "                            pinhole sub-rays; --feature-grid is then unused\n"
     "      --aov arg             also write the feature means F as arg.albedo.png, arg.normal.png\n"
     "                            and arg.depth.png: trunc(clamp(x, 0, 0.999) * 256) of F0..F2, of\n"
     "                            0.5 * F + 0.5 for F3..F5, and of F6 / (1 + F6) (grey: r = g = b)\n"
@@ -152,6 +156,7 @@ struct args {
   yk_denoise_params dn{};
   // the guided filter and the feature images (--feature-grid alone sets the grid of either)
   bool denoise_features = false, have_feature_grid = false;
+  uint32_t feature_samples = 0;  // --feature-samples: != 0, the sampled feature pass at that n
   yk_feature_params fp{};
   std::string aov;
   // --pick X,Y: one ray query instead of a render
@@ -250,6 +255,10 @@ args parse(int argc, char** argv) {
       else if (n == "denoise-k2") { a.dn.k2 = to_positive(n, value(i, n, inl)); a.have_denoise_params = true; have_k2 = true; }
       else if (n == "denoise-features") { a.denoise = a.denoise_features = true; }
       else if (n == "feature-grid") { a.fp.grid = to_u32(n, value(i, n, inl)); a.have_feature_grid = true; }
+      else if (n == "feature-samples") {
+        a.feature_samples = to_u32(n, value(i, n, inl));
+        if (a.feature_samples < 1 || a.feature_samples > 256) throw option_error{"Option 'feature-samples' must be 1..256"};
+      }
       else if (n == "aov") {
         a.aov = value(i, n, inl);
         if (a.aov.empty()) throw option_error{"Option 'aov' needs a file name prefix"};
@@ -305,10 +314,16 @@ args parse(int argc, char** argv) {
   if (a.have_feature_grid && !a.denoise_features && a.aov.empty())
     throw option_error{"Option 'feature-grid' needs --denoise-features or --aov"};
   if (a.fp.grid < 1 || a.fp.grid > 4) throw option_error{"Option 'feature-grid' must be 1..4"};
-  if (a.denoise_features && !have_k2) {  // the colour side of the pair, unless the option set it
+  if (a.feature_samples && !a.denoise_features && a.aov.empty())
+    throw option_error{"Option 'feature-samples' needs --denoise-features or --aov"};
+  if (a.feature_samples > a.spp) throw option_error{"Option 'feature-samples' must be at most --spp"};
+  if (a.denoise_features) {  // the pair of the pass in use; the colour side unless the option set it
     yk_denoise_params pair;
-    yk_guided_defaults(&pair, nullptr);
-    a.dn.k2 = pair.k2;
+    if (a.feature_samples)
+      yk_guided_sampled_defaults(&pair, &a.fp, nullptr);
+    else
+      yk_guided_defaults(&pair, nullptr);
+    if (!have_k2) a.dn.k2 = pair.k2;
   }
   if (a.dn.radius > 10) throw option_error{"Option 'denoise-radius' must be at most 10"};
   if (a.dn.patch > 3) throw option_error{"Option 'denoise-patch' must be at most 3"};
@@ -501,6 +516,7 @@ int main(int argc, char* argv[]) {
       // does not: the filter's error is the run's)
       auto picture = [&](bool preview) {
         if (!a.denoise || (preview && film.count_range().first < 2)) return film.resolve();
+        if (a.denoise_features && a.feature_samples) return film.denoise_guided_sampled(a.dn, a.fp, a.feature_samples);
         return a.denoise_features ? film.denoise_guided(a.dn, a.fp) : film.denoise(a.dn);
       };
       uint32_t chunks = 0;
@@ -549,7 +565,7 @@ int main(int argc, char* argv[]) {
       st.seed_key = film.params().seed_key;
       if (!a.aov.empty()) {
         // the feature means as images (include/ykgpu.h "film features"): one operation per step
-        const std::vector<double> F = film.features(a.fp.grid);
+        const std::vector<double> F = a.feature_samples ? film.features_sampled(a.feature_samples) : film.features(a.fp.grid);
         const auto enc = [](double x) {
           x = (x < 0.0) ? 0.0 : (0.999 < x) ? 0.999 : x;
           return (uint8_t)(uint32_t)(x * 256);

@@ -499,6 +499,49 @@ int denoise_call(ykgpu_film* film, const char* name, const yk_denoise_params& dp
   return YK_OK;
 }
 
+// Both guided entry points: the filter over the pinhole planes at fp.grid (n_samples == 0) or over
+// the sampled planes of the film's first n_samples samples (fp.grid ignored).
+int guided_call(ykgpu_film* film, const char* name, const yk_denoise_params& dp, yk_feature_params fp, uint32_t n_samples,
+                bool sampled, double* mean_host, uint8_t* rgb_host, yk_guided_stats* stats) {
+  if (sampled) fp.grid = 1;  // (not read, so not validated)
+  const double* d_feat = nullptr;
+  double ms_feat = 0;
+  yk_denoise_stats ds{};
+  const int rc = denoise_call(
+      film, name, dp, mean_host, rgb_host, stats ? &ds : nullptr,
+      [&]() -> int {
+        if (int rc = feature_params_check(fp)) return rc;
+        if (sampled) return yk_film_features_sampled_check(film, n_samples);
+        if (film->scene_gen != film->ctx->scene_gen)
+          return fail(YK_ERR_INVALID, "the context's scene was set after the film was created");
+        return YK_OK;
+      },
+      [&]() -> int {
+        if (sampled) {
+          yk_sampled_features_stats fs{};
+          if (int rc = yk_film_features_sampled_ensure(film, n_samples, &d_feat, &fs)) return rc;
+          ms_feat = fs.ms;
+        } else if (int rc = yk_film_features_ensure(film, fp.grid, &d_feat, &ms_feat)) {
+          return rc;
+        }
+        YK_HIP(hipFuncSetAttribute((const void*)yk_film_nlm_guided, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)nlm_lds_bytes(kMaxRadius, kMaxPatch)));
+        return YK_OK;
+      },
+      [&](const NlmArgs& a, dim3 grid, size_t lds, hipStream_t st) {
+        const GuidedArgs g = guided_args(a, d_feat, fp);
+        hipLaunchKernelGGL(yk_film_nlm_guided, grid, dim3(kThreads), lds, st, g);
+        return hipGetLastError();
+      });
+  if (!rc && stats) {
+    stats->features_ms = ms_feat;
+    stats->moments_ms = ds.moments_ms;
+    stats->filter_ms = ds.filter_ms;
+    stats->total_ms = ds.total_ms;
+  }
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -549,6 +592,14 @@ int yk_guided_defaults(yk_denoise_params* colour, yk_feature_params* feat) {
   return YK_OK;
 }
 
+int yk_guided_sampled_defaults(yk_denoise_params* colour, yk_feature_params* feat, uint32_t* n_samples) {
+  if (!colour && !feat && !n_samples) return fail(YK_ERR_INVALID, "null out");
+  // the point of DESIGN.md §6.8 (tools/features_sampled_tune.py)
+  if (colour || feat) yk_guided_defaults(colour, feat);
+  if (n_samples) *n_samples = 16;
+  return YK_OK;
+}
+
 int ykgpu_film_denoise_guided(ykgpu_film* film, const yk_denoise_params* params, const yk_feature_params* fparams,
                               double* mean_host, uint8_t* rgb_host, yk_guided_stats* stats) {
   yk_denoise_params dp;
@@ -556,35 +607,17 @@ int ykgpu_film_denoise_guided(ykgpu_film* film, const yk_denoise_params* params,
   yk_guided_defaults(&dp, &fp);
   if (params) dp = *params;
   if (fparams) fp = *fparams;
-  const double* d_feat = nullptr;
-  double ms_feat = 0;
-  yk_denoise_stats ds{};
-  const int rc = denoise_call(
-      film, "ykgpu_film_denoise_guided", dp, mean_host, rgb_host, stats ? &ds : nullptr,
-      [&]() -> int {
-        if (int rc = feature_params_check(fp)) return rc;
-        if (film->scene_gen != film->ctx->scene_gen)
-          return fail(YK_ERR_INVALID, "the context's scene was set after the film was created");
-        return YK_OK;
-      },
-      [&]() -> int {
-        if (int rc = yk_film_features_ensure(film, fp.grid, &d_feat, &ms_feat)) return rc;
-        YK_HIP(hipFuncSetAttribute((const void*)yk_film_nlm_guided, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)nlm_lds_bytes(kMaxRadius, kMaxPatch)));
-        return YK_OK;
-      },
-      [&](const NlmArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-        const GuidedArgs g = guided_args(a, d_feat, fp);
-        hipLaunchKernelGGL(yk_film_nlm_guided, grid, dim3(kThreads), lds, st, g);
-        return hipGetLastError();
-      });
-  if (!rc && stats) {
-    stats->features_ms = ms_feat;
-    stats->moments_ms = ds.moments_ms;
-    stats->filter_ms = ds.filter_ms;
-    stats->total_ms = ds.total_ms;
-  }
-  return rc;
+  return guided_call(film, "ykgpu_film_denoise_guided", dp, fp, 0, false, mean_host, rgb_host, stats);
+}
+
+int ykgpu_film_denoise_guided_sampled(ykgpu_film* film, const yk_denoise_params* params, const yk_feature_params* fparams,
+                                      uint32_t n_samples, double* mean_host, uint8_t* rgb_host, yk_guided_stats* stats) {
+  yk_denoise_params dp;
+  yk_feature_params fp;
+  yk_guided_sampled_defaults(&dp, &fp, nullptr);
+  if (params) dp = *params;
+  if (fparams) fp = *fparams;
+  return guided_call(film, "ykgpu_film_denoise_guided_sampled", dp, fp, n_samples, true, mean_host, rgb_host, stats);
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 // A unit of its own, like yk_denoise.hip (it also holds the ray queries, yk_cast.hpp, and the
 // radiance queries, yk_radiance.hpp, included at the end).  One kernel, yk_film_features, on the context's stream;
 // its result lives in planes the film owns (ykgpu_film, yk_host_internal.hpp) and is computed once
-// per (film, grid).
+// per (film, grid).  The sampled pass (yk_features_sampled.hpp) fills the same planes another way.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -185,13 +185,13 @@ int ykhost::yk_film_features_ensure(ykgpu_film* film, uint32_t grid, const doubl
   const hipStream_t stream = ctx->stream;  // (film calls are synchronous on it)
   const size_t npix = (size_t)rows * wt;
   if (!film->d_features) {  // (a film's tile never changes size)
-    film->feature_grid = 0;
+    film->feature_grid = film->feature_n = 0;
     YK_HIP(hipMalloc(&film->d_features, kYkFeatPlanes * npix * sizeof(double)));
   }
   *planes = (const double*)film->d_features;
   if (ms) *ms = 0.0;
   if (film->feature_grid == grid) return YK_OK;
-  film->feature_grid = 0;  // (until the pass is whole)
+  film->feature_grid = film->feature_n = 0;  // (until the pass is whole; a sampled pass's planes are replaced)
   const TileCols cols = film_cols(film);
   FeatArgs a{};
   a.cam = ctx->cam;
@@ -235,6 +235,26 @@ int ykhost::yk_film_features_ensure(ykgpu_film* film, uint32_t grid, const doubl
   return YK_OK;
 }
 
+int ykhost::yk_film_features_copy_out(ykgpu_film* film, const double* planes, double* mean_host, double* var_host) {
+  if (!mean_host && !var_host) return YK_OK;
+  // the planes are channel-major (the filter's reads are rows of one channel); the caller's
+  // arrays are pixel-major: transposed on the host, in memory of the call's own, so that nothing
+  // is written when the copy fails
+  const size_t npix = (size_t)film->p.row_count * tile_width(&film->p);
+  std::vector<double> h(2 * kYkFeatChannels * npix);
+  YK_HIP(hipMemcpyAsync(h.data(), planes, h.size() * sizeof(double), hipMemcpyDeviceToHost, film->ctx->stream));
+  YK_HIP(hipStreamSynchronize(film->ctx->stream));
+  for (uint32_t c = 0; c < kYkFeatChannels; ++c) {
+    const double* m = h.data() + (size_t)c * npix;
+    const double* v = m + kYkFeatChannels * npix;
+    for (size_t p = 0; p < npix; ++p) {
+      if (mean_host) mean_host[p * kYkFeatChannels + c] = m[p];
+      if (var_host) var_host[p * kYkFeatChannels + c] = v[p];
+    }
+  }
+  return YK_OK;
+}
+
 extern "C" {
 
 int ykgpu_film_features(ykgpu_film* film, uint32_t grid, double* mean_host, double* var_host, double* ms) {
@@ -242,23 +262,7 @@ int ykgpu_film_features(ykgpu_film* film, uint32_t grid, double* mean_host, doub
   const double* planes = nullptr;
   double t = 0;
   if (int rc = yk_film_features_ensure(film, grid, &planes, &t)) return rc;
-  if (mean_host || var_host) {
-    // the planes are channel-major (the filter's reads are rows of one channel); the caller's
-    // arrays are pixel-major: transposed on the host, in memory of the call's own, so that nothing
-    // is written when the copy fails
-    const size_t npix = (size_t)film->p.row_count * tile_width(&film->p);
-    std::vector<double> h(2 * kYkFeatChannels * npix);
-    YK_HIP(hipMemcpyAsync(h.data(), planes, h.size() * sizeof(double), hipMemcpyDeviceToHost, film->ctx->stream));
-    YK_HIP(hipStreamSynchronize(film->ctx->stream));
-    for (uint32_t c = 0; c < kYkFeatChannels; ++c) {
-      const double* m = h.data() + (size_t)c * npix;
-      const double* v = m + kYkFeatChannels * npix;
-      for (size_t p = 0; p < npix; ++p) {
-        if (mean_host) mean_host[p * kYkFeatChannels + c] = m[p];
-        if (var_host) var_host[p * kYkFeatChannels + c] = v[p];
-      }
-    }
-  }
+  if (int rc = yk_film_features_copy_out(film, planes, mean_host, var_host)) return rc;
   if (ms) *ms = t;
   return YK_OK;
 }
@@ -269,3 +273,5 @@ int ykgpu_film_features(ykgpu_film* film, uint32_t grid, double* mean_host, doub
 #include "yk_cast.hpp"
 // ... and the radiance queries (ykgpu_radiance_rays ...), whose closest hit is the cast's
 #include "yk_radiance.hpp"
+// ... and the sampled feature pass (ykgpu_film_features_sampled ...), whose closest hit is a copy of it
+#include "yk_features_sampled.hpp"

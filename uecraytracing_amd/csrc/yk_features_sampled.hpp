@@ -1,0 +1,549 @@
+// yk_features_sampled.hpp — the sampled feature pass (include/ykgpu.h "sampled film features",
+// DESIGN.md §6.8): a film's 17 feature planes from the first hits of the film's own first n samples,
+// so that a thin-lens render gets guides that are defocused where its colour is.  Every sample's
+// start ray is yk_camera_sample_ray's bit for bit, its hit the ray queries' closest hit, and the
+// channel rule and the folds are the pinhole pass's (yk_features.hip), one unfused IEEE double
+// operation each, so numpy restates the planes byte for byte (tests/film_features_sampled_ref.py).
+//
+// Part of the unit yk_features.hip, which includes this file once at its end (the list of units is
+// fixed, tests/test_build_knobs.py).  Everything but the C-ABI entry points lives in namespace ykfs.
+// Two kernels on the context's stream, beside the render and not inside it:
+//   yk_film_features_sampled<Gen>  one lane per pixel, a wave an 8 x 8 pixel block, the pixel's n
+//                                  samples one after the other (the fold order is the definition's).
+//                                  The start as yk_sky_samples makes it (yk_pipeline.hip): the seed
+//                                  walk of four consecutive samples interleaved, the lazy cursors,
+//                                  the lens rejection loop.  The closest hit as yk_cast finds it — a
+//                                  COPY of its traversal, so that yk_cast's instructions stay what
+//                                  they were: a checked per-lane LDS stack, the float slab test,
+//                                  exact leaves, ties to the later index, the ordered scan on a guard,
+//                                  a stack overflow or YK_FLAG_LINEAR_SCAN.
+//   yk_film_features_redo          the pixels whose lens loop outran the lazy cursors' words (listed
+//                                  by the first kernel; ~55 rejections in a row, or a test's lowered
+//                                  limit): all n samples again from a whole engine (ykd::MtFull), the
+//                                  hit by the ordered scan.  One block of kRedoEngines threads.
+#ifndef YK_FEATURES_SAMPLED_HPP
+#define YK_FEATURES_SAMPLED_HPP
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/ykgpu.h"
+#include "yk_cast.hpp"
+#include "yk_device.hpp"
+#include "yk_film_internal.hpp"
+#include "yk_host_internal.hpp"
+
+namespace ykfs {
+using namespace ykhost;
+namespace {
+
+constexpr uint32_t kMaxSamples = 256;
+// a workgroup: four waves side by side, each an 8 x 8 pixel block
+constexpr uint32_t kWave = 8, kBlockW = 4 * kWave, kBlockH = kWave, kThreads = kBlockW * kBlockH;
+constexpr uint32_t kWalk = 4;  // consecutive samples whose seed walks are interleaved
+constexpr uint32_t kRedoEngines = 64;
+constexpr uint32_t kStackMin = 4, kStackMax = 48;  // yk_cast's
+constexpr uint32_t kLazyMin = 4;                   // (the jitter's words: never checked)
+
+static_assert(sizeof(yk_sampled_features_stats) == 32 && offsetof(yk_sampled_features_stats, samples) == 8 &&
+                  offsetof(yk_sampled_features_stats, hits) == 16 &&
+                  offsetof(yk_sampled_features_stats, redo_pixels) == 24,
+              "yk_sampled_features_stats");
+
+struct SfArgs {
+  yk_camera cam;
+  const char* nodes;          // DevNode; child links are byte offsets
+  const SphereGeo* leaf_geo;  // leaf order
+  const uint32_t* leaf_ids;   // leaf slot -> tuple index
+  const SphereGeo* geo;       // tuple order
+  const SphereMat* mat;
+  double* out;               // kYkFeatPlanes planes of npix doubles
+  uint32_t* redo;            // [0]: pixels listed, [1, 1 + npix): the list, then kRedoEngines engines
+  unsigned long long* hits;  // samples that hit a sphere
+  double t_min, extent, origin_bound;
+  uint64_t seed_key;
+  uint32_t seed0, seed_mode, spp, n;
+  uint32_t lazy_words;  // mt19937 words a start may draw from the lazy cursors (4..227)
+  uint32_t scan_only;   // YK_FLAG_LINEAR_SCAN
+  int32_t root;
+  uint32_t node_bytes, nspheres, stack_cap;
+  uint32_t W, H, rows, wt, npix;
+  uint32_t row_begin, row_stride, row_band, col_begin, col_stride, col_band;
+};
+
+__device__ __forceinline__ uint32_t image_x(const SfArgs& a, uint32_t tj) {
+  return a.col_begin + (((tj >> a.col_band) * a.col_stride) << a.col_band) + (tj & ((1u << a.col_band) - 1u));
+}
+__device__ __forceinline__ uint32_t image_y(const SfArgs& a, uint32_t ti) {
+  return a.row_begin + (((ti >> a.row_band) * a.row_stride) << a.row_band) + (ti & ((1u << a.row_band) - 1u));
+}
+
+// yk_camera_sample_ray's ray (yk_host.cpp) from the start's draws, operation for operation: the
+// jitter (source.cpp:160-164), camera::get_ray (camera.hpp:29-32) and the thin lens' offset
+__device__ __forceinline__ void start_ray(const SfArgs& a, uint32_t x, uint32_t y, double uc, double vc, bool lens,
+                                          double px, double py, v3& o, v3& d) {
+  const double u = film_div(film_add((double)x, uc), (double)a.W);
+  const double v = film_div(film_add((double)(a.H - y - 1), vc), (double)a.H);
+  const v3 org = ld3(a.cam.origin);
+  d = ykd::sub(ykd::add(ykd::add(ld3(a.cam.lower_left_corner), ykd::mul(ld3(a.cam.horizontal), u)),
+                        ykd::mul(ld3(a.cam.vertical), v)),
+               org);
+  o = org;
+  if (lens) {
+    const double rx = px * a.cam.lens_radius, ry = py * a.cam.lens_radius;
+    const v3 off = ykd::add(ykd::mul(ld3(a.cam.lens_u), rx), ykd::mul(ld3(a.cam.lens_v), ry));
+    o = ykd::add(o, off);
+    d = ykd::sub(d, off);
+  }
+}
+
+// hittable_list::hit_impl over sphere::hit_impl, the literal loop in tuple order, t_max = +inf
+__device__ __forceinline__ int scan_hit(const SfArgs& a, v3 o, v3 d, double aa, double& t) {
+  double best = INFINITY;
+  int best_id = -1;
+  for (uint32_t k = 0; k < a.nspheres; ++k) {
+    const SphereGeo sg = a.geo[k];
+    const v3 oc = {o.x - sg.cx, o.y - sg.cy, o.z - sg.cz};
+    const double hb = ykd::dot(oc, d);
+    const double cc = ykd::len2(oc) - sg.rr;
+    const double disc = hb * hb - aa * cc;
+    if (disc < 0) continue;
+    const double sq = ykd::nsqrt(disc);
+    double root = (-hb - sq) / aa;
+    if (root < a.t_min || best < root) {
+      root = (-hb + sq) / aa;
+      if (root < a.t_min || best < root) continue;
+    }
+    best = root;
+    best_id = (int)k;
+  }
+  t = best;
+  return best_id;
+}
+
+// The ray queries' closest hit of (o, d) with t_min = a.t_min and t_max = +inf: the sphere's tuple
+// index and t, or -1.  yk_cast's traversal (yk_cast.hpp), statement for statement; stk is the lane's
+// column of the block's stack, entries kThreads words apart.
+__device__ __forceinline__ int closest_hit(const SfArgs& a, int32_t* const stk, v3 o, v3 d, double& t) {
+  const double tmin = a.t_min;
+  if (!ykcast::in_domain(o, d, tmin, INFINITY, a.extent)) return -1;  // (a miss, and no arithmetic)
+  // the guards that send a ray to the ordered scan (yk_cast)
+  const float dxf = (float)d.x, dyf = (float)d.y, dzf = (float)d.z;
+  const float dmin = fminf(fminf(fabsf(dxf), fabsf(dyf)), fabsf(dzf));
+  const float dmax = fmaxf(fmaxf(fabsf(dxf), fabsf(dyf)), fabsf(dzf));
+  const double mo = fmax(fabs(o.x), fmax(fabs(o.y), fabs(o.z)));
+  bool scan = a.scan_only || a.origin_bound < 0 || !(mo <= a.origin_bound) || !(dmin > 1e-30f && dmax < 1e30f) ||
+              !(dmax * 0x1p-90f <= (float)a.origin_bound);
+  const double aa = ykd::len2(d);
+  double best = INFINITY;
+  int best_id = -1;
+  if (!scan) {
+    const float ix = 1.0f / dxf, iy = 1.0f / dyf, iz = 1.0f / dzf;
+    constexpr float kFar = 1.0f + 0x1p-17f;
+    const float ixs = ix * kFar, iys = iy * kFar, izs = iz * kFar;
+    const float oxf = (float)o.x, oyf = (float)o.y, ozf = (float)o.z;
+    const float nox = -(oxf * ix), noy = -(oyf * iy), noz = -(ozf * iz);
+    const float fox = -(oxf * ixs), foy = -(oyf * iys), foz = -(ozf * izs);
+    const float tmin_lo = ykcast::f32_down(tmin) * (1.0f - 0x1p-17f);
+    const uint32_t qx = ix < 0.0f ? 16u : 0u, qy = 48u + (iy < 0.0f ? 16u : 0u), qz = 96u + (iz < 0.0f ? 16u : 0u);
+    stk[0] = ykbvh::kEmptyLeaf;  // the sentinel: the traversal ends when it has been popped
+    uint32_t sp = 1;
+    int32_t node = a.root;
+    float ustar = ykcast::f32_up(best) * (1.0f + 0x1p-18f);
+    for (;;) {
+      while (node >= 0) {
+        if ((uint32_t)node + (uint32_t)sizeof(DevNode) > a.node_bytes) {  // (never: a link outside the tree)
+          scan = true;
+          break;
+        }
+        const char* w = a.nodes + node;
+        const float4 nx = *(const float4*)(w + qx), fx = *(const float4*)(w + qx + 16);
+        const float4 ny = *(const float4*)(w + qy), fy = *(const float4*)(w + qy + 16);
+        const float4 nz = *(const float4*)(w + qz), fz = *(const float4*)(w + qz + 16);
+        const int4 ch = *(const int4*)(w + 144);
+        const int32_t popped = stk[(sp - 1) * kThreads];
+#define YK_FS_SLOT(c)                                                                                     \
+  (fmaxf(fmaxf(fmaxf(__builtin_fmaf(nx.c, ix, nox), __builtin_fmaf(ny.c, iy, noy)), __builtin_fmaf(nz.c, iz, noz)), \
+         tmin_lo) <=                                                                                      \
+   fminf(fminf(fminf(__builtin_fmaf(fx.c, ixs, fox), __builtin_fmaf(fy.c, iys, foy)), __builtin_fmaf(fz.c, izs, foz)), \
+         ustar))
+        const bool h0 = YK_FS_SLOT(x), h1 = YK_FS_SLOT(y), h2 = YK_FS_SLOT(z), h3 = YK_FS_SLOT(w);
+#undef YK_FS_SLOT
+        node = h3 ? ch.w : (h2 ? ch.z : (h1 ? ch.y : (h0 ? ch.x : popped)));
+        // (written unconditionally at the top: up to two entries past the capacity, which the stack has)
+        stk[sp * kThreads] = ch.x;
+        sp += (h0 && (h1 || h2 || h3)) ? 1u : 0u;
+        stk[sp * kThreads] = ch.y;
+        sp += (h1 && (h2 || h3)) ? 1u : 0u;
+        stk[sp * kThreads] = ch.z;
+        sp += (h2 && h3) ? 1u : 0u;
+        sp -= (h0 || h1 || h2 || h3) ? 0u : 1u;
+        if (sp > a.stack_cap) {  // stack overflow: the ordered scan decides
+          scan = true;
+          break;
+        }
+      }
+      if (scan) break;
+      const uint32_t v = ~(uint32_t)node, first = v >> 4, cnt = v & 15u;
+      for (uint32_t k = 0; k < cnt; ++k) {
+        const uint32_t slot = first + k;
+        if (slot >= a.nspheres) break;  // (never: a leaf outside the table)
+        const SphereGeo sg = a.leaf_geo[slot];
+        const uint32_t id = a.leaf_ids[slot];
+        const v3 oc = {o.x - sg.cx, o.y - sg.cy, o.z - sg.cz};
+        const double hb = ykd::dot(oc, d);
+        const double cc = ykd::len2(oc) - sg.rr;
+        const double disc = hb * hb - aa * cc;
+        if (disc < 0) continue;
+        const double sq = ykd::nsqrt(disc);
+        double r = (-hb - sq) / aa;
+        if (r < tmin) r = (-hb + sq) / aa;
+        // the minimum root wins, an exact tie goes to the later tuple index
+        if (r >= tmin && (r < best || (r == best && (int)id > best_id))) {
+          best = r;
+          best_id = (int)id;
+          ustar = ykcast::f32_up(best) * (1.0f + 0x1p-18f);
+        }
+      }
+      if (sp == 0) break;  // (the sentinel was this leaf)
+      --sp;
+      node = stk[sp * kThreads];
+    }
+  }
+  if (scan) best_id = scan_hit(a, o, d, aa, best);
+  t = best;
+  return best_id;
+}
+
+// the channels of a sample from its hit (the pinhole pass's rule), folded into s and q
+__device__ __forceinline__ void fold_sample(const SfArgs& a, v3 o, v3 d, int hid, double t, double (&s)[kYkFeatChannels],
+                                            double (&q)[kYkFeatChannels]) {
+  double f[kYkFeatChannels] = {1.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0};
+  if (hid >= 0) {
+    const SphereGeo sg = a.geo[hid];
+    const SphereMat& m = a.mat[hid];
+    // hit record (sphere.hpp:41-45, hittable.hpp:23-27)
+    const v3 p = ykd::add(o, ykd::mul(d, t));
+    const v3 outward = ykd::divs(ykd::sub(p, v3{sg.cx, sg.cy, sg.cz}), m.radius);
+    const bool front = ykd::dot(d, outward) < 0;
+    const v3 nrm = front ? outward : ykd::neg(outward);
+    if (m.kind != YK_MATERIAL_DIELECTRIC) {
+      f[0] = m.ar;
+      f[1] = m.ag;
+      f[2] = m.ab;
+    }
+    f[3] = nrm.x;
+    f[4] = nrm.y;
+    f[5] = nrm.z;
+    f[6] = t;
+  }
+#pragma unroll
+  for (uint32_t c = 0; c < kYkFeatChannels; ++c) {
+    s[c] = film_add(s[c], f[c]);
+    q[c] = film_add(q[c], film_mul(f[c], f[c]));
+  }
+}
+
+// F, U and the group sums of pixel `at` from the folds over n samples
+__device__ __forceinline__ void store_planes(const SfArgs& a, size_t at, const double (&s)[kYkFeatChannels],
+                                             const double (&q)[kYkFeatChannels]) {
+  const double G = (double)a.n;
+  const double den = film_mul(G, film_sub(G, 1.0));
+  double U[kYkFeatChannels];
+#pragma unroll
+  for (uint32_t c = 0; c < kYkFeatChannels; ++c) {
+    const double var = film_div(film_sub(q[c], film_div(film_mul(s[c], s[c]), G)), den);
+    U[c] = a.n >= 2 && var > 0.0 ? var : 0.0;
+    a.out[(size_t)c * a.npix + at] = film_div(s[c], G);
+    a.out[(size_t)(kYkFeatChannels + c) * a.npix + at] = U[c];
+  }
+  a.out[(size_t)14 * a.npix + at] = film_add(film_add(U[0], U[1]), U[2]);
+  a.out[(size_t)15 * a.npix + at] = film_add(film_add(U[3], U[4]), U[5]);
+  a.out[(size_t)16 * a.npix + at] = U[6];
+}
+
+// a start's engine from its seed and, for mt19937, the walked x_397
+__device__ __forceinline__ void engine_start(ykd::MtLane& g, uint32_t seed, uint32_t x397) {
+  g.state = nullptr;  // (the lazy cursors only)
+  ykd::mt_start_from(g, seed, x397);
+}
+__device__ __forceinline__ void engine_start(ykd::X128Lane& g, uint32_t seed, uint32_t) { ykd::x128_start(g, seed); }
+// whether the lens loop's next try (four words) stays inside the lazy cursors' words
+__device__ __forceinline__ bool lens_try_ok(const ykd::MtLane& g, uint32_t lazy_words) { return g.j + 4 <= lazy_words; }
+__device__ __forceinline__ bool lens_try_ok(const ykd::X128Lane&, uint32_t) { return true; }
+template <class Gen>
+__device__ __forceinline__ void walk(uint32_t (&x)[kWalk]) {
+  if constexpr (std::is_same<Gen, ykd::MtLane>::value) ykd::mt_walk397xn<(int)kWalk>(x);
+}
+
+template <class Gen>
+__global__ __launch_bounds__(kThreads) void yk_film_features_sampled(SfArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int32_t fs_stack[];  // [entry][lane]: (stack_cap + 3) x kThreads
+  const uint32_t tid = threadIdx.x;
+  const uint32_t wave = tid / 64u, lane = tid & 63u;
+  const uint32_t px = blockIdx.x * kBlockW + wave * kWave + (lane & (kWave - 1u));
+  const uint32_t py = blockIdx.y * kBlockH + lane / kWave;
+  const bool mine = py < a.rows && px < a.wt;
+  uint32_t nh = 0;
+  if (mine) {
+    const uint32_t x = image_x(a, px), y = image_y(a, py);
+    const bool lens = a.cam.lens_radius > 0;
+    double s[kYkFeatChannels], q[kYkFeatChannels];
+#pragma unroll
+    for (uint32_t c = 0; c < kYkFeatChannels; ++c) s[c] = q[c] = 0.0;
+    bool listed = false;
+    for (uint32_t k = 0; k < a.n && !listed; k += kWalk) {
+      uint32_t seed[kWalk], x397[kWalk];
+#pragma unroll
+      for (uint32_t j = 0; j < kWalk; ++j)  // (past n: walked, not used)
+        x397[j] = seed[j] = ykd::sample_seed(a.seed_mode, a.seed_key, a.seed0, y, x, a.W, a.spp, k + j);
+      walk<Gen>(x397);
+#pragma unroll 1
+      for (uint32_t j = 0; j < kWalk && k + j < a.n; ++j) {
+        const uint32_t sj = j == 0 ? seed[0] : j == 1 ? seed[1] : j == 2 ? seed[2] : seed[3];
+        const uint32_t xj = j == 0 ? x397[0] : j == 1 ? x397[1] : j == 2 ? x397[2] : x397[3];
+        Gen g;
+        engine_start(g, sj, xj);
+        const double uc = ykd::canonical<true>(g);  // source.cpp:162
+        const double vc = ykd::canonical<true>(g);  // source.cpp:163
+        double lx = 0.0, ly = 0.0;
+        if (lens) {
+          for (;;) {  // random_in_unit_disk by rejection, x then y
+            if (!lens_try_ok(g, a.lazy_words)) {
+              listed = true;
+              break;
+            }
+            lx = ykd::uniform<true>(g, -1, 1);
+            ly = ykd::uniform<true>(g, -1, 1);
+            if (lx * lx + ly * ly < 1.0) break;
+          }
+          if (listed) break;
+        }
+        v3 o, d;
+        start_ray(a, x, y, uc, vc, lens, lx, ly, o, d);
+        double t = 0.0;
+        const int hid = closest_hit(a, fs_stack + tid, o, d, t);
+        nh += hid >= 0 ? 1u : 0u;
+        fold_sample(a, o, d, hid, t, s, q);
+      }
+    }
+    if (listed) {
+      // the lens loop outran the lazy cursors: yk_film_features_redo runs the pixel's samples
+      nh = 0;
+      a.redo[1 + atomicAdd(a.redo, 1u)] = py * a.wt + px;
+    } else {
+      store_planes(a, (size_t)py * a.wt + px, s, q);
+    }
+  }
+  // one atomic per wave (every lane of the block is here)
+  const uint32_t wh = ykcast::wave_sum(nh);
+  if (lane == 0 && wh) atomicAdd(a.hits, (unsigned long long)wh);
+}
+
+__global__ __launch_bounds__(kRedoEngines) void yk_film_features_redo(SfArgs a) {
+  const uint32_t count = a.redo[0] < a.npix ? a.redo[0] : a.npix;
+  ykd::MtFull g;
+  g.st = a.redo + 1 + a.npix + (size_t)threadIdx.x * ykd::kMtN;
+  uint32_t nh = 0;
+  const bool lens = a.cam.lens_radius > 0;
+  for (uint32_t e = threadIdx.x; e < count; e += kRedoEngines) {
+    const uint32_t at = a.redo[1 + e];
+    if (at >= a.npix) continue;  // (never)
+    const uint32_t py = at / a.wt, px = at - py * a.wt;
+    const uint32_t x = image_x(a, px), y = image_y(a, py);
+    double s[kYkFeatChannels], q[kYkFeatChannels];
+#pragma unroll
+    for (uint32_t c = 0; c < kYkFeatChannels; ++c) s[c] = q[c] = 0.0;
+    for (uint32_t k = 0; k < a.n; ++k) {
+      ykd::mt_full_seed(g, ykd::sample_seed(a.seed_mode, a.seed_key, a.seed0, y, x, a.W, a.spp, k));
+      const double uc = ykd::canonical(g);
+      const double vc = ykd::canonical(g);
+      double lx = 0.0, ly = 0.0;
+      if (lens) {
+        do {
+          lx = ykd::uniform(g, -1, 1);
+          ly = ykd::uniform(g, -1, 1);
+        } while (!(lx * lx + ly * ly < 1.0));
+      }
+      v3 o, d;
+      start_ray(a, x, y, uc, vc, lens, lx, ly, o, d);
+      double t = 0.0;
+      int hid = -1;
+      if (ykcast::in_domain(o, d, a.t_min, INFINITY, a.extent)) hid = scan_hit(a, o, d, ykd::len2(d), t);
+      nh += hid >= 0 ? 1u : 0u;
+      fold_sample(a, o, d, hid, t, s, q);
+    }
+    store_planes(a, at, s, q);
+  }
+  const uint32_t wh = ykcast::wave_sum(nh);
+  if (threadIdx.x == 0 && wh) atomicAdd(a.hits, (unsigned long long)wh);
+}
+
+// the lazy-word limit of the next passes; 0: ykd::kLazyDraws (yk_features_sampled_lazy_words below)
+std::atomic<uint32_t> g_lazy_words{0};
+
+// n_samples against the film: 1..min(256, target)
+int check_n(const ykgpu_film* film, uint32_t n) {
+  if (n < 1 || n > kMaxSamples) return fail(YK_ERR_INVALID, "features: n_samples must be 1..256");
+  if (n > film->p.samples_per_pixel) return fail(YK_ERR_INVALID, "features: n_samples is larger than the film's target");
+  return YK_OK;
+}
+
+int check(const ykgpu_film* film, uint32_t n_samples) {
+  if (int rc = check_n(film, n_samples)) return rc;
+  if (film->scene_gen != film->ctx->scene_gen)
+    return fail(YK_ERR_INVALID, "the context's scene was set after the film was created");
+  return YK_OK;
+}
+
+int ensure(ykgpu_film* film, uint32_t n, const double** planes, yk_sampled_features_stats* stats) {
+  if (int rc = check(film, n)) return rc;
+  const ykgpu_context* ctx = film->ctx;
+  YK_HIP(hipSetDevice(film->device));
+  const yk_render_params& p = film->p;
+  const uint32_t rows = p.row_count, wt = tile_width(&p);
+  const hipStream_t stream = ctx->stream;  // (film calls are synchronous on it)
+  const size_t npix = (size_t)rows * wt;
+  if (!film->d_features) {  // (a film's tile never changes size)
+    film->feature_grid = film->feature_n = 0;
+    YK_HIP(hipMalloc(&film->d_features, kYkFeatPlanes * npix * sizeof(double)));
+  }
+  *planes = (const double*)film->d_features;
+  yk_sampled_features_stats st{};
+  st.samples = (uint64_t)npix * n;
+  if (film->feature_n == n) {  // (ms = 0: the cached pass)
+    st.hits = film->feature_hits;
+    st.redo_pixels = film->feature_redo;
+    if (stats) *stats = st;
+    return YK_OK;
+  }
+  film->feature_grid = film->feature_n = 0;  // (until the pass is whole)
+
+  // the pass's own memory: the hit counter, the redo list and its engines
+  const size_t redo_words = 1 + npix + (size_t)kRedoEngines * ykd::kMtN;
+  char* d_work = nullptr;
+  YK_HIP(hipMalloc(&d_work, 16 + redo_words * sizeof(uint32_t)));
+  const DevTree& t = ctx->t64;
+  SfArgs a{};
+  a.cam = ctx->cam;
+  a.nodes = (const char*)t.nodes;
+  a.leaf_geo = (const SphereGeo*)t.leaf_geo;
+  a.leaf_ids = t.leaf_ids;
+  a.geo = ctx->d_geo;
+  a.mat = ctx->d_mat;
+  a.out = (double*)film->d_features;
+  a.hits = (unsigned long long*)d_work;
+  a.redo = (uint32_t*)(d_work + 16);
+  a.t_min = p.t_min;
+  a.extent = ctx->cast_extent;
+  a.origin_bound = t.origin_bound;
+  a.seed_key = p.seed_key;
+  a.seed0 = p.seed0;
+  a.seed_mode = p.seed_mode == YK_SEED_RANDOM_DEVICE ? 1u : 0u;
+  a.spp = p.samples_per_pixel;
+  a.n = n;
+  const uint32_t lw = g_lazy_words.load();
+  a.lazy_words = lw ? std::max(kLazyMin, std::min(lw, ykd::kLazyDraws)) : ykd::kLazyDraws;
+  a.scan_only = (p.flags & YK_FLAG_LINEAR_SCAN) ? 1u : 0u;
+  a.root = t.root;
+  a.node_bytes = t.n_nodes * (uint32_t)sizeof(DevNode);
+  a.nspheres = ctx->nspheres;
+  a.stack_cap = std::max(kStackMin, std::min(3 * t.wide_depth + 1, kStackMax));
+  a.W = p.image_width;
+  a.H = p.image_height;
+  a.rows = rows;
+  a.wt = wt;
+  a.npix = (uint32_t)npix;
+  const TileCols cols = film_cols(film);
+  a.row_begin = p.row_begin;
+  a.row_stride = p.row_stride;
+  a.row_band = p.row_band_log2;
+  a.col_begin = cols.begin;
+  a.col_stride = cols.stride;
+  a.col_band = cols.band;
+  const bool x128 = p.rng == YK_RNG_XOR128;
+
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  hipError_t e = hipEventCreate(&ev[0]);
+  if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+  if (e == hipSuccess) e = hipMemsetAsync(d_work, 0, 16 + sizeof(uint32_t), stream);  // the counter and the list's count
+  if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
+  if (e == hipSuccess) {
+    const dim3 blocks((wt + kBlockW - 1) / kBlockW, (rows + kBlockH - 1) / kBlockH);
+    // (the branch-free visit writes up to two entries past the capacity before its check)
+    const size_t lds = (size_t)(a.stack_cap + 3) * kThreads * sizeof(int32_t);
+    if (x128)
+      hipLaunchKernelGGL(yk_film_features_sampled<ykd::X128Lane>, blocks, dim3(kThreads), lds, stream, a);
+    else
+      hipLaunchKernelGGL(yk_film_features_sampled<ykd::MtLane>, blocks, dim3(kThreads), lds, stream, a);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && !x128) {  // (almost always finds its list empty)
+    hipLaunchKernelGGL(yk_film_features_redo, dim3(1), dim3(kRedoEngines), 0, stream, a);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
+  struct {
+    unsigned long long hits, pad;
+    uint32_t listed;
+  } back{};
+  if (e == hipSuccess) e = hipMemcpyAsync(&back, d_work, 16 + sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  float ms = 0;
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  for (hipEvent_t v : ev)
+    if (v) (void)hipEventDestroy(v);
+  (void)hipFree(d_work);
+  if (e != hipSuccess)
+    return fail(e == hipErrorOutOfMemory ? YK_ERR_NOMEM : YK_ERR_DEVICE,
+                std::string("ykgpu_film_features_sampled: ") + hipGetErrorString(e));
+  film->feature_n = n;
+  film->feature_hits = back.hits;
+  film->feature_redo = back.listed;
+  st.ms = ms;
+  st.hits = back.hits;
+  st.redo_pixels = back.listed;
+  if (stats) *stats = st;
+  return YK_OK;
+}
+
+}  // namespace
+}  // namespace ykfs
+
+int ykhost::yk_film_features_sampled_check(const ykgpu_film* film, uint32_t n_samples) {
+  return ykfs::check(film, n_samples);
+}
+int ykhost::yk_film_features_sampled_ensure(ykgpu_film* film, uint32_t n_samples, const double** planes,
+                                            yk_sampled_features_stats* stats) {
+  return ykfs::ensure(film, n_samples, planes, stats);
+}
+
+extern "C" {
+
+// Lowers the words a start may draw from the lazy cursors for the passes that follow (clamped to
+// 4..227; 0 restores the default), so that a test reaches yk_film_features_redo: 55 rejections in a
+// row never happen on their own.  For the tests, like yk_schedule_plan: not part of the C-ABI
+// (include/ykgpu.h does not declare it).
+void yk_features_sampled_lazy_words(uint32_t words) { ykfs::g_lazy_words.store(words); }
+
+int ykgpu_film_features_sampled(ykgpu_film* film, uint32_t n_samples, double* mean_host, double* var_host,
+                                yk_sampled_features_stats* stats) {
+  if (int rc = film_ready(film)) return rc;
+  const double* planes = nullptr;
+  yk_sampled_features_stats st{};
+  if (int rc = yk_film_features_sampled_ensure(film, n_samples, &planes, &st)) return rc;
+  if (int rc = yk_film_features_copy_out(film, planes, mean_host, var_host)) return rc;
+  if (stats) *stats = st;
+  return YK_OK;
+}
+
+}  // extern "C"
+
+#endif

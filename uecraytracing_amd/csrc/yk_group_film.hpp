@@ -116,9 +116,17 @@ void gf_make_bands(ykgpu_group_film* f, uint32_t halo, const std::vector<ykplan:
   f->have_bands = true;
 }
 
-// Both filters.  fp: the guided filter's feature parameters, null for the colour-only one.
-int gf_denoise(ykgpu_group_film* f, const yk_denoise_params& dp, const yk_feature_params* fp, double* mean_host,
-               uint8_t* rgb_host, yk_group_denoise_stats* stats) {
+// n_samples of a sampled feature pass against the group film's target
+int gf_check_n(const ykgpu_group_film* f, uint32_t n) {
+  if (n < 1 || n > 256) return fail(YK_ERR_INVALID, "features: n_samples must be 1..256");
+  if (n > f->p.samples_per_pixel) return fail(YK_ERR_INVALID, "features: n_samples is larger than the film's target");
+  return YK_OK;
+}
+
+// Both filters.  fp: the guided filter's feature parameters, null for the colour-only one;
+// n_samples != 0: the guides are the sampled pass's (fp->grid is not read).
+int gf_denoise(ykgpu_group_film* f, const yk_denoise_params& dp, const yk_feature_params* fp, uint32_t n_samples,
+               double* mean_host, uint8_t* rgb_host, yk_group_denoise_stats* stats) {
   const auto t0 = std::chrono::steady_clock::now();
   if (int rc = gf_ready(f)) return rc;
   if (int rc = denoise_params_check(dp)) return rc;
@@ -152,7 +160,13 @@ int gf_denoise(ykgpu_group_film* f, const yk_denoise_params& dp, const yk_featur
     for (uint32_t e = 0; fp && e < k; ++e) {
       if (!f->band[e]) continue;
       double t = 0;
-      if (int rc = yk_film_features_ensure(f->band[e], fp->grid, &feat[e], &t)) return entry_fail(e, rc);
+      if (n_samples) {
+        yk_sampled_features_stats fs{};
+        if (int rc = yk_film_features_sampled_ensure(f->band[e], n_samples, &feat[e], &fs)) return entry_fail(e, rc);
+        t = fs.ms;
+      } else if (int rc = yk_film_features_ensure(f->band[e], fp->grid, &feat[e], &t)) {
+        return entry_fail(e, rc);
+      }
       ms_feat = std::max(ms_feat, t);
     }
     // (a) the moments, on every entry's own film
@@ -555,7 +569,7 @@ int ykgpu_group_film_denoise(ykgpu_group_film* f, const yk_denoise_params* param
   yk_denoise_params dp;
   yk_denoise_defaults(&dp);
   if (params) dp = *params;
-  return gf_denoise(f, dp, nullptr, mean_host, rgb_host, stats);
+  return gf_denoise(f, dp, nullptr, 0, mean_host, rgb_host, stats);
 }
 
 int ykgpu_group_film_denoise_guided(ykgpu_group_film* f, const yk_denoise_params* colour, const yk_feature_params* feat,
@@ -565,7 +579,54 @@ int ykgpu_group_film_denoise_guided(ykgpu_group_film* f, const yk_denoise_params
   yk_guided_defaults(&dp, &fp);
   if (colour) dp = *colour;
   if (feat) fp = *feat;
-  return gf_denoise(f, dp, &fp, mean_host, rgb_host, stats);
+  return gf_denoise(f, dp, &fp, 0, mean_host, rgb_host, stats);
+}
+
+int ykgpu_group_film_features_sampled(ykgpu_group_film* f, uint32_t n_samples, double* mean_host, double* var_host,
+                                      yk_sampled_features_stats* stats) {
+  if (int rc = gf_ready(f)) return rc;
+  if (int rc = gf_check_n(f, n_samples)) return rc;
+  if (int rc = gf_stale(f)) return rc;
+  const bool want = mean_host || var_host;
+  std::vector<std::vector<double>> m(f->k), v(f->k);
+  yk_sampled_features_stats sum{};
+  for (uint32_t e = 0; e < f->k; ++e) {
+    if (!f->film[e]) continue;
+    if (want) {
+      m[e].resize(gf_sub_npix(f, e) * 7);
+      v[e].resize(m[e].size());
+    }
+    yk_sampled_features_stats st{};
+    if (const int rc = ykgpu_film_features_sampled(f->film[e], n_samples, want ? m[e].data() : nullptr,
+                                                   want ? v[e].data() : nullptr, &st))
+      return entry_fail(e, rc);
+    sum.ms = std::max(sum.ms, st.ms);
+    sum.samples += st.samples;
+    sum.hits += st.hits;
+    sum.redo_pixels += st.redo_pixels;
+  }
+  // (the caller's arrays are written only once every entry's pass is in)
+  for (uint32_t e = 0; want && e < f->k; ++e) {
+    if (!f->film[e]) continue;
+    if (mean_host) gf_scatter(f, e, m[e].data(), mean_host, 7);
+    if (var_host) gf_scatter(f, e, v[e].data(), var_host, 7);
+  }
+  if (stats) *stats = sum;
+  return YK_OK;
+}
+
+int ykgpu_group_film_denoise_guided_sampled(ykgpu_group_film* f, const yk_denoise_params* colour,
+                                            const yk_feature_params* feat, uint32_t n_samples, double* mean_host,
+                                            uint8_t* rgb_host, yk_group_denoise_stats* stats) {
+  yk_denoise_params dp;
+  yk_feature_params fp;
+  yk_guided_sampled_defaults(&dp, &fp, nullptr);
+  if (colour) dp = *colour;
+  if (feat) fp = *feat;
+  fp.grid = 1;  // (not read, so not validated)
+  if (int rc = gf_ready(f)) return rc;
+  if (int rc = gf_check_n(f, n_samples)) return rc;
+  return gf_denoise(f, dp, &fp, n_samples, mean_host, rgb_host, stats);
 }
 
 }  // extern "C"

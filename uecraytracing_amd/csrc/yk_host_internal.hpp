@@ -226,9 +226,13 @@ struct ykgpu_film {
   uint32_t g_slots = 0;  // != 0: launch() renders the group (d_gorder, d_gmap) instead of the film's order
   // ykgpu_film_denoise's buffers (yk_denoise.hip), allocated at the film's first denoise
   void* d_denoise = nullptr;
-  // ykgpu_film_features' planes (yk_features.hip), allocated at the first pass, and their grid
+  // ykgpu_film_features' planes (yk_features.hip), allocated at the first pass, and their key: the
+  // pinhole pass's grid or the sampled pass's n (yk_features_sampled.hpp), at most one of them not 0,
+  // with the sampled pass's counts (yk_sampled_features_stats)
   void* d_features = nullptr;
   uint32_t feature_grid = 0;
+  uint32_t feature_n = 0, feature_redo = 0;
+  uint64_t feature_hits = 0;
   bool uniform() const { return hist.size() <= 1; }
 };
 
@@ -318,6 +322,15 @@ hipError_t denoise_band_enqueue(ykgpu_film* band, const DenoiseBufs& b, const yk
 // time, 0 when the cached planes were reused.  Synchronous.  YK_ERR_INVALID on a stale scene or a
 // grid out of range.
 int yk_film_features_ensure(ykgpu_film* film, uint32_t grid, const double** planes, double* ms);
+// ... and from the first hits of the film's own first n samples (yk_features_sampled.hpp): the
+// checks alone (n in 1..min(256, target), a stale scene: YK_ERR_INVALID), and the pass with them;
+// *stats (may be null) receives the counts of the pass that made the planes, ms = 0 when they were
+// reused.  Either kind of pass replaces the other's planes.
+int yk_film_features_sampled_check(const ykgpu_film* film, uint32_t n_samples);
+int yk_film_features_sampled_ensure(ykgpu_film* film, uint32_t n_samples, const double** planes,
+                                    yk_sampled_features_stats* stats);
+// the feature planes' F and U into the caller's pixel-major arrays (either may be null)
+int yk_film_features_copy_out(ykgpu_film* film, const double* planes, double* mean_host, double* var_host);
 
 // What the denoise and feature units derive from a film:
 // its per-slot counts, null while the film is uniform (every count == done)

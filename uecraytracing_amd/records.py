@@ -235,6 +235,21 @@ class GuidedStats(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class SampledFeaturesStats(ctypes.Structure):
+    """yk_sampled_features_stats (include/ykgpu.h "sampled film features"): the pass that made a film's
+    sampled feature planes."""
+    _fields_ = [
+        ("ms", ctypes.c_double),  # 0 when the cached pass was reused
+        ("samples", ctypes.c_uint64),  # pixels * n
+        ("hits", ctypes.c_uint64),
+        ("redo_pixels", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved"}
+
+
 HIT_HIT = 1  # yk_hit.flags (include/ykgpu.h "ray queries")
 HIT_FRONT_FACE = 2
 HIT_OUT_OF_DOMAIN = 4
