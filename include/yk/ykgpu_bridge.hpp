@@ -661,6 +661,22 @@ class renderer {
     return out;
   }
 
+  // diffuse radiance at points (include/ykgpu.h "gather queries"): per point the fold of n_samples
+  // lambertian scatters at (p, n), each followed by ray_color with depth max_depth; the engine and
+  // t_min are the options'.  One context only.
+  std::vector<yk_gather> gather(const std::vector<yk_gather_point>& points, uint32_t n_samples, uint32_t max_depth,
+                                const render_options& o = render_options{}) {
+    if (!ctx_ || group_) throw error(YK_ERR_UNSUPPORTED, "gather queries belong to one context: not a device group");
+    yk_gather_params p{};
+    p.n_samples = n_samples;
+    p.max_depth = max_depth;
+    p.rng = o.rng;
+    p.t_min = o.t_min;
+    std::vector<yk_gather> out(points.size());
+    check(ykgpu_gather_points(ctx_, &p, points.data(), points.size(), out.data()), "ykgpu_gather_points");
+    return out;
+  }
+
   // the last render's statistics (a group: the whole call, include/ykgpu.h)
   yk_render_stats stats() {
     yk_render_stats s;

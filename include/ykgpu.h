@@ -903,6 +903,106 @@ int yk_camera_sample_ray(const yk_camera* camera, const yk_render_params* params
 int yk_camera_sample_rays(const yk_camera* camera, const yk_render_params* params, const uint32_t* ys,
                           const uint32_t* xs, const uint32_t* ss, uint64_t n, yk_path_ray* out);
 
+/* ---- gather queries (ABI 11) -----------------------------------------------
+ * Diffuse radiance at arbitrary points: for a point p with a normal n, the colours of N rays
+ * scattered the way the reference's lambertian scatters (material.hpp:50-59: lambertian::scatter,
+ * then ray_color of the scattered ray), folded on the device.  A gather at (p, n) is "the colour a
+ * white lambertian surface at p facing n returns".  FP64 only, one context only: T = float and
+ * device groups are out of scope.
+ * (Added under ABI 11 like the films: nothing that existed changed size or meaning.)
+ *
+ * MEANING.  For point i and s = 0 .. N-1, in order:
+ *   g   = Engine(seed_i + s) after g.discard(skip_i)           (seed_i + s in uint32: it wraps)
+ *   ru  = random(-1, 1)                  three uniforms, two words each: 6 words
+ *   ru  = ru / math::sqrt(dot(ru, ru))
+ *   d   = n_i + ru;   if (|d.x| < 1e-8 && |d.y| < 1e-8) d = n_i     (the reference's near_zero, x/y only)
+ *   c_s = ray_color(ray(p_i, d), world, max_depth, g)               (g goes on from word skip_i + 6)
+ * c_s and its flags are, by definition, the yk_radiance record of ykgpu_radiance_rays for the path
+ * ray (p_i, d, seed_i + s, skip_i + 6), computed with the same max_depth, t_min, rng and flags;
+ * yk_gather_sample_ray returns that path ray.  The record of the point is the fold of its samples:
+ *   sum    = ((0 + c_0) + c_1) + ... + c_{N-1}
+ *   sumsq  = q + (c*c) per sample: the product rounded to double, then the sum; no FMA
+ *   open   = samples whose gather ray hit nothing (YK_RAD_SKY with segments == 1)
+ *   flags  = OR over the samples of (record.flags & (YK_RAD_OUT_OF_DOMAIN | YK_RAD_MT_FALLBACK))
+ *   - a sample ray outside the radiance queries' domain contributes colour +0.0 and sets
+ *     YK_RAD_OUT_OF_DOMAIN;
+ *   - a point with skip > 221 does no arithmetic: its path rays carry the direction (+0, +0, +0),
+ *     so all its samples are out of domain: sums +0.0, open 0.  (The six scatter words must lie
+ *     inside mt19937's 227 lazy words; xor128 has the same limit so that the contract has one
+ *     rule.)  So does a point whose n is zero in all three components, which faces nowhere;
+ *   - both are a per-point status, as out-of-domain rays are in the queries: one bad point does
+ *     not void a batch;
+ *   - every + - * / is one IEEE double operation, never fused;
+ *   - a record depends on its point and the scene alone, never on the batch or the point's place
+ *     in it.
+ *
+ * THE TIE TO THE RENDER.  For a camera sample whose first hit is a lambertian sphere with albedo a:
+ * p and n that hit's p and normal as ykgpu_cast_rays returns them, seed and skip what
+ * yk_camera_sample_ray returns, N = 1 and max_depth = D - 1.  Then a * sum (one multiplication per
+ * channel) is the sample's colour bit for bit, and skip + 6 + the path's words its word count.
+ *
+ * The call is processed in chunks of max(1, floor(2^22 / N)) whole points (no fold is carried
+ * across chunks) through the radiance queries' staging and scratch, so the gathers and the
+ * radiance queries of one context run one after the other, whatever their streams, and
+ * ykgpu_set_scene waits for both.  ykgpu_gather_points is synchronous and records yk_gather_stats
+ * (ykgpu_gather_get_stats: the last synchronous call).  ykgpu_gather_points_async launches on
+ * `stream` (NULL: the context's), reads n yk_gather_point at points_device and writes n yk_gather
+ * at out_device (both 16-byte aligned device memory); it neither synchronises nor records
+ * statistics.  Films, the rings and the render streams are untouched.
+ *   n == 0               YK_OK, nothing done
+ *   YK_ERR_INVALID       a null pointer; unknown flag bits; n_samples outside 1..65536; max_depth
+ *                        outside 1..65535; t_min not finite and >= 0; non-zero reserved fields of
+ *                        the params
+ *   YK_ERR_NO_SCENE      a call before ykgpu_set_scene
+ *   YK_ERR_UNSUPPORTED   an unknown rng */
+typedef struct yk_gather_point {   /* 64 bytes */
+  double p[3];                     /* origin of every gather ray                                   */
+  double n[3];                     /* hit_record.normal of the scatter; used as given, never normalised */
+  uint32_t seed;                   /* sample s draws from Engine(seed + s), uint32 wrap            */
+  uint32_t skip;                   /* engine words discarded before the scatter's draws; <= 221     */
+  uint64_t reserved;               /* 0 */
+} yk_gather_point;
+
+typedef struct yk_gather {         /* 64 bytes */
+  double sum[3];                   /* ((0 + c_0) + c_1) + ... + c_{N-1}                             */
+  double sumsq[3];                 /* q = q + (c*c): product rounded to double, then the sum; no FMA */
+  uint32_t samples;                /* N */
+  uint32_t open;                   /* samples whose gather ray hit nothing (YK_RAD_SKY with segments == 1) */
+  uint32_t flags;                  /* OR over the samples of (record.flags & (YK_RAD_OUT_OF_DOMAIN | YK_RAD_MT_FALLBACK)) */
+  uint32_t reserved;               /* 0 */
+} yk_gather;
+
+typedef struct yk_gather_params {  /* 32 bytes */
+  uint32_t n_samples;              /* N, 1 .. 65536 */
+  uint32_t max_depth;              /* 1 .. 65535: ray_color's depth argument for the gather ray */
+  uint32_t rng, flags;             /* YK_RNG_*; YK_RADIANCE_LINEAR_SCAN | YK_RADIANCE_COUNT_WORK */
+  double t_min;                    /* finite, >= 0 */
+  uint64_t reserved;               /* 0 */
+} yk_gather_params;
+
+typedef struct yk_gather_stats {   /* 64 bytes */
+  double kernel_ms, total_ms;      /* device time of the kernels; the call's host wall clock */
+  double starts_ms, fold_ms;       /* the parts of kernel_ms in yk_gather_starts and yk_gather_fold */
+  uint64_t points, rays;           /* rays = points * n_samples */
+  uint64_t open;                   /* the records' open, added up */
+  uint32_t out_of_domain;          /* POINTS with YK_RAD_OUT_OF_DOMAIN (32-bit counts stop at 0xFFFFFFFF) */
+  uint32_t mt_fallbacks;           /* POINTS with YK_RAD_MT_FALLBACK */
+} yk_gather_stats;
+
+int ykgpu_gather_points(ykgpu_context* ctx, const yk_gather_params* params, const yk_gather_point* points_host,
+                        uint64_t n, yk_gather* out_host);
+int ykgpu_gather_points_async(ykgpu_context* ctx, const yk_gather_params* params, const void* points_device,
+                              uint64_t n, void* out_device, void* stream);
+int ykgpu_gather_get_stats(ykgpu_context* ctx, yk_gather_stats* out); /* the last synchronous gather */
+
+/* The path ray of sample s of a gather point (host only, both engines): (p, d, seed + s, skip + 6)
+ * with d as MEANING defines it, (+0, +0, +0) for a point with skip > 221 or a zero n.
+ * ykgpu_radiance_rays on a point's N path rays, folded as above, is that point's yk_gather. */
+int yk_gather_sample_ray(const yk_gather_point* point, uint32_t rng, uint32_t s, yk_path_ray* out);
+/* ... for n_points points and s = 0 .. n_samples-1 into out[i * n_samples + s] */
+int yk_gather_sample_rays(const yk_gather_point* points, uint64_t n_points, uint32_t rng, uint32_t n_samples,
+                          yk_path_ray* out);
+
 /* ---- host-side scene helpers (no device needed) ---------------------------------------- */
 
 /* camera<double>{} of camera.hpp:16-27 (16:9, viewport height 2, focal length 1, origin 0). */

@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 from . import records
-from .records import CastStats, Hit, Ray, PathRay, RadianceParams, RadianceStats, Camera, DenoiseParams, DenoiseStats, FeatureParams, FilmPass, GroupDenoiseStats, GuidedStats, FilmStats, SampledFeaturesStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
+from .records import CastStats, Hit, Ray, PathRay, GatherParams, GatherStats, RadianceParams, RadianceStats, Camera, DenoiseParams, DenoiseStats, FeatureParams, FilmPass, GroupDenoiseStats, GuidedStats, FilmStats, SampledFeaturesStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(PKG_DIR, "lib")
@@ -48,6 +48,8 @@ EXPORTS = (
     "ykgpu_cast_rays", "ykgpu_cast_rays_async", "ykgpu_cast_get_stats",
     "ykgpu_radiance_rays", "ykgpu_radiance_rays_async", "ykgpu_radiance_get_stats", "yk_camera_sample_ray",
     "yk_camera_sample_rays",
+    "ykgpu_gather_points", "ykgpu_gather_points_async", "ykgpu_gather_get_stats", "yk_gather_sample_ray",
+    "yk_gather_sample_rays",
 )
 ABI_VERSION = 11
 SCENE_DIR = os.path.join(PKG_DIR, "scenes")  # committed scene files of the BASELINE configs
@@ -150,6 +152,12 @@ def load_library():
         "yk_camera_sample_ray": ([P(Camera), P(RenderParams), c.c_uint32, c.c_uint32, c.c_uint32, c.c_void_p], c.c_int),
         "yk_camera_sample_rays": ([P(Camera), P(RenderParams), c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64,
                                    c.c_void_p], c.c_int),
+        "ykgpu_gather_points": ([c.c_void_p, P(GatherParams), c.c_void_p, c.c_uint64, c.c_void_p], c.c_int),
+        "ykgpu_gather_points_async": ([c.c_void_p, P(GatherParams), c.c_void_p, c.c_uint64, c.c_void_p, c.c_void_p],
+                                      c.c_int),
+        "ykgpu_gather_get_stats": ([c.c_void_p, P(GatherStats)], c.c_int),
+        "yk_gather_sample_ray": ([c.c_void_p, c.c_uint32, c.c_uint32, c.c_void_p], c.c_int),
+        "yk_gather_sample_rays": ([c.c_void_p, c.c_uint64, c.c_uint32, c.c_uint32, c.c_void_p], c.c_int),
     }
     # the group film calls take the film calls' arguments (include/ykgpu.h "group films"); the two
     # filters report yk_group_denoise_stats
@@ -343,6 +351,35 @@ def camera_sample_rays(camera: Camera, params: RenderParams, ys, xs, ss) -> np.n
                                    ss.ctypes.data, ys.size, out.ctypes.data)
     if rc != 0:
         raise YkError(f"{records.ERRORS.get(rc, rc)}: camera_sample_rays: a sample outside the image, or fp32")
+    return out
+
+
+def gather_points(points, normals, seeds, skip=0) -> np.ndarray:
+    """records.GATHER_POINT_DTYPE[N] from points and normals float64[N, 3] and seeds and skip, scalars
+    or uint32[N]."""
+    p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
+    if p.shape != n.shape:
+        raise YkError("gather: points and normals must both be [N, 3]")
+    pts = np.zeros(p.shape[0], records.GATHER_POINT_DTYPE)
+    pts["p"], pts["n"] = p, n
+    pts["seed"] = np.broadcast_to(np.asarray(seeds, np.uint32), (len(pts),))
+    pts["skip"] = np.broadcast_to(np.asarray(skip, np.uint32), (len(pts),))
+    return pts
+
+
+def gather_sample_rays(points, n_samples: int, rng=records.RNG_MT19937) -> np.ndarray:
+    """yk_gather_sample_rays (host only): records.PATH_RAY_DTYPE[N, n_samples], the path ray of every
+    sample of records.GATHER_POINT_DTYPE[N] points.  Renderer.radiance_rays on a point's rays, folded
+    in sample order, is that point's record of Renderer.gather_points."""
+    pts = np.ascontiguousarray(points, dtype=records.GATHER_POINT_DTYPE).reshape(-1)
+    if n_samples < 1 or n_samples > records.GATHER_MAX_SAMPLES:
+        raise YkError("gather_sample_rays: n_samples must be 1..65536")
+    out = np.zeros((pts.size, n_samples), records.PATH_RAY_DTYPE)
+    rc = load_library().yk_gather_sample_rays(pts.ctypes.data if pts.size else None, pts.size, rng, n_samples,
+                                              out.ctypes.data if pts.size else None)
+    if rc != 0:
+        raise YkError(f"{records.ERRORS.get(rc, rc)}: gather_sample_rays: an unknown rng")
     return out
 
 
@@ -765,6 +802,48 @@ class Renderer:
         _check(self._lib.ykgpu_radiance_get_stats(self._ctx, ctypes.byref(st)))
         return st.as_dict()
 
+    @staticmethod
+    def _gather_params(n_samples, max_depth, t_min, rng, linear_scan, count_work) -> GatherParams:
+        flags = (records.RADIANCE_LINEAR_SCAN if linear_scan else 0) | (records.RADIANCE_COUNT_WORK if count_work else 0)
+        return GatherParams(n_samples, max_depth, rng, flags, t_min, 0)
+
+    def gather(self, points, normals, seeds, n_samples, skip=0, max_depth=50, t_min=records.T_MIN,
+               rng=records.RNG_MT19937, linear_scan: bool = False, count_work: bool = False) -> np.ndarray:
+        """Diffuse radiance at N points (include/ykgpu.h "gather queries"): points and normals
+        float64[N, 3], seeds and skip scalars or uint32[N]; per point n_samples lambertian scatters
+        (sample s from Engine(seed + s) with skip words discarded), each followed by ray_color.
+        Returns records.GATHER_DTYPE[N]: sum, sumsq, samples, open and flags."""
+        return self.gather_points(gather_points(points, normals, seeds, skip), n_samples, max_depth, t_min, rng,
+                                  linear_scan, count_work)
+
+    def gather_points(self, points, n_samples, max_depth=50, t_min=records.T_MIN, rng=records.RNG_MT19937,
+                      linear_scan: bool = False, count_work: bool = False) -> np.ndarray:
+        """gather() on records.GATHER_POINT_DTYPE[N]."""
+        pts = np.ascontiguousarray(points, dtype=records.GATHER_POINT_DTYPE).reshape(-1)
+        n = pts.size
+        out = np.zeros(n, records.GATHER_DTYPE)
+        par = self._gather_params(n_samples, max_depth, t_min, rng, linear_scan, count_work)
+        _check(self._lib.ykgpu_gather_points(self._ctx, ctypes.byref(par), pts.ctypes.data if n else None, n,
+                                             out.ctypes.data if n else None))
+        return out
+
+    def gather_device(self, points_ptr: int, n: int, out_ptr: int, n_samples: int, max_depth=50, t_min=records.T_MIN,
+                      rng=records.RNG_MT19937, linear_scan: bool = False, count_work: bool = False,
+                      stream_ptr: int = 0):
+        """Enqueue a gather over device memory (ykgpu_gather_points_async): n yk_gather_point records
+        at points_ptr, n yk_gather records written at out_ptr (e.g. [N, 8] float64 CUDA tensors'
+        data_ptr()), on the stream (0: the context's).  Does not synchronise."""
+        par = self._gather_params(n_samples, max_depth, t_min, rng, linear_scan, count_work)
+        _check(self._lib.ykgpu_gather_points_async(self._ctx, ctypes.byref(par), ctypes.c_void_p(points_ptr or None), n,
+                                                   ctypes.c_void_p(out_ptr or None),
+                                                   ctypes.c_void_p(stream_ptr or None)))
+
+    def gather_stats(self) -> dict:
+        """yk_gather_stats of the last synchronous gather()."""
+        st = GatherStats()
+        _check(self._lib.ykgpu_gather_get_stats(self._ctx, ctypes.byref(st)))
+        return st.as_dict()
+
 
 class Group:
     """Several device contexts in one process (ykgpu_group): rows dealt cyclically over the
@@ -832,5 +911,5 @@ def render_devices(devices, spheres, camera: Camera, params: RenderParams) -> np
     return out
 
 
-__all__ = ["Renderer", "Film", "GroupFilm", "GroupDenoiseStats", "Ray", "Hit", "CastStats", "PathRay", "RadianceParams", "RadianceStats", "camera_sample_rays", "FilmPass", "DenoiseParams", "DenoiseStats", "denoise_defaults", "FeatureParams", "GuidedStats", "guided_defaults", "SampledFeaturesStats", "guided_sampled_defaults", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
+__all__ = ["Renderer", "Film", "GroupFilm", "GroupDenoiseStats", "Ray", "Hit", "CastStats", "PathRay", "RadianceParams", "RadianceStats", "camera_sample_rays", "GatherParams", "GatherStats", "gather_points", "gather_sample_rays", "FilmPass", "DenoiseParams", "DenoiseStats", "denoise_defaults", "FeatureParams", "GuidedStats", "guided_defaults", "SampledFeaturesStats", "guided_sampled_defaults", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
            "make_params", "load_library", "records", "EXPORTS", "LIB_PATH", "CLI_PATH"]

@@ -19,8 +19,8 @@
 // Added (render parameters are compile-time macros in the reference): --width, --spp,
 // --depth, --scene, --scene-seed, --scene-file, --save-scene, --seed0, --precision, --rng,
 // --device, --devices (a device list as the bridge's YKGPU_DEVICES takes it: the rows dealt over a
-// group, films as group films, include/ykgpu.h "group films"), --stats, --pick and --probe (one ray query / one pixel's radiance queries instead of a
-// render), the progressive film's --progressive, --until, --checkpoint, --stop-after
+// group, films as group films, include/ykgpu.h "group films"), --stats, --pick, --probe and --gather (one ray query / one pixel's radiance queries /
+// one gather at a pixel's first hit instead of a render), the progressive film's --progressive, --until, --checkpoint, --stop-after
 // (include/ykgpu.h "progressive film": the image in chunks of samples, the same bytes as in one
 // call), and --denoise with --denoise-radius, --denoise-patch, --denoise-k2 (include/ykgpu.h "film
 // denoise": the final image and every preview through the film's variance-guided filter),
@@ -127,7 +127,13 @@ const char* kHelp =
     "                            'sample <s>: colour (<r>, <g>, <b>) words <n> segments <n> end <how>'\n"
     "                            (%.17g; how: sky|absorbed|depth|out-of-domain), then 'sum (...)',\n"
     "                            the samples added in order, and 'rgb <r> <g> <b>', the pixel of the\n"
-    "                            image (fp64 only, needs --seed0; no output file needed)\n";
+    "                            image (fp64 only, needs --seed0; no output file needed)\n"
+    "      --gather arg          arg = X,Y: cast the pixel-centre pinhole ray of --pick and run one\n"
+    "                            gather query at the hit's p and normal: --spp lambertian scatters\n"
+    "                            from seed --seed0, each followed to --depth; prints\n"
+    "                            'gather X Y: id <n> samples <N> sum (<r>, <g>, <b>) mean (<r>, <g>,\n"
+    "                            <b>) open <k>' (%.17g) or 'gather X Y: miss' (fp64 only, needs\n"
+    "                            --seed0; no output file needed)\n";
 
 struct args {
   bool help = false, verbose_flag = false, stats = false;
@@ -165,6 +171,9 @@ struct args {
   // --probe X,Y: the pixel's samples through the radiance query instead of a render
   bool have_probe = false;
   uint32_t probe_x = 0, probe_y = 0;
+  // --gather X,Y: one gather query at the pixel's first hit instead of a render
+  bool have_gather = false;
+  uint32_t gather_x = 0, gather_y = 0;
   bool film() const { return denoise || !aov.empty() || adaptive || have_progressive || have_until || have_stop_after || !checkpoint.empty(); }
 };
 
@@ -279,6 +288,14 @@ args parse(int argc, char** argv) {
         a.probe_y = to_u32(n, v.substr(c + 1));
         a.have_probe = true;
       }
+      else if (n == "gather") {
+        const std::string v = value(i, n, inl);
+        const size_t c = v.find(',');
+        if (c == std::string::npos) throw option_error{"Option 'gather' needs X,Y"};
+        a.gather_x = to_u32(n, v.substr(0, c));
+        a.gather_y = to_u32(n, v.substr(c + 1));
+        a.have_gather = true;
+      }
       else if (n == "checkpoint") {
         a.checkpoint = value(i, n, inl);
         if (a.checkpoint.empty()) throw option_error{"Option 'checkpoint' needs a file name"};
@@ -310,6 +327,11 @@ args parse(int argc, char** argv) {
   if (a.have_probe && !a.have_seed0) throw option_error{"Option 'probe' needs --seed0 (the samples it repeats)"};
   if (a.have_probe && a.precision != "fp64") throw option_error{"Option 'probe' is fp64 only"};
   if (a.have_probe && !a.spp) throw option_error{"Option 'probe' needs --spp of at least 1"};
+  if (a.have_gather && a.have_pick) throw option_error{"Options 'gather' and 'pick' exclude each other"};
+  if (a.have_gather && a.have_probe) throw option_error{"Options 'gather' and 'probe' exclude each other"};
+  if (a.have_gather && !a.have_seed0) throw option_error{"Option 'gather' needs --seed0 (the samples it draws)"};
+  if (a.have_gather && a.precision != "fp64") throw option_error{"Option 'gather' is fp64 only"};
+  if (a.have_gather && !a.spp) throw option_error{"Option 'gather' needs --spp of at least 1"};
   if (a.have_denoise_params && !a.denoise) throw option_error{"The denoise parameters need --denoise"};
   if (a.have_feature_grid && !a.denoise_features && a.aov.empty())
     throw option_error{"Option 'feature-grid' needs --denoise-features or --aov"};
@@ -343,7 +365,7 @@ int main(int argc, char* argv[]) {
     std::cerr << "raytrace: " << e.what << " (see --help)" << std::endl;
     return 2;
   }
-  if (a.help || (!a.have_output && !a.have_pick && !a.have_probe)) {
+  if (a.help || (!a.have_output && !a.have_pick && !a.have_probe && !a.have_gather)) {
     std::cout << kHelp << std::endl;
     std::exit(EXIT_SUCCESS);
   }
@@ -359,6 +381,11 @@ int main(int argc, char* argv[]) {
   }
   if (a.have_probe && (a.probe_x >= W || a.probe_y >= H)) {
     std::cerr << "raytrace: Option 'probe' names a pixel outside the " << W << " x " << H << " image (see --help)"
+              << std::endl;
+    return 2;
+  }
+  if (a.have_gather && (a.gather_x >= W || a.gather_y >= H)) {
+    std::cerr << "raytrace: Option 'gather' names a pixel outside the " << W << " x " << H << " image (see --help)"
               << std::endl;
     return 2;
   }
@@ -421,18 +448,36 @@ int main(int argc, char* argv[]) {
       gpu.set_records(s, cam);
       if (!a.save_scene.empty()) yk_scene_write(a.save_scene.c_str(), s.data(), n, &cam);
     }
-    if (a.have_pick) {
+    if (a.have_pick || a.have_gather) {
       // the feature pass's sub-ray with a = b = 0.5 (include/ykgpu.h "film features"), every step one
       // IEEE double operation, through the bridge's hit()
+      const uint32_t px = a.have_pick ? a.pick_x : a.gather_x, py = a.have_pick ? a.pick_y : a.gather_y;
       const yk_camera& c = gpu.camera();
-      const double u = ((double)a.pick_x + 0.5) / (double)W;
-      const double v = ((double)(H - a.pick_y - 1) + 0.5) / (double)H;
+      const double u = ((double)px + 0.5) / (double)W;
+      const double v = ((double)(H - py - 1) + 0.5) / (double)H;
       yk::ray<double> r{};
       r.origin = {c.origin[0], c.origin[1], c.origin[2]};
       r.direction = {((c.lower_left_corner[0] + c.horizontal[0] * u) + c.vertical[0] * v) - c.origin[0],
                      ((c.lower_left_corner[1] + c.horizontal[1] * u) + c.vertical[1] * v) - c.origin[1],
                      ((c.lower_left_corner[2] + c.horizontal[2] * u) + c.vertical[2] * v) - c.origin[2]};
       const auto rec = gpu.hit(std::vector<yk::ray<double>>{r}, ro.t_min, (double)INFINITY)[0];
+      if (a.have_gather) {
+        // one gather at the hit's (p, normal): N = --spp, seed = --seed0, skip = 0 (include/ykgpu.h
+        // "gather queries")
+        if (!rec) {
+          std::printf("gather %u %u: miss\n", px, py);
+          return EXIT_SUCCESS;
+        }
+        yk_gather_point pt{};
+        pt.p[0] = rec->p.x, pt.p[1] = rec->p.y, pt.p[2] = rec->p.z;
+        pt.n[0] = rec->normal.x, pt.n[1] = rec->normal.y, pt.n[2] = rec->normal.z;
+        pt.seed = seed0;
+        const yk_gather g = gpu.gather(std::vector<yk_gather_point>{pt}, a.spp, a.depth, ro)[0];
+        std::printf("gather %u %u: id %zu samples %u sum (%.17g, %.17g, %.17g) mean (%.17g, %.17g, %.17g) open %u\n", px,
+                    py, rec->id, g.samples, g.sum[0], g.sum[1], g.sum[2], g.sum[0] / (double)g.samples,
+                    g.sum[1] / (double)g.samples, g.sum[2] / (double)g.samples, g.open);
+        return EXIT_SUCCESS;
+      }
       if (!rec) {
         std::printf("pick %u %u: miss\n", a.pick_x, a.pick_y);
       } else {

@@ -59,6 +59,7 @@ uint64_t device_bytes(const ykgpu_context* ctx) {
   b += (uint64_t)ctx->cast_cap * (sizeof(yk_ray) + sizeof(yk_hit));
   if (ctx->d_cast_counters) b += (uint64_t)kCastStripes * kCastCounters * sizeof(unsigned long long);
   b += (uint64_t)ctx->rad_cap * (sizeof(yk_path_ray) + sizeof(yk_radiance));
+  b += (uint64_t)ctx->gat_cap * (sizeof(yk_gather_point) + sizeof(yk_gather));
   if (ctx->d_rad_x397) b += kRadChunk * sizeof(uint32_t) + sizeof(uint32_t);
   b += (uint64_t)ctx->rad_mt_lanes * ykd::kMtN * sizeof(uint32_t);
   b += (uint64_t)ctx->rad_lanes * ctx->rad_id_stride * sizeof(uint16_t);
@@ -340,7 +341,7 @@ int ykgpu_context_destroy(ykgpu_context* ctx) {
   (void)hipFree(ctx->d_cast_counters);
   if (ctx->cast_ev) (void)hipEventDestroy(ctx->cast_ev);
   for (void* q : {ctx->d_rad_rays, ctx->d_rad_out, (void*)ctx->d_rad_x397, (void*)ctx->d_rad_claim, (void*)ctx->d_rad_mt,
-                  (void*)ctx->d_rad_ids, (void*)ctx->d_rad_counters})
+                  (void*)ctx->d_rad_ids, (void*)ctx->d_rad_counters, ctx->d_gat_points, ctx->d_gat_out})
     (void)hipFree(q);
   if (ctx->rad_ev) (void)hipEventDestroy(ctx->rad_ev);
   for (hipEvent_t e : ctx->lev) (void)hipEventDestroy(e);
@@ -398,7 +399,7 @@ int ykgpu_set_scene(ykgpu_context* ctx, const yk_sphere* spheres, uint32_t count
   for (hipStream_t s : {ctx->aux, ctx->red, ctx->ren, ctx->alt}) YK_HIP(hipStreamSynchronize(s));
   // ... and for the last ray query enqueued on a caller's stream (ykgpu_cast_rays_async)
   if (ctx->cast_ev) YK_HIP(hipEventSynchronize(ctx->cast_ev));
-  // ... and for the last radiance query (ykgpu_radiance_rays_async)
+  // ... and for the last radiance query or gather (ykgpu_radiance_rays_async, ykgpu_gather_points_async)
   if (ctx->rad_ev) YK_HIP(hipEventSynchronize(ctx->rad_ev));
   ++ctx->scene_gen;  // from here on the device holds another scene: the context's films are over
   if (count > ctx->nspheres || !ctx->d_geo) {

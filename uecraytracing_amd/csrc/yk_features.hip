@@ -3,7 +3,7 @@
 // in IEEE double so that numpy restates it bit for bit (tests/film_features_ref.py).
 //
 // A unit of its own, like yk_denoise.hip (it also holds the ray queries, yk_cast.hpp, and the
-// radiance queries, yk_radiance.hpp, included at the end).  One kernel, yk_film_features, on the context's stream;
+// radiance queries, yk_radiance.hpp, and the gather queries, yk_gather.hpp, included at the end).  One kernel, yk_film_features, on the context's stream;
 // its result lives in planes the film owns (ykgpu_film, yk_host_internal.hpp) and is computed once
 // per (film, grid).  The sampled pass (yk_features_sampled.hpp) fills the same planes another way.
 #include <hip/hip_runtime.h>
@@ -273,5 +273,7 @@ int ykgpu_film_features(ykgpu_film* film, uint32_t grid, double* mean_host, doub
 #include "yk_cast.hpp"
 // ... and the radiance queries (ykgpu_radiance_rays ...), whose closest hit is the cast's
 #include "yk_radiance.hpp"
+// ... and the gather queries (ykgpu_gather_points ...), whose rays are radiance queries' rays
+#include "yk_gather.hpp"
 // ... and the sampled feature pass (ykgpu_film_features_sampled ...), whose closest hit is a copy of it
 #include "yk_features_sampled.hpp"

@@ -327,6 +327,68 @@ extern "C" int yk_camera_sample_ray(const yk_camera* cam, const yk_render_params
   return YK_OK;
 }
 
+// ---- the path rays of a gather point (include/ykgpu.h "gather queries") --------------------
+namespace {
+// math::sqrt (math.hpp:10-19) as DESIGN.md §3 describes it: x = s/2, then x <- (x + s/x)/2 until
+// two iterates are equal.  (The bound only matters for NaN and infinity, where the loop has no end.)
+double newton_sqrt(double s) {
+  double x = s / 2.0, prev = 0.0;
+  for (int guard = 0; x != prev && guard < 4096; ++guard) {
+    prev = x;
+    x = (x + s / x) / 2.0;
+  }
+  return x;
+}
+constexpr uint32_t kGatherMaxSkip = 221;  // the scatter's six words lie inside mt19937's 227 lazy words
+}  // namespace
+
+extern "C" int yk_gather_sample_ray(const yk_gather_point* pt, uint32_t rng, uint32_t s, yk_path_ray* out) {
+  if (!pt || !out) return YK_ERR_INVALID;
+  if (rng != YK_RNG_MT19937 && rng != YK_RNG_XOR128) return YK_ERR_UNSUPPORTED;
+  const uint32_t seed = pt->seed + s;
+  const d3 n = of(pt->n);
+  d3 d{0.0, 0.0, 0.0};
+  // (a point past the skip limit or with a zero normal does no arithmetic: a zero direction)
+  if (pt->skip <= kGatherMaxSkip && !(n.x == 0.0 && n.y == 0.0 && n.z == 0.0)) {
+    sample_rng g(seed, rng == YK_RNG_XOR128);
+    for (uint32_t k = 0; k < pt->skip; ++k) (void)g.next();
+    // lambertian::scatter (material.hpp:50-59) with random_unit_vector (:33-36)
+    d3 ru;
+    ru.x = g.uniform(-1, 1);
+    ru.y = g.uniform(-1, 1);
+    ru.z = g.uniform(-1, 1);
+    ru = ru / newton_sqrt(dot(ru, ru));
+    d = n + ru;
+    if (std::fabs(d.x) < 1e-8 && std::fabs(d.y) < 1e-8) d = n;  // near_zero (vec3.hpp:76-80): x and y only
+  }
+  std::memset(out, 0, sizeof(*out));
+  put(out->origin, of(pt->p));
+  put(out->direction, d);
+  out->seed = seed;
+  out->skip = pt->skip + 6u;
+  return YK_OK;
+}
+
+// ... for every sample of n_points points -> out[i * n_samples + s]; large batches are split over a
+// few host threads
+extern "C" int yk_gather_sample_rays(const yk_gather_point* points, uint64_t n_points, uint32_t rng, uint32_t n_samples,
+                                     yk_path_ray* out) {
+  if (n_points && n_samples && (!points || !out)) return YK_ERR_INVALID;
+  if (rng != YK_RNG_MT19937 && rng != YK_RNG_XOR128) return YK_ERR_UNSUPPORTED;
+  const uint64_t n = n_points * n_samples;
+  const unsigned hw = std::thread::hardware_concurrency();
+  const uint64_t nt = n < 65536 ? 1 : std::min<uint64_t>(16, hw ? hw : 1);
+  auto work = [&](uint64_t t) {
+    for (uint64_t j = n * t / nt; j < n * (t + 1) / nt; ++j)
+      (void)yk_gather_sample_ray(&points[j / n_samples], rng, (uint32_t)(j % n_samples), &out[j]);
+  };
+  std::vector<std::thread> th;
+  for (uint64_t t = 1; t < nt; ++t) th.emplace_back(work, t);
+  work(0);
+  for (std::thread& t : th) t.join();
+  return YK_OK;
+}
+
 // ---- scene files -------------------------------------------------------------------------
 // Text, one record per line, numbers as %.17g (every double round-trips exactly):
 //   yk-scene 1

@@ -193,6 +193,13 @@ struct ykgpu_context {
   unsigned long long* d_rad_counters = nullptr;
   hipEvent_t rad_ev = nullptr;
   yk_radiance_stats rad_stats{};
+  // Gather queries (yk_gather.hpp): the synchronous call's staging (gat_cap points and as many
+  // records) and statistics; a chunk's rays and their records go through the radiance queries'
+  // staging and scratch above, and rad_ev orders gathers and queries alike
+  void* d_gat_points = nullptr;
+  void* d_gat_out = nullptr;
+  size_t gat_cap = 0;
+  yk_gather_stats gat_stats{};
 };
 
 // A film (include/ykgpu.h): the accumulation state of one tile, owned by the film — the six planes

@@ -487,18 +487,11 @@ int ensure(ykgpu_context* ctx, const yk_radiance_params* p, const Plan& pl) {
   return YK_OK;
 }
 
-// the two launches over rays [0, n), n <= kRadChunk, on st; mid (may be null) is recorded between them
-hipError_t enqueue(const ykgpu_context* ctx, const yk_radiance_params* p, const Plan& pl, const void* rays, void* out,
-                   uint32_t n, unsigned long long* counters, hipStream_t st, hipEvent_t mid) {
+// the path launch alone over rays [0, n), n <= kRadChunk, on st: d_rad_x397 holds the rays' x_397
+// (mt19937), written by yk_radiance_starts or by the gather's starts kernel (yk_gather.hpp)
+hipError_t enqueue_paths(const ykgpu_context* ctx, const yk_radiance_params* p, const Plan& pl, const void* rays,
+                         void* out, uint32_t n, unsigned long long* counters, hipStream_t st) {
   const DevTree& t = ctx->t64;
-  if (p->rng == YK_RNG_MT19937) {
-    const uint32_t per = kThreads * kWalk;
-    hipLaunchKernelGGL(yk_radiance_starts, dim3((n + per - 1) / per), dim3(kThreads), 0, st, (const uint32_t*)rays, n,
-                       ctx->d_rad_x397);
-    if (hipError_t e = hipGetLastError()) return e;
-  }
-  if (mid)
-    if (hipError_t e = hipEventRecord(mid, st)) return e;
   if (hipError_t e = hipMemsetAsync(ctx->d_rad_claim, 0, sizeof(uint32_t), st)) return e;
   RadArgs a{};
   a.rays = (const double*)rays;
@@ -529,6 +522,35 @@ hipError_t enqueue(const ykgpu_context* ctx, const yk_radiance_params* p, const 
   return hipGetLastError();
 }
 
+// the two launches over rays [0, n), n <= kRadChunk, on st; mid (may be null) is recorded between them
+hipError_t enqueue(const ykgpu_context* ctx, const yk_radiance_params* p, const Plan& pl, const void* rays, void* out,
+                   uint32_t n, unsigned long long* counters, hipStream_t st, hipEvent_t mid) {
+  if (p->rng == YK_RNG_MT19937) {
+    const uint32_t per = kThreads * kWalk;
+    hipLaunchKernelGGL(yk_radiance_starts, dim3((n + per - 1) / per), dim3(kThreads), 0, st, (const uint32_t*)rays, n,
+                       ctx->d_rad_x397);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  if (mid)
+    if (hipError_t e = hipEventRecord(mid, st)) return e;
+  return enqueue_paths(ctx, p, pl, rays, out, n, counters, st);
+}
+
+// the staging of the synchronous query and of a gather's sample slots (yk_gather.hpp): `need` rays
+// and as many records, grown after the context's queries in flight
+int ensure_staging(ykgpu_context* ctx, size_t need) {
+  if (need <= ctx->rad_cap) return YK_OK;
+  YK_HIP(hipEventSynchronize(ctx->rad_ev));
+  (void)hipFree(ctx->d_rad_rays);
+  (void)hipFree(ctx->d_rad_out);
+  ctx->d_rad_rays = ctx->d_rad_out = nullptr;
+  ctx->rad_cap = 0;
+  YK_HIP(hipMalloc(&ctx->d_rad_rays, need * sizeof(yk_path_ray)));
+  YK_HIP(hipMalloc(&ctx->d_rad_out, need * sizeof(yk_radiance)));
+  ctx->rad_cap = need;
+  return YK_OK;
+}
+
 int check_call(const ykgpu_context* ctx, const yk_radiance_params* p, const void* rays, uint64_t n, const void* out) {
   if (!ctx || !p) return fail(YK_ERR_INVALID, "null argument");
   if (p->flags & ~kKnownFlags) return fail(YK_ERR_INVALID, "radiance: unknown flag bits");
@@ -557,17 +579,7 @@ int ykgpu_radiance_rays(ykgpu_context* ctx, const yk_radiance_params* params, co
   ykrad::Plan pl;
   if (int rc = ykrad::make_plan(ctx, params, pl)) return rc;
   if (int rc = ykrad::ensure(ctx, params, pl)) return rc;
-  const size_t need = (size_t)std::min<uint64_t>(n, kRadChunk);
-  if (need > ctx->rad_cap) {
-    YK_HIP(hipEventSynchronize(ctx->rad_ev));
-    (void)hipFree(ctx->d_rad_rays);
-    (void)hipFree(ctx->d_rad_out);
-    ctx->d_rad_rays = ctx->d_rad_out = nullptr;
-    ctx->rad_cap = 0;
-    YK_HIP(hipMalloc(&ctx->d_rad_rays, need * sizeof(yk_path_ray)));
-    YK_HIP(hipMalloc(&ctx->d_rad_out, need * sizeof(yk_radiance)));
-    ctx->rad_cap = need;
-  }
+  if (int rc = ykrad::ensure_staging(ctx, (size_t)std::min<uint64_t>(n, kRadChunk))) return rc;
   constexpr size_t kCounterBytes = (size_t)kRadStripes * kRadCounters * sizeof(unsigned long long);
   if (!ctx->d_rad_counters) YK_HIP(hipMalloc(&ctx->d_rad_counters, kCounterBytes));
   const hipStream_t st = ctx->stream;

@@ -367,6 +367,71 @@ RADIANCE_DTYPE = _np_dtype(["colour", "t_first", "id_first", "id_last", "words",
 assert RAY_DTYPE.itemsize == 64 and HIT_DTYPE.itemsize == 64
 assert PATH_RAY_DTYPE.itemsize == 64 and RADIANCE_DTYPE.itemsize == 64
 assert RADIANCE_DTYPE.fields["flags"][1] == 48 and PATH_RAY_DTYPE.fields["seed"][1] == 48
+GATHER_MAX_SKIP = 221  # yk_gather_point.skip (include/ykgpu.h "gather queries"): past it, out of domain
+GATHER_MAX_SAMPLES = 65536
+
+
+class GatherPoint(ctypes.Structure):
+    """yk_gather_point (include/ykgpu.h "gather queries"): a point, its normal and its samples' engines."""
+    _fields_ = [
+        ("p", D3),
+        ("n", D3),  # used as given, never normalised
+        ("seed", ctypes.c_uint32),  # sample s draws from Engine(seed + s)
+        ("skip", ctypes.c_uint32),  # engine words discarded before the scatter's draws; <= GATHER_MAX_SKIP
+        ("reserved", ctypes.c_uint64),
+    ]
+
+
+class Gather(ctypes.Structure):
+    """yk_gather (include/ykgpu.h): the fold of a point's samples."""
+    _fields_ = [
+        ("sum", D3),
+        ("sumsq", D3),
+        ("samples", ctypes.c_uint32),
+        ("open", ctypes.c_uint32),  # samples whose gather ray hit nothing
+        ("flags", ctypes.c_uint32),  # RAD_OUT_OF_DOMAIN | RAD_MT_FALLBACK of any sample
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class GatherParams(ctypes.Structure):
+    """yk_gather_params (include/ykgpu.h): samples per point, ray_color's depth, the engine, RADIANCE_* flags, t_min."""
+    _fields_ = [
+        ("n_samples", ctypes.c_uint32),  # 1..GATHER_MAX_SAMPLES
+        ("max_depth", ctypes.c_uint32),  # 1..65535
+        ("rng", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("t_min", ctypes.c_double),
+        ("reserved", ctypes.c_uint64),
+    ]
+
+
+class GatherStats(ctypes.Structure):
+    """yk_gather_stats (include/ykgpu.h): what the last synchronous ykgpu_gather_points did."""
+    _fields_ = [
+        ("kernel_ms", ctypes.c_double),
+        ("total_ms", ctypes.c_double),
+        ("starts_ms", ctypes.c_double),  # the parts of kernel_ms in the starts and the fold kernel
+        ("fold_ms", ctypes.c_double),
+        ("points", ctypes.c_uint64),
+        ("rays", ctypes.c_uint64),
+        ("open", ctypes.c_uint64),
+        ("out_of_domain", ctypes.c_uint32),  # points, not rays
+        ("mt_fallbacks", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+# numpy views of yk_gather_point and yk_gather
+GATHER_POINT_DTYPE = _np_dtype(["p", "n", "seed", "skip", "reserved"], [("<f8", 3), ("<f8", 3), "<u4", "<u4", "<u8"], 64)
+GATHER_DTYPE = _np_dtype(["sum", "sumsq", "samples", "open", "flags", "reserved"],
+                         [("<f8", 3), ("<f8", 3), "<u4", "<u4", "<u4", "<u4"], 64)
+assert ctypes.sizeof(GatherPoint) == 64 and ctypes.sizeof(Gather) == 64
+assert ctypes.sizeof(GatherParams) == 32 and ctypes.sizeof(GatherStats) == 64
+assert GATHER_POINT_DTYPE.itemsize == 64 and GATHER_DTYPE.itemsize == 64
+assert GATHER_POINT_DTYPE.fields["seed"][1] == 48 and GATHER_DTYPE.fields["samples"][1] == 48
 assert ctypes.sizeof(Sphere) == 80
 assert ctypes.sizeof(FeatureParams) == 48
 assert ctypes.sizeof(GuidedStats) == 32
