@@ -8,8 +8,10 @@ file into context, pipeline, film, group and math units behind yk_host_internal.
 (profiles/r13_units/README.md), which removed the film view the denoise and feature units worked
 through and their copies of the error macro.  Three things keep that true: the
 product's Makefile recipes define no `YK_*` at all, none of the removed names comes back into the
-sources, and a test variant compiles one host-side unit with its switch and links the product's
-other objects.
+sources, and a test variant compiles one unit with its switch and links the product's other objects:
+a unit without a path kernel, whose switch replaces one constant of its host code or, for the sky
+blocks' lazy-word limit and the query kernels' stack capacity, of one of its own small kernels'
+launches (tests/test_gpu_fallbacks.py runs those two).
 """
 import os
 import re
@@ -25,7 +27,12 @@ CXX_UNITS = ("yk_host", "yk_bvh")
 PRODUCT_TARGETS = ("%.o", "libykgpu.so")
 # target -> (its switch, the one unit that reads it, the Makefile variable of the product's other objects)
 TEST_VARIANTS = {"abl/libykgpu_retry%.so": ("YK_RETRY_CAP_FORCE", "yk_pipeline", "REST_RETRY"),
-                 "abl/libykgpu_stack%.so": ("YK_STACK_CAP_FORCE", "yk_context", "REST_STACK")}
+                 "abl/libykgpu_stack%.so": ("YK_STACK_CAP_FORCE", "yk_context", "REST_STACK"),
+                 "abl/libykgpu_skylazy%.so": ("YK_SKY_LAZY_FORCE", "yk_pipeline", "REST_RETRY"),
+                 "abl/libykgpu_qstack%.so": ("YK_QUERY_STACK_FORCE", "yk_features", "REST_QSTACK")}
+# the instances `make all` builds (the Makefile's TESTVARIANTS)
+TEST_VARIANT_FILES = ["abl/libykgpu_retry64.so", "abl/libykgpu_retry0.so", "abl/libykgpu_stack5.so",
+                      "abl/libykgpu_skylazy8.so", "abl/libykgpu_qstack2.so"]
 
 REMOVED = [
     "YK_NODE_BF",
@@ -152,11 +159,30 @@ def test_test_variants_compile_one_host_unit_and_link_the_products_objects():
                 assert switch not in text, f
             if f not in [u + ".hip" for _, u, _ in TEST_VARIANTS.values()] + ["Makefile"]:
                 assert "_CAP_FORCE" not in text, f
+                assert not re.search(r"YK_\w+_FORCE", text), f
         main = open(os.path.join(CSRC, unit + ".hip")).read()
         assert switch in main
-        assert [w for w in re.findall(r"YK_\w+_CAP_FORCE", main) if w != switch] == [], unit
+        # ... and the unit reads no switch but its own (yk_pipeline.hip has two, each with its variant)
+        own = {s for s, u, _ in TEST_VARIANTS.values() if u == unit}
+        assert [w for w in re.findall(r"YK_\w+_CAP_FORCE", main) if w not in own] == [], unit
+        assert set(re.findall(r"YK_\w+_FORCE", main)) == own, unit
         assert not re.search(r"void\s+yk_render_\w+\s*\(", main)
         assert "#include \"yk_path.hpp\"" not in main
+
+
+def test_make_all_builds_every_test_variant():
+    words = []
+    lines = makefile()
+    k = next(i for i, l in enumerate(lines) if re.match(r"^TESTVARIANTS\s*=", l))
+    while True:  # (the variable's value, continuation lines included)
+        words += lines[k].rstrip("\\").split("=")[-1].split()
+        if not lines[k].endswith("\\"):
+            break
+        k += 1
+    assert words == ["$(LIB)/" + f for f in TEST_VARIANT_FILES]
+    assert [l for l in lines if l.startswith("all:")] == ["all: $(LIB)/libykgpu.so $(LIB)/raytrace $(TESTVARIANTS)"]
+    for f in TEST_VARIANT_FILES:  # every instance is one of the pattern rules
+        assert [t for t in TEST_VARIANTS if re.fullmatch(t.replace("%", r"\d+"), f)], f
 
 
 def test_no_removed_switch_in_the_sources():

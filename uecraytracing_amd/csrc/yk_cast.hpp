@@ -34,6 +34,16 @@ constexpr uint64_t kChunk = 1ull << 22;  // rays per launch (and per staging rou
 // most kStackMax (51 KiB of LDS a block); the top is checked either way, and a lane that overflows
 // takes the scan
 constexpr uint32_t kStackMin = 4, kStackMax = 48;
+// ... of every query kernel of the unit (this one, yk_radiance.hpp, yk_features_sampled.hpp): the
+// kernel argument and the LDS size both come from it.  kYkQueryStackForce: yk_features.hip.
+inline uint32_t query_stack_cap(const DevTree& t) {
+  if (kYkQueryStackForce) return kYkQueryStackForce;
+  return std::max(kStackMin, std::min(3 * t.wide_depth + 1, kStackMax));
+}
+// (the branch-free visit writes up to two entries past the capacity before its check)
+inline size_t query_stack_lds(uint32_t stack_cap, uint32_t threads) {
+  return (size_t)(stack_cap + 3) * threads * sizeof(int32_t);
+}
 constexpr uint32_t kKnownFlags = YK_CAST_ANY_HIT | YK_CAST_LINEAR_SCAN | YK_CAST_COUNT_WORK;
 constexpr uint32_t kNoId = 0xFFFFFFFFu;
 
@@ -319,9 +329,8 @@ hipError_t enqueue(const ykgpu_context* ctx, const void* rays, void* hits, uint3
   a.root = t.root;
   a.node_bytes = t.n_nodes * (uint32_t)sizeof(DevNode);
   a.nspheres = ctx->nspheres;
-  a.stack_cap = std::max(kStackMin, std::min(3 * t.wide_depth + 1, kStackMax));
-  // (the branch-free visit writes up to two entries past the capacity before its check)
-  const size_t lds = (size_t)(a.stack_cap + 3) * kThreads * sizeof(int32_t);
+  a.stack_cap = query_stack_cap(t);
+  const size_t lds = query_stack_lds(a.stack_cap, kThreads);
   hipLaunchKernelGGL(yk_cast, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), lds, st, a);
   return hipGetLastError();
 }

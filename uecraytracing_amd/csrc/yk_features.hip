@@ -269,6 +269,17 @@ int ykgpu_film_features(ykgpu_film* film, uint32_t grid, double* mean_host, doub
 
 }  // extern "C"
 
+// The query kernels' checked stack capacity (ykcast::query_stack_cap, yk_cast.hpp: the cast, the
+// radiance and gather queries, the sampled feature pass).  0: the tree's own.  A test build forces a
+// shallow one (Makefile libykgpu_qstack%.so), so that lanes overflow it and take the ordered scan
+// (tests/test_gpu_fallbacks.py).
+#ifdef YK_QUERY_STACK_FORCE
+constexpr uint32_t kYkQueryStackForce = YK_QUERY_STACK_FORCE;
+static_assert(kYkQueryStackForce >= 1 && kYkQueryStackForce <= 48, "the forced query stack: 1..kStackMax entries");
+#else
+constexpr uint32_t kYkQueryStackForce = 0;
+#endif
+
 // the ray queries (ykgpu_cast_rays ...): the unit's other first-hit query, in a file of its own
 #include "yk_cast.hpp"
 // ... and the radiance queries (ykgpu_radiance_rays ...), whose closest hit is the cast's

@@ -49,8 +49,7 @@ constexpr uint32_t kMaxSamples = 256;
 constexpr uint32_t kWave = 8, kBlockW = 4 * kWave, kBlockH = kWave, kThreads = kBlockW * kBlockH;
 constexpr uint32_t kWalk = 4;  // consecutive samples whose seed walks are interleaved
 constexpr uint32_t kRedoEngines = 64;
-constexpr uint32_t kStackMin = 4, kStackMax = 48;  // yk_cast's
-constexpr uint32_t kLazyMin = 4;                   // (the jitter's words: never checked)
+constexpr uint32_t kLazyMin = 4;  // (the jitter's words: never checked)
 
 static_assert(sizeof(yk_sampled_features_stats) == 32 && offsetof(yk_sampled_features_stats, samples) == 8 &&
                   offsetof(yk_sampled_features_stats, hits) == 16 &&
@@ -455,7 +454,7 @@ int ensure(ykgpu_film* film, uint32_t n, const double** planes, yk_sampled_featu
   a.root = t.root;
   a.node_bytes = t.n_nodes * (uint32_t)sizeof(DevNode);
   a.nspheres = ctx->nspheres;
-  a.stack_cap = std::max(kStackMin, std::min(3 * t.wide_depth + 1, kStackMax));
+  a.stack_cap = ykcast::query_stack_cap(t);
   a.W = p.image_width;
   a.H = p.image_height;
   a.rows = rows;
@@ -477,8 +476,7 @@ int ensure(ykgpu_film* film, uint32_t n, const double** planes, yk_sampled_featu
   if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
   if (e == hipSuccess) {
     const dim3 blocks((wt + kBlockW - 1) / kBlockW, (rows + kBlockH - 1) / kBlockH);
-    // (the branch-free visit writes up to two entries past the capacity before its check)
-    const size_t lds = (size_t)(a.stack_cap + 3) * kThreads * sizeof(int32_t);
+    const size_t lds = ykcast::query_stack_lds(a.stack_cap, kThreads);
     if (x128)
       hipLaunchKernelGGL(yk_film_features_sampled<ykd::X128Lane>, blocks, dim3(kThreads), lds, stream, a);
     else

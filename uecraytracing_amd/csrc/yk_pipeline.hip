@@ -400,9 +400,12 @@ __device__ __forceinline__ void sky_add(const SkyArgs& sa, uint32_t xx, uint32_t
   a[1] = a[1] + ((1.0 - t) * 1.0 + t * 0.7);
   a[2] = a[2] + ((1.0 - t) * 1.0 + t * 1.0);
 }
-// words the lens loop may draw from the lazy cursors (test builds lower it: the full engine then runs)
-#ifndef YK_SKY_LAZY_WORDS
-#define YK_SKY_LAZY_WORDS ykd::kLazyDraws
+// words the lens loop may draw from the lazy cursors (a test build lowers it, Makefile
+// libykgpu_skylazy%.so: the pixels it lists then run yk_sky_redo, tests/test_gpu_fallbacks.py)
+#ifdef YK_SKY_LAZY_FORCE
+constexpr uint32_t kSkyLazyWords = YK_SKY_LAZY_FORCE;
+#else
+constexpr uint32_t kSkyLazyWords = ykd::kLazyDraws;
 #endif
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(YK_DEFER_VGPRS / 2))) void yk_sky_samples(SkyArgs sa) {
   const uint32_t p = blockIdx.x * 256u + threadIdx.x;
@@ -433,7 +436,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(YK_DEFER_VGPRS 
       double px = 0.0, py = 0.0;
       if (sa.lens) {
         for (;;) {  // thin-lens extension: random_in_unit_disk by rejection, x then y
-          if (g.j + 4 > YK_SKY_LAZY_WORDS) {
+          if (g.j + 4 > kSkyLazyWords) {
             // (never seen) the lens loop outran the lazy cursors: the pixel keeps its carried sums
             // and yk_sky_redo runs this launch's samples of it from a whole engine
             sa.engines[1 + atomicAdd(sa.engines, 1u)] = p;

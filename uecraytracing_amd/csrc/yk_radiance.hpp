@@ -449,9 +449,8 @@ struct Plan {
 
 int make_plan(ykgpu_context* ctx, const yk_radiance_params* p, Plan& pl) {
   const DevTree& t = ctx->t64;
-  pl.stack_cap = std::max(ykcast::kStackMin, std::min(3 * t.wide_depth + 1, ykcast::kStackMax));
-  // (the branch-free visit writes up to two entries past the capacity before its check)
-  pl.lds = (size_t)(pl.stack_cap + 3) * kThreads * sizeof(int32_t);
+  pl.stack_cap = ykcast::query_stack_cap(t);
+  pl.lds = ykcast::query_stack_lds(pl.stack_cap, kThreads);
   int occ = 0;
   YK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)path_kernel(p->rng), (int)kThreads, pl.lds));
   if (occ < 1) return fail(YK_ERR_DEVICE, "radiance: the path kernel does not fit a compute unit");
