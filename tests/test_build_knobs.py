@@ -185,6 +185,27 @@ def test_make_all_builds_every_test_variant():
         assert [t for t in TEST_VARIANTS if re.fullmatch(t.replace("%", r"\d+"), f)], f
 
 
+def test_the_query_kernels_share_one_closest_hit():
+    """The checked-stack FP64 visit of DESIGN.md §4 is written once, in yk_query.hpp: no other header
+    of the unit yk_features.hip stores the stack's sentinel, defines a slot test, states the tie
+    rule or writes the ordered scan's loop (the unit's own file keeps the pinhole pass's staged scan)."""
+    main = open(os.path.join(CSRC, "yk_features.hip")).read()
+    # the unit's query headers: what it includes at its end, after the stack switch
+    headers = re.findall(r'#include "(yk_\w+\.hpp)"', main[main.index("kYkQueryStackForce = 0;"):])
+    assert headers == ["yk_query.hpp", "yk_cast.hpp", "yk_radiance.hpp", "yk_gather.hpp", "yk_features_sampled.hpp"]
+    once = {"the sentinel's store": r"=\s*ykbvh::kEmptyLeaf\s*;",
+            "the slot test": r"#define\s+YK_\w*SLOT\b",
+            "the tie rule": re.escape("r == best && (int)id > best_id"),
+            "the ordered loop": r"root < \w[\w.]* \|\| \w+ < root"}
+    for what, pattern in once.items():
+        found = {f: len(re.findall(pattern, open(os.path.join(CSRC, f)).read())) for f in headers}
+        want = 2 if what == "the ordered loop" else 1  # (the loop tests each of a sphere's two roots)
+        assert found == {f: (want if f == "yk_query.hpp" else 0) for f in headers}, (what, found)
+    # ... and the unit's own file has the pinhole pass's loop alone
+    assert len(re.findall(once["the ordered loop"], main)) == 2
+    assert not [w for w in list(once)[:3] if re.search(once[w], main)]
+
+
 def test_no_removed_switch_in_the_sources():
     found = []
     for dirpath, _, files in os.walk(CSRC):

@@ -17,7 +17,8 @@ per pixel it times, in one process on one device after a warm-up of every shape:
 The variants alternate round by round, so a drift of the device shows in all of them; each figure is
 the median of --runs rounds, with the minimum and maximum beside it.
 
-usage: python tools/features_sampled_bench.py [--runs 7] [--width 1920] [--out profiles/TAG_features_sampled.json]
+usage: python tools/features_sampled_bench.py [--runs 7] [--width 1920] [--commit ID]
+       [--out profiles/TAG_features_sampled.json]
 """
 import argparse
 import ctypes
@@ -46,6 +47,7 @@ def main():
     ap.add_argument("--spp", type=int, default=64)
     ap.add_argument("--depth", type=int, default=50)
     ap.add_argument("--scene", default="final")
+    ap.add_argument("--commit", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.runs < 5:
@@ -105,7 +107,7 @@ def main():
         film.close()
     med = {k: statistics.median(v) for k, v in t.items()}
     out = {
-        "tool": "tools/features_sampled_bench.py", "scene": a.scene, "width": a.width, "height": p.image_height,
+        "tool": "tools/features_sampled_bench.py", "commit": a.commit, "scene": a.scene, "width": a.width, "height": p.image_height,
         "film_target_spp": a.spp, "depth": a.depth, "spheres": len(arr), "lens_radius": cam.lens_radius,
         "colour": dp.as_dict(), "features": fp.as_dict(), "n_default": n_default, "pass_counts": counts,
         "timing": "chunk and *_wall: host wall clock around synchronous calls; sampled_*, pinhole_* and *_device: between "

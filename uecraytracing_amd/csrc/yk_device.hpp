@@ -386,6 +386,13 @@ __device__ __forceinline__ void x128_start(X128Lane& g, uint32_t seed) {
   g.w = 88675123u ^ seed;
   g.n = 0;
 }
+// An engine that lives on the lazy cursors alone (a start's few draws: the sampled feature pass, the
+// gather's scatter), from its seed and, for mt19937, the walked x_397: no scratch behind it.
+__device__ __forceinline__ void engine_start(MtLane& g, uint32_t seed, uint32_t x397) {
+  g.state = nullptr;
+  mt_start_from(g, seed, x397);
+}
+__device__ __forceinline__ void engine_start(X128Lane& g, uint32_t seed, uint32_t) { x128_start(g, seed); }
 __device__ __forceinline__ uint32_t x128_next(X128Lane& g) {  // operator(), :34-40
   const uint32_t t = g.x ^ (g.x << 11);
   g.x = g.y;

@@ -269,7 +269,7 @@ int ykgpu_film_features(ykgpu_film* film, uint32_t grid, double* mean_host, doub
 
 }  // extern "C"
 
-// The query kernels' checked stack capacity (ykcast::query_stack_cap, yk_cast.hpp: the cast, the
+// The query kernels' checked stack capacity (ykquery::query_stack_cap, yk_query.hpp: the cast, the
 // radiance and gather queries, the sampled feature pass).  0: the tree's own.  A test build forces a
 // shallow one (Makefile libykgpu_qstack%.so), so that lanes overflow it and take the ordered scan
 // (tests/test_gpu_fallbacks.py).
@@ -280,11 +280,13 @@ static_assert(kYkQueryStackForce >= 1 && kYkQueryStackForce <= 48, "the forced q
 constexpr uint32_t kYkQueryStackForce = 0;
 #endif
 
+// what the query kernels below share: the closest hit of the context's FP64 tree
+#include "yk_query.hpp"
 // the ray queries (ykgpu_cast_rays ...): the unit's other first-hit query, in a file of its own
 #include "yk_cast.hpp"
-// ... and the radiance queries (ykgpu_radiance_rays ...), whose closest hit is the cast's
+// ... and the radiance queries (ykgpu_radiance_rays ...), whose closest hit is the same
 #include "yk_radiance.hpp"
 // ... and the gather queries (ykgpu_gather_points ...), whose rays are radiance queries' rays
 #include "yk_gather.hpp"
-// ... and the sampled feature pass (ykgpu_film_features_sampled ...), whose closest hit is a copy of it
+// ... and the sampled feature pass (ykgpu_film_features_sampled ...), whose closest hit is the same
 #include "yk_features_sampled.hpp"

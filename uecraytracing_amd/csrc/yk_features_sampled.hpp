@@ -12,33 +12,23 @@
 //                                  samples one after the other (the fold order is the definition's).
 //                                  The start as yk_sky_samples makes it (yk_pipeline.hip): the seed
 //                                  walk of four consecutive samples interleaved, the lazy cursors,
-//                                  the lens rejection loop.  The closest hit as yk_cast finds it — a
-//                                  COPY of its traversal, so that yk_cast's instructions stay what
-//                                  they were: a checked per-lane LDS stack, the float slab test,
-//                                  exact leaves, ties to the later index, the ordered scan on a guard,
-//                                  a stack overflow or YK_FLAG_LINEAR_SCAN.
+//                                  the lens rejection loop.  The closest hit is the ray queries'
+//                                  (ykquery::closest_hit, yk_query.hpp) with t_max = +inf, the
+//                                  ordered scan under YK_FLAG_LINEAR_SCAN.
 //   yk_film_features_redo          the pixels whose lens loop outran the lazy cursors' words (listed
 //                                  by the first kernel; ~55 rejections in a row, or a test's lowered
 //                                  limit): all n samples again from a whole engine (ykd::MtFull), the
-//                                  hit by the ordered scan.  One block of kRedoEngines threads.
+//                                  hit by the ordered scan (ykquery::scan_hit).  One block of
+//                                  kRedoEngines threads.
 #ifndef YK_FEATURES_SAMPLED_HPP
 #define YK_FEATURES_SAMPLED_HPP
 
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <atomic>
-#include <cmath>
-#include <cstdint>
 #include <string>
 #include <type_traits>
-#include <vector>
 
-#include "../../include/ykgpu.h"
-#include "yk_cast.hpp"
-#include "yk_device.hpp"
 #include "yk_film_internal.hpp"
-#include "yk_host_internal.hpp"
+#include "yk_query.hpp"
 
 namespace ykfs {
 using namespace ykhost;
@@ -58,21 +48,15 @@ static_assert(sizeof(yk_sampled_features_stats) == 32 && offsetof(yk_sampled_fea
 
 struct SfArgs {
   yk_camera cam;
-  const char* nodes;          // DevNode; child links are byte offsets
-  const SphereGeo* leaf_geo;  // leaf order
-  const uint32_t* leaf_ids;   // leaf slot -> tuple index
-  const SphereGeo* geo;       // tuple order
-  const SphereMat* mat;
+  ykquery::QueryTree q;
   double* out;               // kYkFeatPlanes planes of npix doubles
   uint32_t* redo;            // [0]: pixels listed, [1, 1 + npix): the list, then kRedoEngines engines
   unsigned long long* hits;  // samples that hit a sphere
-  double t_min, extent, origin_bound;
+  double t_min;
   uint64_t seed_key;
   uint32_t seed0, seed_mode, spp, n;
   uint32_t lazy_words;  // mt19937 words a start may draw from the lazy cursors (4..227)
   uint32_t scan_only;   // YK_FLAG_LINEAR_SCAN
-  int32_t root;
-  uint32_t node_bytes, nspheres, stack_cap;
   uint32_t W, H, rows, wt, npix;
   uint32_t row_begin, row_stride, row_band, col_begin, col_stride, col_band;
 };
@@ -103,136 +87,13 @@ __device__ __forceinline__ void start_ray(const SfArgs& a, uint32_t x, uint32_t 
   }
 }
 
-// hittable_list::hit_impl over sphere::hit_impl, the literal loop in tuple order, t_max = +inf
-__device__ __forceinline__ int scan_hit(const SfArgs& a, v3 o, v3 d, double aa, double& t) {
-  double best = INFINITY;
-  int best_id = -1;
-  for (uint32_t k = 0; k < a.nspheres; ++k) {
-    const SphereGeo sg = a.geo[k];
-    const v3 oc = {o.x - sg.cx, o.y - sg.cy, o.z - sg.cz};
-    const double hb = ykd::dot(oc, d);
-    const double cc = ykd::len2(oc) - sg.rr;
-    const double disc = hb * hb - aa * cc;
-    if (disc < 0) continue;
-    const double sq = ykd::nsqrt(disc);
-    double root = (-hb - sq) / aa;
-    if (root < a.t_min || best < root) {
-      root = (-hb + sq) / aa;
-      if (root < a.t_min || best < root) continue;
-    }
-    best = root;
-    best_id = (int)k;
-  }
-  t = best;
-  return best_id;
-}
-
-// The ray queries' closest hit of (o, d) with t_min = a.t_min and t_max = +inf: the sphere's tuple
-// index and t, or -1.  yk_cast's traversal (yk_cast.hpp), statement for statement; stk is the lane's
-// column of the block's stack, entries kThreads words apart.
-__device__ __forceinline__ int closest_hit(const SfArgs& a, int32_t* const stk, v3 o, v3 d, double& t) {
-  const double tmin = a.t_min;
-  if (!ykcast::in_domain(o, d, tmin, INFINITY, a.extent)) return -1;  // (a miss, and no arithmetic)
-  // the guards that send a ray to the ordered scan (yk_cast)
-  const float dxf = (float)d.x, dyf = (float)d.y, dzf = (float)d.z;
-  const float dmin = fminf(fminf(fabsf(dxf), fabsf(dyf)), fabsf(dzf));
-  const float dmax = fmaxf(fmaxf(fabsf(dxf), fabsf(dyf)), fabsf(dzf));
-  const double mo = fmax(fabs(o.x), fmax(fabs(o.y), fabs(o.z)));
-  bool scan = a.scan_only || a.origin_bound < 0 || !(mo <= a.origin_bound) || !(dmin > 1e-30f && dmax < 1e30f) ||
-              !(dmax * 0x1p-90f <= (float)a.origin_bound);
-  const double aa = ykd::len2(d);
-  double best = INFINITY;
-  int best_id = -1;
-  if (!scan) {
-    const float ix = 1.0f / dxf, iy = 1.0f / dyf, iz = 1.0f / dzf;
-    constexpr float kFar = 1.0f + 0x1p-17f;
-    const float ixs = ix * kFar, iys = iy * kFar, izs = iz * kFar;
-    const float oxf = (float)o.x, oyf = (float)o.y, ozf = (float)o.z;
-    const float nox = -(oxf * ix), noy = -(oyf * iy), noz = -(ozf * iz);
-    const float fox = -(oxf * ixs), foy = -(oyf * iys), foz = -(ozf * izs);
-    const float tmin_lo = ykcast::f32_down(tmin) * (1.0f - 0x1p-17f);
-    const uint32_t qx = ix < 0.0f ? 16u : 0u, qy = 48u + (iy < 0.0f ? 16u : 0u), qz = 96u + (iz < 0.0f ? 16u : 0u);
-    stk[0] = ykbvh::kEmptyLeaf;  // the sentinel: the traversal ends when it has been popped
-    uint32_t sp = 1;
-    int32_t node = a.root;
-    float ustar = ykcast::f32_up(best) * (1.0f + 0x1p-18f);
-    for (;;) {
-      while (node >= 0) {
-        if ((uint32_t)node + (uint32_t)sizeof(DevNode) > a.node_bytes) {  // (never: a link outside the tree)
-          scan = true;
-          break;
-        }
-        const char* w = a.nodes + node;
-        const float4 nx = *(const float4*)(w + qx), fx = *(const float4*)(w + qx + 16);
-        const float4 ny = *(const float4*)(w + qy), fy = *(const float4*)(w + qy + 16);
-        const float4 nz = *(const float4*)(w + qz), fz = *(const float4*)(w + qz + 16);
-        const int4 ch = *(const int4*)(w + 144);
-        const int32_t popped = stk[(sp - 1) * kThreads];
-#define YK_FS_SLOT(c)                                                                                     \
-  (fmaxf(fmaxf(fmaxf(__builtin_fmaf(nx.c, ix, nox), __builtin_fmaf(ny.c, iy, noy)), __builtin_fmaf(nz.c, iz, noz)), \
-         tmin_lo) <=                                                                                      \
-   fminf(fminf(fminf(__builtin_fmaf(fx.c, ixs, fox), __builtin_fmaf(fy.c, iys, foy)), __builtin_fmaf(fz.c, izs, foz)), \
-         ustar))
-        const bool h0 = YK_FS_SLOT(x), h1 = YK_FS_SLOT(y), h2 = YK_FS_SLOT(z), h3 = YK_FS_SLOT(w);
-#undef YK_FS_SLOT
-        node = h3 ? ch.w : (h2 ? ch.z : (h1 ? ch.y : (h0 ? ch.x : popped)));
-        // (written unconditionally at the top: up to two entries past the capacity, which the stack has)
-        stk[sp * kThreads] = ch.x;
-        sp += (h0 && (h1 || h2 || h3)) ? 1u : 0u;
-        stk[sp * kThreads] = ch.y;
-        sp += (h1 && (h2 || h3)) ? 1u : 0u;
-        stk[sp * kThreads] = ch.z;
-        sp += (h2 && h3) ? 1u : 0u;
-        sp -= (h0 || h1 || h2 || h3) ? 0u : 1u;
-        if (sp > a.stack_cap) {  // stack overflow: the ordered scan decides
-          scan = true;
-          break;
-        }
-      }
-      if (scan) break;
-      const uint32_t v = ~(uint32_t)node, first = v >> 4, cnt = v & 15u;
-      for (uint32_t k = 0; k < cnt; ++k) {
-        const uint32_t slot = first + k;
-        if (slot >= a.nspheres) break;  // (never: a leaf outside the table)
-        const SphereGeo sg = a.leaf_geo[slot];
-        const uint32_t id = a.leaf_ids[slot];
-        const v3 oc = {o.x - sg.cx, o.y - sg.cy, o.z - sg.cz};
-        const double hb = ykd::dot(oc, d);
-        const double cc = ykd::len2(oc) - sg.rr;
-        const double disc = hb * hb - aa * cc;
-        if (disc < 0) continue;
-        const double sq = ykd::nsqrt(disc);
-        double r = (-hb - sq) / aa;
-        if (r < tmin) r = (-hb + sq) / aa;
-        // the minimum root wins, an exact tie goes to the later tuple index
-        if (r >= tmin && (r < best || (r == best && (int)id > best_id))) {
-          best = r;
-          best_id = (int)id;
-          ustar = ykcast::f32_up(best) * (1.0f + 0x1p-18f);
-        }
-      }
-      if (sp == 0) break;  // (the sentinel was this leaf)
-      --sp;
-      node = stk[sp * kThreads];
-    }
-  }
-  if (scan) best_id = scan_hit(a, o, d, aa, best);
-  t = best;
-  return best_id;
-}
-
 // the channels of a sample from its hit (the pinhole pass's rule), folded into s and q
 __device__ __forceinline__ void fold_sample(const SfArgs& a, v3 o, v3 d, int hid, double t, double (&s)[kYkFeatChannels],
                                             double (&q)[kYkFeatChannels]) {
   double f[kYkFeatChannels] = {1.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0};
   if (hid >= 0) {
-    const SphereGeo sg = a.geo[hid];
-    const SphereMat& m = a.mat[hid];
-    // hit record (sphere.hpp:41-45, hittable.hpp:23-27)
-    const v3 p = ykd::add(o, ykd::mul(d, t));
-    const v3 outward = ykd::divs(ykd::sub(p, v3{sg.cx, sg.cy, sg.cz}), m.radius);
-    const bool front = ykd::dot(d, outward) < 0;
-    const v3 nrm = front ? outward : ykd::neg(outward);
+    const SphereMat& m = a.q.mat[hid];
+    const v3 nrm = ykquery::hit_record(o, d, t, a.q.geo[hid], m.radius).nrm;
     if (m.kind != YK_MATERIAL_DIELECTRIC) {
       f[0] = m.ar;
       f[1] = m.ag;
@@ -268,12 +129,6 @@ __device__ __forceinline__ void store_planes(const SfArgs& a, size_t at, const d
   a.out[(size_t)16 * a.npix + at] = U[6];
 }
 
-// a start's engine from its seed and, for mt19937, the walked x_397
-__device__ __forceinline__ void engine_start(ykd::MtLane& g, uint32_t seed, uint32_t x397) {
-  g.state = nullptr;  // (the lazy cursors only)
-  ykd::mt_start_from(g, seed, x397);
-}
-__device__ __forceinline__ void engine_start(ykd::X128Lane& g, uint32_t seed, uint32_t) { ykd::x128_start(g, seed); }
 // whether the lens loop's next try (four words) stays inside the lazy cursors' words
 __device__ __forceinline__ bool lens_try_ok(const ykd::MtLane& g, uint32_t lazy_words) { return g.j + 4 <= lazy_words; }
 __device__ __forceinline__ bool lens_try_ok(const ykd::X128Lane&, uint32_t) { return true; }
@@ -309,7 +164,7 @@ __global__ __launch_bounds__(kThreads) void yk_film_features_sampled(SfArgs a) {
         const uint32_t sj = j == 0 ? seed[0] : j == 1 ? seed[1] : j == 2 ? seed[2] : seed[3];
         const uint32_t xj = j == 0 ? x397[0] : j == 1 ? x397[1] : j == 2 ? x397[2] : x397[3];
         Gen g;
-        engine_start(g, sj, xj);
+        ykd::engine_start(g, sj, xj);
         const double uc = ykd::canonical<true>(g);  // source.cpp:162
         const double vc = ykd::canonical<true>(g);  // source.cpp:163
         double lx = 0.0, ly = 0.0;
@@ -327,10 +182,11 @@ __global__ __launch_bounds__(kThreads) void yk_film_features_sampled(SfArgs a) {
         }
         v3 o, d;
         start_ray(a, x, y, uc, vc, lens, lx, ly, o, d);
-        double t = 0.0;
-        const int hid = closest_hit(a, fs_stack + tid, o, d, t);
-        nh += hid >= 0 ? 1u : 0u;
-        fold_sample(a, o, d, hid, t, s, q);
+        ykquery::Hit h = {0.0, -1, false, 0, 0};  // (outside the domain: a miss, and no arithmetic)
+        if (ykquery::in_domain(o, d, a.t_min, INFINITY, a.q.extent))
+          h = ykquery::closest_hit<kThreads>(a.q, fs_stack + tid, true, o, d, a.t_min, INFINITY, a.scan_only != 0, false);
+        nh += h.id >= 0 ? 1u : 0u;
+        fold_sample(a, o, d, h.id, h.t, s, q);
       }
     }
     if (listed) {
@@ -342,7 +198,7 @@ __global__ __launch_bounds__(kThreads) void yk_film_features_sampled(SfArgs a) {
     }
   }
   // one atomic per wave (every lane of the block is here)
-  const uint32_t wh = ykcast::wave_sum(nh);
+  const uint32_t wh = ykquery::wave_sum(nh);
   if (lane == 0 && wh) atomicAdd(a.hits, (unsigned long long)wh);
 }
 
@@ -373,15 +229,15 @@ __global__ __launch_bounds__(kRedoEngines) void yk_film_features_redo(SfArgs a) 
       }
       v3 o, d;
       start_ray(a, x, y, uc, vc, lens, lx, ly, o, d);
-      double t = 0.0;
-      int hid = -1;
-      if (ykcast::in_domain(o, d, a.t_min, INFINITY, a.extent)) hid = scan_hit(a, o, d, ykd::len2(d), t);
-      nh += hid >= 0 ? 1u : 0u;
-      fold_sample(a, o, d, hid, t, s, q);
+      ykquery::Hit h = {0.0, -1, false, 0, 0};
+      if (ykquery::in_domain(o, d, a.t_min, INFINITY, a.q.extent))
+        ykquery::scan_hit(a.q, o, d, ykd::len2(d), a.t_min, INFINITY, false, h);
+      nh += h.id >= 0 ? 1u : 0u;
+      fold_sample(a, o, d, h.id, h.t, s, q);
     }
     store_planes(a, at, s, q);
   }
-  const uint32_t wh = ykcast::wave_sum(nh);
+  const uint32_t wh = ykquery::wave_sum(nh);
   if (threadIdx.x == 0 && wh) atomicAdd(a.hits, (unsigned long long)wh);
 }
 
@@ -429,20 +285,13 @@ int ensure(ykgpu_film* film, uint32_t n, const double** planes, yk_sampled_featu
   const size_t redo_words = 1 + npix + (size_t)kRedoEngines * ykd::kMtN;
   char* d_work = nullptr;
   YK_HIP(hipMalloc(&d_work, 16 + redo_words * sizeof(uint32_t)));
-  const DevTree& t = ctx->t64;
   SfArgs a{};
   a.cam = ctx->cam;
-  a.nodes = (const char*)t.nodes;
-  a.leaf_geo = (const SphereGeo*)t.leaf_geo;
-  a.leaf_ids = t.leaf_ids;
-  a.geo = ctx->d_geo;
-  a.mat = ctx->d_mat;
+  a.q = ykquery::query_tree(ctx);
   a.out = (double*)film->d_features;
   a.hits = (unsigned long long*)d_work;
   a.redo = (uint32_t*)(d_work + 16);
   a.t_min = p.t_min;
-  a.extent = ctx->cast_extent;
-  a.origin_bound = t.origin_bound;
   a.seed_key = p.seed_key;
   a.seed0 = p.seed0;
   a.seed_mode = p.seed_mode == YK_SEED_RANDOM_DEVICE ? 1u : 0u;
@@ -451,10 +300,6 @@ int ensure(ykgpu_film* film, uint32_t n, const double** planes, yk_sampled_featu
   const uint32_t lw = g_lazy_words.load();
   a.lazy_words = lw ? std::max(kLazyMin, std::min(lw, ykd::kLazyDraws)) : ykd::kLazyDraws;
   a.scan_only = (p.flags & YK_FLAG_LINEAR_SCAN) ? 1u : 0u;
-  a.root = t.root;
-  a.node_bytes = t.n_nodes * (uint32_t)sizeof(DevNode);
-  a.nspheres = ctx->nspheres;
-  a.stack_cap = ykcast::query_stack_cap(t);
   a.W = p.image_width;
   a.H = p.image_height;
   a.rows = rows;
@@ -476,7 +321,7 @@ int ensure(ykgpu_film* film, uint32_t n, const double** planes, yk_sampled_featu
   if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
   if (e == hipSuccess) {
     const dim3 blocks((wt + kBlockW - 1) / kBlockW, (rows + kBlockH - 1) / kBlockH);
-    const size_t lds = ykcast::query_stack_lds(a.stack_cap, kThreads);
+    const size_t lds = ykquery::query_stack_lds(a.q.stack_cap, kThreads);
     if (x128)
       hipLaunchKernelGGL(yk_film_features_sampled<ykd::X128Lane>, blocks, dim3(kThreads), lds, stream, a);
     else

@@ -57,12 +57,6 @@ struct FoldArgs {
   uint32_t cnt, n_samples;
 };
 
-__device__ __forceinline__ void engine_start(ykd::MtLane& g, uint32_t seed, uint32_t x397) {
-  g.state = nullptr;  // (never read: a slot draws at most kMaxSkip + 6 = 227 lazy words)
-  ykd::mt_start_from(g, seed, x397);
-}
-__device__ __forceinline__ void engine_start(ykd::X128Lane& g, uint32_t seed, uint32_t) { ykd::x128_start(g, seed); }
-
 template <class G>
 __global__ __launch_bounds__(kThreads) void yk_gather_starts(StartArgs a) {
   constexpr bool kMt = __is_same(G, ykd::MtLane);
@@ -92,8 +86,8 @@ __global__ __launch_bounds__(kThreads) void yk_gather_starts(StartArgs a) {
     // a point past the skip limit or with a zero normal does no arithmetic: the zero direction
     // puts its rays outside the path kernel's domain
     if (skip <= kMaxSkip && !(n.x == 0.0 && n.y == 0.0 && n.z == 0.0)) {
-      G g;
-      engine_start(g, seed[k], x[k]);
+      G g;  // (its scratch is never read: a slot draws at most kMaxSkip + 6 = 227 lazy words)
+      ykd::engine_start(g, seed[k], x[k]);
       for (uint32_t w = 0; w < skip; ++w) (void)ykd::rng_next<true>(g);  // discard(skip), with the lazy draw
       // lambertian::scatter (material.hpp:50-59), random_unit_vector (:33-36): vec3::random's x, y, z
       v3 ru;
@@ -221,16 +215,9 @@ int ykgpu_gather_points(ykgpu_context* ctx, const yk_gather_params* params, cons
   if (int rc = ykgather::prepare(ctx, params, &rp, n, pl)) return rc;
   const uint64_t cp = ykgather::chunk_points(params->n_samples);
   const size_t need = (size_t)std::min<uint64_t>(n, cp);
-  if (need > ctx->gat_cap) {
-    YK_HIP(hipEventSynchronize(ctx->rad_ev));
-    (void)hipFree(ctx->d_gat_points);
-    (void)hipFree(ctx->d_gat_out);
-    ctx->d_gat_points = ctx->d_gat_out = nullptr;
-    ctx->gat_cap = 0;
-    YK_HIP(hipMalloc(&ctx->d_gat_points, need * sizeof(yk_gather_point)));
-    YK_HIP(hipMalloc(&ctx->d_gat_out, need * sizeof(yk_gather)));
-    ctx->gat_cap = need;
-  }
+  if (int rc = ykquery::ensure_pair(ctx->d_gat_points, ctx->d_gat_out, ctx->gat_cap, need, sizeof(yk_gather_point),
+                                    sizeof(yk_gather), ctx->rad_ev))
+    return rc;
   const hipStream_t st = ctx->stream;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   hipError_t e = hipStreamWaitEvent(st, ctx->rad_ev, 0);  // (after the context's queries on other streams)

@@ -14,15 +14,18 @@
 //                       for all lanes; a lane whose path ended unwinds its attenuations back to
 //                       front, writes its 64-byte record and takes the next ray from the wave's
 //                       reserve (one atomic per wave and claim, small claims near the end).
-// The closest hit restates yk_cast's visit (the cast kernel itself stays as it is): the context's
-// FP64 tree with a checked per-lane stack in LDS and the cast's guards, the ordered scan otherwise.
+// The closest hit and the hit record are the ray queries' (ykquery::closest_hit and hit_record,
+// yk_query.hpp), with t_max = +inf.
 // A path's record depends on its ray alone: the engine is the path's own, a lane's scratch is
 // rewritten before it is read (mt_slow seeds all 624 words at word 227), and the unwind multiplies
 // in the path's own order — so neither the batch nor the lane a ray lands on can change a byte.
 #ifndef YK_RADIANCE_HPP
 #define YK_RADIANCE_HPP
 
-#include "yk_cast.hpp"
+#include <chrono>
+#include <string>
+
+#include "yk_query.hpp"
 
 namespace ykrad {
 using namespace ykhost;
@@ -57,18 +60,12 @@ struct RadArgs {
   uint32_t flags;        // YK_RADIANCE_*
   uint32_t max_depth, claim_tail;
   double t_min;
-  const char* nodes;  // DevNode; child links are byte offsets
-  const SphereGeo* leaf_geo;
-  const uint32_t* leaf_ids;
-  const SphereGeo* geo;  // tuple order
-  const SphereMat* mat;
   uint32_t* claim;                // the launch's ray counter
   uint32_t* mt_scratch;           // 624 words per resident lane
   uint16_t* id_scratch;           // id_stride ids per resident lane
   unsigned long long* counters;   // kRadStripes x kRadCounters words, or null (asynchronous queries)
-  double extent, origin_bound;    // as CastArgs
-  int32_t root;
-  uint32_t node_bytes, nspheres, stack_cap, id_stride;
+  ykquery::QueryTree q;
+  uint32_t id_stride;
 };
 
 __global__ __launch_bounds__(kThreads) void yk_radiance_starts(const uint32_t* rays, uint32_t n, uint32_t* x397) {
@@ -98,119 +95,6 @@ __device__ __forceinline__ void path_start(ykd::MtLane& g, const RadArgs& a, uin
 }
 __device__ __forceinline__ void path_start(ykd::X128Lane& g, const RadArgs&, uint32_t, uint32_t seed) {
   ykd::x128_start(g, seed);
-}
-
-// world.hit(r, t_min, +inf) as yk_cast computes it (yk_cast.hpp; include/ykgpu.h "ray queries"): the
-// tree's visit with its guards, or the ordered scan.  The ray is in the domain.  stk: the lane's
-// stack in LDS, entries kThreads words apart.  best_id < 0: a miss.
-__device__ __forceinline__ void closest_hit(const RadArgs& a, v3 o, v3 d, int32_t* const stk, double& best,
-                                            int& best_id, bool& scanned) {
-  const double tmin = a.t_min;
-  const float dxf = (float)d.x, dyf = (float)d.y, dzf = (float)d.z;
-  const float dmin = fminf(fminf(fabsf(dxf), fabsf(dyf)), fabsf(dzf));
-  const float dmax = fmaxf(fmaxf(fabsf(dxf), fabsf(dyf)), fabsf(dzf));
-  const double mo = fmax(fabs(o.x), fmax(fabs(o.y), fabs(o.z)));
-  bool scan = (a.flags & YK_RADIANCE_LINEAR_SCAN) || a.origin_bound < 0 || !(mo <= a.origin_bound) ||
-              !(dmin > 1e-30f && dmax < 1e30f) || !(dmax * 0x1p-90f <= (float)a.origin_bound);
-  const double aa = ykd::len2(d);
-  best = INFINITY;
-  best_id = -1;
-  if (!scan) {
-    const float ix = 1.0f / dxf, iy = 1.0f / dyf, iz = 1.0f / dzf;
-    constexpr float kFar = 1.0f + 0x1p-17f;
-    const float ixs = ix * kFar, iys = iy * kFar, izs = iz * kFar;
-    const float oxf = (float)o.x, oyf = (float)o.y, ozf = (float)o.z;
-    const float nox = -(oxf * ix), noy = -(oyf * iy), noz = -(ozf * iz);
-    const float fox = -(oxf * ixs), foy = -(oyf * iys), foz = -(ozf * izs);
-    const float tmin_lo = ykcast::f32_down(tmin) * (1.0f - 0x1p-17f);
-    const uint32_t qx = ix < 0.0f ? 16u : 0u, qy = 48u + (iy < 0.0f ? 16u : 0u), qz = 96u + (iz < 0.0f ? 16u : 0u);
-    stk[0] = ykbvh::kEmptyLeaf;  // the sentinel below the stack: a pop needs no test of its own
-    uint32_t sp = 1;
-    int32_t node = a.root;
-    float ustar = ykcast::f32_up(best) * (1.0f + 0x1p-18f);
-    for (;;) {
-      while (node >= 0) {
-        if ((uint32_t)node + (uint32_t)sizeof(DevNode) > a.node_bytes) {  // (never: a link outside the tree)
-          scan = true;
-          break;
-        }
-        const char* w = a.nodes + node;
-        const float4 nx = *(const float4*)(w + qx), fx = *(const float4*)(w + qx + 16);
-        const float4 ny = *(const float4*)(w + qy), fy = *(const float4*)(w + qy + 16);
-        const float4 nz = *(const float4*)(w + qz), fz = *(const float4*)(w + qz + 16);
-        const int4 ch = *(const int4*)(w + 144);
-        const int32_t popped = stk[(sp - 1) * kThreads];
-#define YK_RAD_SLOT(c)                                                                                    \
-  (fmaxf(fmaxf(fmaxf(__builtin_fmaf(nx.c, ix, nox), __builtin_fmaf(ny.c, iy, noy)), __builtin_fmaf(nz.c, iz, noz)), \
-         tmin_lo) <=                                                                                      \
-   fminf(fminf(fminf(__builtin_fmaf(fx.c, ixs, fox), __builtin_fmaf(fy.c, iys, foy)), __builtin_fmaf(fz.c, izs, foz)), \
-         ustar))
-        const bool h0 = YK_RAD_SLOT(x), h1 = YK_RAD_SLOT(y), h2 = YK_RAD_SLOT(z), h3 = YK_RAD_SLOT(w);
-#undef YK_RAD_SLOT
-        node = h3 ? ch.w : (h2 ? ch.z : (h1 ? ch.y : (h0 ? ch.x : popped)));
-        stk[sp * kThreads] = ch.x;
-        sp += (h0 && (h1 || h2 || h3)) ? 1u : 0u;
-        stk[sp * kThreads] = ch.y;
-        sp += (h1 && (h2 || h3)) ? 1u : 0u;
-        stk[sp * kThreads] = ch.z;
-        sp += (h2 && h3) ? 1u : 0u;
-        sp -= (h0 || h1 || h2 || h3) ? 0u : 1u;
-        if (sp > a.stack_cap) {  // stack overflow: the ordered scan decides
-          scan = true;
-          break;
-        }
-      }
-      if (scan) break;
-      {
-        const uint32_t v = ~(uint32_t)node, first = v >> 4, cnt = v & 15u;
-        for (uint32_t k = 0; k < cnt; ++k) {
-          const uint32_t slot = first + k;
-          if (slot >= a.nspheres) break;  // (never: a leaf outside the table)
-          const SphereGeo sg = a.leaf_geo[slot];
-          const uint32_t id = a.leaf_ids[slot];
-          const v3 oc = {o.x - sg.cx, o.y - sg.cy, o.z - sg.cz};
-          const double hb = ykd::dot(oc, d);
-          const double cc = ykd::len2(oc) - sg.rr;
-          const double disc = hb * hb - aa * cc;
-          if (disc < 0) continue;
-          const double sq = ykd::nsqrt(disc);
-          double r = (-hb - sq) / aa;
-          if (r < tmin) r = (-hb + sq) / aa;
-          // the minimum root wins, an exact tie goes to the later tuple index (yk_cast)
-          if (r >= tmin && (r < best || (r == best && (int)id > best_id))) {
-            best = r;
-            best_id = (int)id;
-            ustar = ykcast::f32_up(best) * (1.0f + 0x1p-18f);
-          }
-        }
-      }
-      if (sp == 0) break;  // (the sentinel was this leaf)
-      --sp;
-      node = stk[sp * kThreads];
-    }
-  }
-  if (scan) {
-    // hittable_list::hit_impl over sphere::hit_impl, the literal loop in tuple order
-    best = INFINITY;
-    best_id = -1;
-    for (uint32_t k = 0; k < a.nspheres; ++k) {
-      const SphereGeo sg = a.geo[k];
-      const v3 oc = {o.x - sg.cx, o.y - sg.cy, o.z - sg.cz};
-      const double hb = ykd::dot(oc, d);
-      const double cc = ykd::len2(oc) - sg.rr;
-      const double disc = hb * hb - aa * cc;
-      if (disc < 0) continue;
-      const double sq = ykd::nsqrt(disc);
-      double root = (-hb - sq) / aa;
-      if (root < tmin || best < root) {
-        root = (-hb + sq) / aa;
-        if (root < tmin || best < root) continue;
-      }
-      best = root;
-      best_id = (int)k;
-    }
-  }
-  scanned = scan;
 }
 
 template <class G>
@@ -287,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void yk_radiance_paths(RadArgs a) {
     if (in_path) {
       // the domain rule before every hit (include/ykgpu.h): no discriminant is NaN or infinite, so
       // math::sqrt's loop ends (ykd::nsqrt bounds it besides)
-      if (!ykcast::in_domain(o, d, a.t_min, INFINITY, a.extent)) {
+      if (!ykquery::in_domain(o, d, a.t_min, INFINITY, a.q.extent)) {
         ended = true;
         unwind = false;
         endfl = YK_RAD_OUT_OF_DOMAIN;
@@ -295,11 +179,12 @@ __global__ __launch_bounds__(kThreads) void yk_radiance_paths(RadArgs a) {
         if (segments == 0)  // mt19937::discard(skip), with the ordinary draw
           for (uint32_t k = 0; k < skip; ++k) (void)ykd::rng_next(g);
         ++segments;
-        double T;
-        int hid;
-        bool scanned;
-        closest_hit(a, o, d, stk, T, hid, scanned);
-        if (scanned) ++scans;
+        // world.hit(r, t_min, +inf)
+        const ykquery::Hit h = ykquery::closest_hit<kThreads>(a.q, stk, true, o, d, a.t_min, INFINITY,
+                                                              (a.flags & YK_RADIANCE_LINEAR_SCAN) != 0, false);
+        const double T = h.t;
+        const int hid = h.id;
+        if (h.scanned) ++scans;
         if (hid < 0) {
           // sky (raytracer.hpp:35-36): t = (normalized(dir).y + 1)/2, lerp white -> (.5,.7,1)
           const v3 un = ykd::normalized(d);
@@ -310,13 +195,10 @@ __global__ __launch_bounds__(kThreads) void yk_radiance_paths(RadArgs a) {
           ended = true;
           endfl = YK_RAD_SKY;
         } else {
-          const SphereGeo sg = a.geo[hid];
-          const SphereMat m = a.mat[hid];
-          // hit record (sphere.hpp:41-45, hittable.hpp:23-27)
-          const v3 p = ykd::add(o, ykd::mul(d, T));
-          const v3 outward = ykd::divs(ykd::sub(p, v3{sg.cx, sg.cy, sg.cz}), m.radius);
-          const bool front = ykd::dot(d, outward) < 0;
-          const v3 nrm = front ? outward : ykd::neg(outward);
+          const SphereMat m = a.q.mat[hid];
+          const ykquery::HitRecord rec = ykquery::hit_record(o, d, T, a.q.geo[hid], m.radius);
+          const v3 p = rec.p, nrm = rec.nrm;
+          const bool front = rec.front;
           if (segments == 1) {
             t_first = T;
             id_first = (uint32_t)hid;
@@ -391,7 +273,7 @@ __global__ __launch_bounds__(kThreads) void yk_radiance_paths(RadArgs a) {
         st2 = (st2 >> 16) | (st3 << 16);
         st3 = (st3 >> 16) | (nstk > kIdRegs ? ((uint32_t)id_spill[nstk - kIdRegs - 1] << 16) : 0u);
         --nstk;
-        const SphereMat m = a.mat[id];
+        const SphereMat m = a.q.mat[id];
         L_r = m.ar * L_r;
         L_g = m.ag * L_g;
         L_b = m.ab * L_b;
@@ -417,12 +299,12 @@ __global__ __launch_bounds__(kThreads) void yk_radiance_paths(RadArgs a) {
   if (a.counters) {
     unsigned long long* const cnt =
         a.counters + (size_t)((blockIdx.x * (kThreads / 64u) + tid / 64u) % kRadStripes) * kRadCounters;
-    const uint32_t s_rays = ykcast::wave_sum(c_rays), s_ood = ykcast::wave_sum(c_ood), s_fb = ykcast::wave_sum(c_fb);
+    const uint32_t s_rays = ykquery::wave_sum(c_rays), s_ood = ykquery::wave_sum(c_ood), s_fb = ykquery::wave_sum(c_fb);
     uint32_t s_seg = 0, s_words = 0, s_scan = 0;
     if (count) {
-      s_seg = ykcast::wave_sum(c_seg);
-      s_words = ykcast::wave_sum(c_words);
-      s_scan = ykcast::wave_sum(c_scan);
+      s_seg = ykquery::wave_sum(c_seg);
+      s_words = ykquery::wave_sum(c_words);
+      s_scan = ykquery::wave_sum(c_scan);
     }
     if (lane == 0) {
       if (s_rays) atomicAdd(cnt + 0, (unsigned long long)s_rays);
@@ -443,14 +325,12 @@ inline PathKernel path_kernel(uint32_t rng) {
 // the grid and the scratch of a query: a persistent grid of the blocks the device holds at once
 // (fewer when max_depth would take the attenuation ids past kIdBudget)
 struct Plan {
-  uint32_t grid = 0, stack_cap = 0, id_stride = 0;
+  uint32_t grid = 0, id_stride = 0;
   size_t lds = 0;
 };
 
 int make_plan(ykgpu_context* ctx, const yk_radiance_params* p, Plan& pl) {
-  const DevTree& t = ctx->t64;
-  pl.stack_cap = ykcast::query_stack_cap(t);
-  pl.lds = ykcast::query_stack_lds(pl.stack_cap, kThreads);
+  pl.lds = ykquery::query_stack_lds(ykquery::query_stack_cap(ctx->t64), kThreads);
   int occ = 0;
   YK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)path_kernel(p->rng), (int)kThreads, pl.lds));
   if (occ < 1) return fail(YK_ERR_DEVICE, "radiance: the path kernel does not fit a compute unit");
@@ -490,7 +370,6 @@ int ensure(ykgpu_context* ctx, const yk_radiance_params* p, const Plan& pl) {
 // (mt19937), written by yk_radiance_starts or by the gather's starts kernel (yk_gather.hpp)
 hipError_t enqueue_paths(const ykgpu_context* ctx, const yk_radiance_params* p, const Plan& pl, const void* rays,
                          void* out, uint32_t n, unsigned long long* counters, hipStream_t st) {
-  const DevTree& t = ctx->t64;
   if (hipError_t e = hipMemsetAsync(ctx->d_rad_claim, 0, sizeof(uint32_t), st)) return e;
   RadArgs a{};
   a.rays = (const double*)rays;
@@ -501,21 +380,11 @@ hipError_t enqueue_paths(const ykgpu_context* ctx, const yk_radiance_params* p, 
   a.max_depth = p->max_depth;
   a.claim_tail = pl.grid * (kThreads / 64u) * kClaim * 2u;
   a.t_min = p->t_min;
-  a.nodes = (const char*)t.nodes;
-  a.leaf_geo = (const SphereGeo*)t.leaf_geo;
-  a.leaf_ids = t.leaf_ids;
-  a.geo = ctx->d_geo;
-  a.mat = ctx->d_mat;
   a.claim = ctx->d_rad_claim;
   a.mt_scratch = ctx->d_rad_mt;
   a.id_scratch = ctx->d_rad_ids;
   a.counters = counters;
-  a.extent = ctx->cast_extent;
-  a.origin_bound = t.origin_bound;
-  a.root = t.root;
-  a.node_bytes = t.n_nodes * (uint32_t)sizeof(DevNode);
-  a.nspheres = ctx->nspheres;
-  a.stack_cap = pl.stack_cap;
+  a.q = ykquery::query_tree(ctx);
   a.id_stride = pl.id_stride;
   hipLaunchKernelGGL(path_kernel(p->rng), dim3(pl.grid), dim3(kThreads), pl.lds, st, a);
   return hipGetLastError();
@@ -538,16 +407,8 @@ hipError_t enqueue(const ykgpu_context* ctx, const yk_radiance_params* p, const 
 // the staging of the synchronous query and of a gather's sample slots (yk_gather.hpp): `need` rays
 // and as many records, grown after the context's queries in flight
 int ensure_staging(ykgpu_context* ctx, size_t need) {
-  if (need <= ctx->rad_cap) return YK_OK;
-  YK_HIP(hipEventSynchronize(ctx->rad_ev));
-  (void)hipFree(ctx->d_rad_rays);
-  (void)hipFree(ctx->d_rad_out);
-  ctx->d_rad_rays = ctx->d_rad_out = nullptr;
-  ctx->rad_cap = 0;
-  YK_HIP(hipMalloc(&ctx->d_rad_rays, need * sizeof(yk_path_ray)));
-  YK_HIP(hipMalloc(&ctx->d_rad_out, need * sizeof(yk_radiance)));
-  ctx->rad_cap = need;
-  return YK_OK;
+  return ykquery::ensure_pair(ctx->d_rad_rays, ctx->d_rad_out, ctx->rad_cap, need, sizeof(yk_path_ray),
+                              sizeof(yk_radiance), ctx->rad_ev);
 }
 
 int check_call(const ykgpu_context* ctx, const yk_radiance_params* p, const void* rays, uint64_t n, const void* out) {
@@ -603,10 +464,8 @@ int ykgpu_radiance_rays(ykgpu_context* ctx, const yk_radiance_params* params, co
     kernel_ms += ms;
     starts_ms += ms0;
   }
-  unsigned long long stripes[kRadStripes][kRadCounters] = {}, c[kRadCounters] = {};
-  if (e == hipSuccess) e = hipMemcpy(stripes, ctx->d_rad_counters, sizeof(stripes), hipMemcpyDeviceToHost);
-  for (const auto& sc : stripes)
-    for (int k = 0; k < kRadCounters; ++k) c[k] += sc[k];
+  unsigned long long c[kRadCounters] = {};
+  if (e == hipSuccess) e = ykquery::read_stripes(ctx->d_rad_counters, kRadStripes, kRadCounters, c);
   for (hipEvent_t v : ev)
     if (v) (void)hipEventDestroy(v);
   if (e != hipSuccess)
