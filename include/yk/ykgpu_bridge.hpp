@@ -255,6 +255,8 @@ class any_film {
   virtual std::vector<double> features_sampled(uint32_t n_samples) = 0;
   virtual std::vector<uint8_t> denoise_guided_sampled(const yk_denoise_params& dp, const yk_feature_params& fp,
                                                       uint32_t n_samples) = 0;
+  virtual yk_matte_stats mattes(uint32_t n_samples) = 0;
+  virtual std::vector<uint8_t> matte_coverage(const std::vector<uint32_t>& ids, yk_matte_coverage_stats* stats) = 0;
   virtual yk_film_stats error_stats(double threshold2) = 0;
   virtual void save(const std::string& path, uint64_t scene_hash) = 0;
   virtual void load(const std::string& path, uint64_t scene_hash) = 0;
@@ -283,6 +285,8 @@ struct film_api {
   static constexpr auto denoise_guided = &ykgpu_film_denoise_guided;
   static constexpr auto features_sampled = &ykgpu_film_features_sampled;
   static constexpr auto denoise_guided_sampled = &ykgpu_film_denoise_guided_sampled;
+  static constexpr auto mattes = &ykgpu_film_mattes;
+  static constexpr auto matte_coverage = &ykgpu_film_matte_coverage;
 };
 struct group_film_api {
   using handle = ykgpu_group_film;
@@ -305,6 +309,8 @@ struct group_film_api {
   static constexpr auto denoise_guided = &ykgpu_group_film_denoise_guided;
   static constexpr auto features_sampled = &ykgpu_group_film_features_sampled;
   static constexpr auto denoise_guided_sampled = &ykgpu_group_film_denoise_guided_sampled;
+  static constexpr auto mattes = &ykgpu_group_film_mattes;
+  static constexpr auto matte_coverage = &ykgpu_group_film_matte_coverage;
 };
 }  // namespace detail
 
@@ -396,6 +402,18 @@ class basic_film : public any_film {
     std::vector<uint8_t> img(pixels() * 3);
     ck(Api::denoise_guided_sampled(f_, &dp, &fp, n_samples, nullptr, img.data(), nullptr), "denoise_guided_sampled");
     return img;
+  }
+  // the id-coverage table of include/ykgpu.h "film mattes" (n_samples 0: the film's own counts; the
+  // table stays in the film), and from it the grey coverage of a set of ids, one byte per pixel
+  yk_matte_stats mattes(uint32_t n_samples) override {
+    yk_matte_stats st{};
+    ck(Api::mattes(f_, n_samples, nullptr, &st), "mattes");
+    return st;
+  }
+  std::vector<uint8_t> matte_coverage(const std::vector<uint32_t>& ids, yk_matte_coverage_stats* stats) override {
+    std::vector<uint8_t> grey(pixels());
+    ck(Api::matte_coverage(f_, ids.data(), (uint32_t)ids.size(), nullptr, grey.data(), stats), "matte_coverage");
+    return grey;
   }
   yk_film_stats error_stats(double threshold2) override {
     yk_film_stats st;

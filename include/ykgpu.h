@@ -723,6 +723,78 @@ int ykgpu_group_film_denoise_guided_sampled(ykgpu_group_film* film, const yk_den
                                             const yk_feature_params* feat, uint32_t n_samples, double* mean_host,
                                             uint8_t* rgb_host, yk_group_denoise_stats* stats);
 
+/* ---- film mattes: per-pixel sphere-id coverage from the film's own samples -----------------
+ * (Added under ABI 11 like the film: nothing that existed changed size or meaning.  DESIGN.md 6.10.)
+ *
+ * Which spheres are in a pixel and how much of each, antialiased and defocused exactly as the
+ * film's colour is (the idea behind Cryptomatte).  For pixel (x, y) of the film's tile let
+ * n_p = n_samples if n_samples > 0, else the pixel's own count in the film (ykgpu_film_counts').
+ * For s = 0 .. n_p-1 in order:
+ *   ray       what yk_camera_sample_ray(camera, the film's params, y, x, s) returns, exactly as in
+ *             "sampled film features": in double whatever the film's precision, with the film's
+ *             seed mode, key and engine.
+ *   hit       "ray queries" below, closest mode, t_min = params.t_min, t_max = +inf; a ray outside
+ *             that section's domain rule is a miss and does no arithmetic.
+ *   table     8 slots, empty at first, miss = other = 0:
+ *               a miss:                                              miss += 1
+ *               a hit on sphere k, and k holds a slot:               that slot's count += 1
+ *               a hit on k, no slot holds k, fewer than 8 in use:    a new slot (k, 1)
+ *               otherwise:                                           other += 1
+ *             so the slots hold the first 8 distinct ids in sample order (the rule depends on the
+ *             order by design).
+ *   result    the slots sorted by count descending, equal counts by id ascending; unused slots
+ *             are (0xFFFFFFFF, 0).
+ * The counts are integers: the table is reproducible bit for bit (tests/mattes_ref.py).
+ *
+ * ykgpu_film_mattes: n_samples is 0 (own counts) or 1 .. samples_per_pixel (the sampled features'
+ * cap of 256 does not apply).  The film owns ONE table, allocated at first use and freed with the
+ * film; a repeat call with the same n_samples > 0 reuses it (ms = 0, the counts those of the pass
+ * that made it), n_samples = 0 always recomputes.  table_host (may be NULL) receives row_count *
+ * tile width records in pixel order.  Works on any tile, strided ones included, and changes
+ * nothing of the film's sums, counts or feature planes.
+ * ykgpu_film_matte_coverage works on the table the film holds now, without tracing: ids are
+ * sphere indices and/or YK_MATTE_SKY, duplicates count once.  Per pixel sel = the sum of the
+ * counts of the selected slots, plus miss if the sky is selected;
+ *   cov = n == 0 ? 0.0 : (double)sel / (double)n      (one IEEE division)
+ *   grey = trunc(clamp(cov, 0, 0.999) * 256)
+ * Either output may be NULL, not both.  A pixel with other > 0 is a lower bound.
+ * The group calls return the single film's bytes in whole-tile pixel order; of the stats a group
+ * reports the largest entry's ms and the sums of the entries' counts.
+ * Errors, with nothing written:
+ *   YK_ERR_INVALID      mattes: n_samples > the film's target; the context's scene was set after
+ *                       the film was created.  coverage: the film holds no table; n_ids == 0; ids
+ *                       NULL; an id at or above the sphere count that is not YK_MATTE_SKY; both
+ *                       outputs NULL */
+typedef struct yk_matte_pixel { /* 80 bytes */
+  uint32_t id[8], count[8];
+  uint32_t n, miss, other, used; /* count[0..7] + miss + other == n; used = slots in use */
+} yk_matte_pixel;
+enum { YK_MATTE_SKY = 0xFFFFFFFFu };
+
+typedef struct yk_matte_stats { /* 40 bytes */
+  double ms;                /* device time of the pass; 0 when the cached table was reused */
+  uint64_t samples;         /* the sum of n over the pixels */
+  uint64_t hits;            /* of those, samples whose ray hit a sphere */
+  uint64_t other_samples;   /* ... and hits that found the 8 slots taken by other ids */
+  uint32_t overflow_pixels; /* pixels with other > 0 */
+  uint32_t redo_pixels;     /* pixels finished by the whole-engine redo */
+} yk_matte_stats;
+
+typedef struct yk_matte_coverage_stats { /* 32 bytes */
+  double ms;                 /* device time of the coverage kernel */
+  uint64_t pixels_selected;  /* pixels with sel > 0 */
+  uint64_t pixels_uncertain; /* pixels with other > 0 */
+  uint64_t samples_selected; /* the sum of sel */
+} yk_matte_coverage_stats;
+
+int ykgpu_film_mattes(ykgpu_film* film, uint32_t n_samples, yk_matte_pixel* table_host, yk_matte_stats* stats);
+int ykgpu_film_matte_coverage(ykgpu_film* film, const uint32_t* ids, uint32_t n_ids, double* cov_host,
+                              uint8_t* grey_host, yk_matte_coverage_stats* stats);
+int ykgpu_group_film_mattes(ykgpu_group_film* film, uint32_t n_samples, yk_matte_pixel* table_host,
+                            yk_matte_stats* stats);
+int ykgpu_group_film_matte_coverage(ykgpu_group_film* film, const uint32_t* ids, uint32_t n_ids, double* cov_host,
+                                    uint8_t* grey_host, yk_matte_coverage_stats* stats);
+
 /* ---- ray queries (ABI 11) -------------------------------------------------
  * The reference's public world.hit(r, t_min, t_max) (hittable.hpp:32-34, hittable_list.hpp:32-58,
  * sphere.hpp:25-48) for batches of arbitrary rays against the scene of the last ykgpu_set_scene:

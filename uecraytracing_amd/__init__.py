@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 from . import records
-from .records import CastStats, Hit, Ray, PathRay, GatherParams, GatherStats, RadianceParams, RadianceStats, Camera, DenoiseParams, DenoiseStats, FeatureParams, FilmPass, GroupDenoiseStats, GuidedStats, FilmStats, SampledFeaturesStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
+from .records import CastStats, Hit, Ray, PathRay, GatherParams, GatherStats, RadianceParams, RadianceStats, Camera, DenoiseParams, DenoiseStats, FeatureParams, FilmPass, GroupDenoiseStats, GuidedStats, FilmStats, MatteCoverageStats, MattePixel, MatteStats, SampledFeaturesStats, RenderParams, RenderStats, Sphere, make_params, sphere_array
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(PKG_DIR, "lib")
@@ -45,6 +45,7 @@ EXPORTS = (
     "ykgpu_group_film_denoise_guided",
     "yk_guided_sampled_defaults", "ykgpu_film_features_sampled", "ykgpu_film_denoise_guided_sampled",
     "ykgpu_group_film_features_sampled", "ykgpu_group_film_denoise_guided_sampled",
+    "ykgpu_film_mattes", "ykgpu_film_matte_coverage", "ykgpu_group_film_mattes", "ykgpu_group_film_matte_coverage",
     "ykgpu_cast_rays", "ykgpu_cast_rays_async", "ykgpu_cast_get_stats",
     "ykgpu_radiance_rays", "ykgpu_radiance_rays_async", "ykgpu_radiance_get_stats", "yk_camera_sample_ray",
     "yk_camera_sample_rays",
@@ -142,6 +143,9 @@ def load_library():
                                         c.c_int),
         "ykgpu_film_denoise_guided_sampled": ([c.c_void_p, P(DenoiseParams), P(FeatureParams), c.c_uint32, c.c_void_p,
                                                c.c_void_p, P(GuidedStats)], c.c_int),
+        "ykgpu_film_mattes": ([c.c_void_p, c.c_uint32, c.c_void_p, P(MatteStats)], c.c_int),
+        "ykgpu_film_matte_coverage": ([c.c_void_p, c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, P(MatteCoverageStats)],
+                                      c.c_int),
         "ykgpu_cast_rays": ([c.c_void_p, c.c_void_p, c.c_uint64, c.c_uint32, c.c_void_p], c.c_int),
         "ykgpu_cast_rays_async": ([c.c_void_p, c.c_void_p, c.c_uint64, c.c_uint32, c.c_void_p, c.c_void_p], c.c_int),
         "ykgpu_cast_get_stats": ([c.c_void_p, P(CastStats)], c.c_int),
@@ -163,7 +167,7 @@ def load_library():
     # filters report yk_group_denoise_stats
     for name in ("create", "destroy", "params", "accumulate", "accumulate_adaptive", "resolve", "read", "write",
                  "counts", "write_counts", "error", "features", "denoise", "denoise_guided", "features_sampled",
-                 "denoise_guided_sampled"):
+                 "denoise_guided_sampled", "mattes", "matte_coverage"):
         args, res = sig["ykgpu_film_" + name]
         if name.startswith("denoise"):
             args = args[:-1] + [P(GroupDenoiseStats)]
@@ -565,6 +569,32 @@ class Film:
                 rgb.ctypes.data if want_rgb else None, ctypes.byref(st)))
         return mean, rgb, st.as_dict()
 
+    def mattes(self, n_samples: int = 0):
+        """(table records.MATTE_DTYPE[row_count, tile width], stats dict): the id-coverage table of
+        include/ykgpu.h "film mattes": per pixel, the spheres the first hits of its samples landed
+        on and how many samples each got.  n_samples 0: every pixel's own count in the film; else the
+        first n_samples samples (computed once per (film, n_samples): ms is 0 when the film's table
+        was reused)."""
+        table = np.zeros(self._shape, records.MATTE_DTYPE)
+        st = MatteStats()
+        with _feature_lazy_words(self._lib):
+            _check(self._fn("mattes")(self._f, n_samples, table.ctypes.data, ctypes.byref(st)))
+        return table, st.as_dict()
+
+    def matte_coverage(self, ids, want_cov: bool = True, want_grey: bool = True):
+        """(cov float64[row_count, tile width] | None, grey uint8[row_count, tile width] | None, stats
+        dict): the share of each pixel's samples whose first hit is one of `ids` (sphere indices
+        and/or records.MATTE_SKY), from the table the last mattes() call left in the film; grey is
+        trunc(clamp(cov, 0, 0.999) * 256).  A lower bound where the pixel's `other` is not 0."""
+        k = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        cov = np.empty(self._shape, np.float64) if want_cov else None
+        grey = np.empty(self._shape, np.uint8) if want_grey else None
+        st = MatteCoverageStats()
+        _check(self._fn("matte_coverage")(self._f, k.ctypes.data if k.size else None, k.size,
+                                          cov.ctypes.data if want_cov else None, grey.ctypes.data if want_grey else None,
+                                          ctypes.byref(st)))
+        return cov, grey, st.as_dict()
+
     def render_until(self, threshold: float, chunk: int) -> dict:
         """Accumulates `chunk` samples at a time until no pixel's standard error exceeds
         `threshold` (e2 <= threshold**2 everywhere) or the target is reached; returns the stats
@@ -911,5 +941,5 @@ def render_devices(devices, spheres, camera: Camera, params: RenderParams) -> np
     return out
 
 
-__all__ = ["Renderer", "Film", "GroupFilm", "GroupDenoiseStats", "Ray", "Hit", "CastStats", "PathRay", "RadianceParams", "RadianceStats", "camera_sample_rays", "GatherParams", "GatherStats", "gather_points", "gather_sample_rays", "FilmPass", "DenoiseParams", "DenoiseStats", "denoise_defaults", "FeatureParams", "GuidedStats", "guided_defaults", "SampledFeaturesStats", "guided_sampled_defaults", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
+__all__ = ["Renderer", "Film", "GroupFilm", "GroupDenoiseStats", "Ray", "Hit", "CastStats", "PathRay", "RadianceParams", "RadianceStats", "camera_sample_rays", "GatherParams", "GatherStats", "gather_points", "gather_sample_rays", "FilmPass", "DenoiseParams", "DenoiseStats", "denoise_defaults", "FeatureParams", "GuidedStats", "guided_defaults", "SampledFeaturesStats", "guided_sampled_defaults", "MattePixel", "MatteStats", "MatteCoverageStats", "scene_hash", "save_film", "load_film", "save_film_counts", "load_film_counts", "Group", "render_devices", "YkError", "build_scene", "write_scene", "read_scene", "SCENE_DIR", "reference_camera", "device_count",
            "make_params", "load_library", "records", "EXPORTS", "LIB_PATH", "CLI_PATH"]

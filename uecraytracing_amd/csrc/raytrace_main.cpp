@@ -117,6 +117,14 @@ const char* kHelp =
     "      --aov arg             also write the feature means F as arg.albedo.png, arg.normal.png\n"
     "                            and arg.depth.png: trunc(clamp(x, 0, 0.999) * 256) of F0..F2, of\n"
     "                            0.5 * F + 0.5 for F3..F5, and of F6 / (1 + F6) (grey: r = g = b)\n"
+    "      --matte arg           arg = a comma list of sphere ids and/or 'sky': after the render, the\n"
+    "                            antialiased coverage of those ids, from the first hits of each\n"
+    "                            pixel's own samples (lens and jitter included), written to\n"
+    "                            --matte-out as grey trunc(clamp(cov, 0, 0.999) * 256); prints\n"
+    "                            'matte: pixels <n> uncertain <n> samples <n> of <n>'\n"
+    "      --matte-out arg       the matte's PNG file (needs --matte, and --matte needs it)\n"
+    "      --matte-samples arg   the matte from the first arg samples of every pixel, at most --spp,\n"
+    "                            instead of the samples each pixel got (default: 0, those)\n"
     "      --pick arg            arg = X,Y: cast the pixel-centre pinhole ray of image pixel (X, Y)\n"
     "                            (column, row from the top) at the render's t_min, print\n"
     "                            'pick X Y: id <n> t <t> p (<x>, <y>, <z>) normal (<x>, <y>, <z>)\n"
@@ -165,6 +173,11 @@ struct args {
   uint32_t feature_samples = 0;  // --feature-samples: != 0, the sampled feature pass at that n
   yk_feature_params fp{};
   std::string aov;
+  // --matte IDS --matte-out FILE [--matte-samples N]: the ids' coverage after the render
+  std::vector<uint32_t> matte_ids;
+  std::string matte_out;
+  bool have_matte = false, have_matte_out = false, have_matte_samples = false;
+  uint32_t matte_samples = 0;
   // --pick X,Y: one ray query instead of a render
   bool have_pick = false;
   uint32_t pick_x = 0, pick_y = 0;
@@ -174,7 +187,7 @@ struct args {
   // --gather X,Y: one gather query at the pixel's first hit instead of a render
   bool have_gather = false;
   uint32_t gather_x = 0, gather_y = 0;
-  bool film() const { return denoise || !aov.empty() || adaptive || have_progressive || have_until || have_stop_after || !checkpoint.empty(); }
+  bool film() const { return denoise || !aov.empty() || have_matte || adaptive || have_progressive || have_until || have_stop_after || !checkpoint.empty(); }
 };
 
 uint32_t to_u32(const std::string& opt, const std::string& v) {
@@ -272,6 +285,23 @@ args parse(int argc, char** argv) {
         a.aov = value(i, n, inl);
         if (a.aov.empty()) throw option_error{"Option 'aov' needs a file name prefix"};
       }
+      else if (n == "matte") {
+        const std::string v = value(i, n, inl);
+        for (size_t p = 0; p <= v.size();) {
+          const size_t q = v.find(',', p);
+          const std::string id = v.substr(p, q == std::string::npos ? std::string::npos : q - p);
+          a.matte_ids.push_back(id == "sky" ? (uint32_t)YK_MATTE_SKY : to_u32(n, id));
+          if (q == std::string::npos) break;
+          p = q + 1;
+        }
+        a.have_matte = true;
+      }
+      else if (n == "matte-out") {
+        a.matte_out = value(i, n, inl);
+        a.have_matte_out = true;
+        if (a.matte_out.empty()) throw option_error{"Option 'matte-out' needs a file name"};
+      }
+      else if (n == "matte-samples") { a.matte_samples = to_u32(n, value(i, n, inl)); a.have_matte_samples = true; }
       else if (n == "pick") {
         const std::string v = value(i, n, inl);
         const size_t c = v.find(',');
@@ -332,6 +362,11 @@ args parse(int argc, char** argv) {
   if (a.have_gather && !a.have_seed0) throw option_error{"Option 'gather' needs --seed0 (the samples it draws)"};
   if (a.have_gather && a.precision != "fp64") throw option_error{"Option 'gather' is fp64 only"};
   if (a.have_gather && !a.spp) throw option_error{"Option 'gather' needs --spp of at least 1"};
+  if (a.have_matte != a.have_matte_out) throw option_error{"Options 'matte' and 'matte-out' need each other"};
+  if (a.have_matte_samples && !a.have_matte) throw option_error{"Option 'matte-samples' needs --matte"};
+  if (a.matte_samples > a.spp) throw option_error{"Option 'matte-samples' must be at most --spp"};
+  if (a.have_matte && (a.have_pick || a.have_probe || a.have_gather))
+    throw option_error{"Option 'matte' needs a render: not with --pick, --probe or --gather"};
   if (a.have_denoise_params && !a.denoise) throw option_error{"The denoise parameters need --denoise"};
   if (a.have_feature_grid && !a.denoise_features && a.aov.empty())
     throw option_error{"Option 'feature-grid' needs --denoise-features or --aov"};
@@ -629,6 +664,19 @@ int main(int argc, char* argv[]) {
           const std::string path = a.aov + "." + name + ".png";
           if (!ykpng::write_rgb(path.c_str(), W, H, img->data())) throw ykgpu::error(YK_ERR_INVALID, "cannot write " + path);
         }
+      }
+      if (a.have_matte) {
+        // the ids' coverage (include/ykgpu.h "film mattes") from the samples each pixel got, or from
+        // every pixel's first --matte-samples; grey as the depth image is: r = g = b
+        const yk_matte_stats ms = film.mattes(a.matte_samples);
+        yk_matte_coverage_stats cs{};
+        const std::vector<uint8_t> grey = film.matte_coverage(a.matte_ids, &cs);
+        std::vector<uint8_t> rgb((size_t)W * H * 3);
+        for (size_t px = 0; px < (size_t)W * H; ++px) rgb[px * 3] = rgb[px * 3 + 1] = rgb[px * 3 + 2] = grey[px];
+        if (!ykpng::write_rgb(a.matte_out.c_str(), W, H, rgb.data()))
+          throw ykgpu::error(YK_ERR_INVALID, "cannot write " + a.matte_out);
+        std::cout << "matte: pixels " << cs.pixels_selected << " uncertain " << cs.pixels_uncertain << " samples "
+                  << cs.samples_selected << " of " << ms.samples << std::endl;
       }
     }
     if (verbose) {

@@ -7,6 +7,8 @@
 //
 // Part of the unit yk_features.hip, which includes this file once at its end (the list of units is
 // fixed, tests/test_build_knobs.py).  Everything but the C-ABI entry points lives in namespace ykfs.
+// The per-sample loop is written once (sampled_block, sampled_redo) and takes a sink: the feature
+// folds here, the id table of the film mattes in yk_mattes.hpp, included at this file's end.
 // Two kernels on the context's stream, beside the render and not inside it:
 //   yk_film_features_sampled<Gen>  one lane per pixel, a wave an 8 x 8 pixel block, the pixel's n
 //                                  samples one after the other (the fold order is the definition's).
@@ -24,6 +26,7 @@
 #define YK_FEATURES_SAMPLED_HPP
 
 #include <atomic>
+#include <cstring>
 #include <string>
 #include <type_traits>
 
@@ -52,6 +55,11 @@ struct SfArgs {
   double* out;               // kYkFeatPlanes planes of npix doubles
   uint32_t* redo;            // [0]: pixels listed, [1, 1 + npix): the list, then kRedoEngines engines
   unsigned long long* hits;  // samples that hit a sphere
+  // the film mattes' (yk_mattes.hpp): the table, the pixels' own sample counts in pixel order (null:
+  // n for every pixel) and the counters of samples past the slots and of pixels that have some
+  yk_matte_pixel* table;
+  const uint32_t* counts;
+  unsigned long long* tally;
   double t_min;
   uint64_t seed_key;
   uint32_t seed0, seed_mode, spp, n;
@@ -137,8 +145,26 @@ __device__ __forceinline__ void walk(uint32_t (&x)[kWalk]) {
   if constexpr (std::is_same<Gen, ykd::MtLane>::value) ykd::mt_walk397xn<(int)kWalk>(x);
 }
 
-template <class Gen>
-__global__ __launch_bounds__(kThreads) void yk_film_features_sampled(SfArgs a) {
+// The feature pass's sink of the per-sample loop below: the folds s and q of the seven channels
+struct FeatureSink {
+  double s[kYkFeatChannels], q[kYkFeatChannels];
+  __device__ __forceinline__ void begin() {}
+  __device__ __forceinline__ void init() {
+#pragma unroll
+    for (uint32_t c = 0; c < kYkFeatChannels; ++c) s[c] = q[c] = 0.0;
+  }
+  __device__ __forceinline__ uint32_t samples(const SfArgs& a, uint32_t) { return a.n; }
+  __device__ __forceinline__ void add(const SfArgs& a, v3 o, v3 d, int hid, double t) { fold_sample(a, o, d, hid, t, s, q); }
+  __device__ __forceinline__ void store(const SfArgs& a, size_t at) { store_planes(a, at, s, q); }
+  __device__ __forceinline__ void tally(const SfArgs&, bool) {}
+};
+
+// The per-sample loop of the passes that read a film's own samples, written once: the sampled
+// feature pass and the film mattes (yk_mattes.hpp) differ in the Sink that receives each sample's
+// hit.  A sink says how many samples its pixel has (samples), takes them in order (add), writes the
+// pixel (store) and adds what it counted to the pass's counters, once per wave (tally).
+template <class Gen, class Sink>
+__device__ __forceinline__ void sampled_block(const SfArgs& a) {
   extern __shared__ __attribute__((aligned(16))) int32_t fs_stack[];  // [entry][lane]: (stack_cap + 3) x kThreads
   const uint32_t tid = threadIdx.x;
   const uint32_t wave = tid / 64u, lane = tid & 63u;
@@ -146,21 +172,23 @@ __global__ __launch_bounds__(kThreads) void yk_film_features_sampled(SfArgs a) {
   const uint32_t py = blockIdx.y * kBlockH + lane / kWave;
   const bool mine = py < a.rows && px < a.wt;
   uint32_t nh = 0;
+  Sink sink;
+  sink.begin();
   if (mine) {
     const uint32_t x = image_x(a, px), y = image_y(a, py);
     const bool lens = a.cam.lens_radius > 0;
-    double s[kYkFeatChannels], q[kYkFeatChannels];
-#pragma unroll
-    for (uint32_t c = 0; c < kYkFeatChannels; ++c) s[c] = q[c] = 0.0;
+    const uint32_t at = py * a.wt + px;
+    sink.init();
+    const uint32_t n = sink.samples(a, at);
     bool listed = false;
-    for (uint32_t k = 0; k < a.n && !listed; k += kWalk) {
+    for (uint32_t k = 0; k < n && !listed; k += kWalk) {
       uint32_t seed[kWalk], x397[kWalk];
 #pragma unroll
       for (uint32_t j = 0; j < kWalk; ++j)  // (past n: walked, not used)
         x397[j] = seed[j] = ykd::sample_seed(a.seed_mode, a.seed_key, a.seed0, y, x, a.W, a.spp, k + j);
       walk<Gen>(x397);
 #pragma unroll 1
-      for (uint32_t j = 0; j < kWalk && k + j < a.n; ++j) {
+      for (uint32_t j = 0; j < kWalk && k + j < n; ++j) {
         const uint32_t sj = j == 0 ? seed[0] : j == 1 ? seed[1] : j == 2 ? seed[2] : seed[3];
         const uint32_t xj = j == 0 ? x397[0] : j == 1 ? x397[1] : j == 2 ? x397[2] : x397[3];
         Gen g;
@@ -186,37 +214,41 @@ __global__ __launch_bounds__(kThreads) void yk_film_features_sampled(SfArgs a) {
         if (ykquery::in_domain(o, d, a.t_min, INFINITY, a.q.extent))
           h = ykquery::closest_hit<kThreads>(a.q, fs_stack + tid, true, o, d, a.t_min, INFINITY, a.scan_only != 0, false);
         nh += h.id >= 0 ? 1u : 0u;
-        fold_sample(a, o, d, h.id, h.t, s, q);
+        sink.add(a, o, d, h.id, h.t);
       }
     }
     if (listed) {
-      // the lens loop outran the lazy cursors: yk_film_features_redo runs the pixel's samples
+      // the lens loop outran the lazy cursors: the pass's redo kernel runs the pixel's samples
       nh = 0;
-      a.redo[1 + atomicAdd(a.redo, 1u)] = py * a.wt + px;
+      a.redo[1 + atomicAdd(a.redo, 1u)] = at;
     } else {
-      store_planes(a, (size_t)py * a.wt + px, s, q);
+      sink.store(a, at);
     }
   }
   // one atomic per wave (every lane of the block is here)
   const uint32_t wh = ykquery::wave_sum(nh);
   if (lane == 0 && wh) atomicAdd(a.hits, (unsigned long long)wh);
+  sink.tally(a, lane == 0);
 }
 
-__global__ __launch_bounds__(kRedoEngines) void yk_film_features_redo(SfArgs a) {
+// ... and its whole-engine form for the listed pixels: one block of kRedoEngines threads
+template <class Sink>
+__device__ __forceinline__ void sampled_redo(const SfArgs& a) {
   const uint32_t count = a.redo[0] < a.npix ? a.redo[0] : a.npix;
   ykd::MtFull g;
   g.st = a.redo + 1 + a.npix + (size_t)threadIdx.x * ykd::kMtN;
   uint32_t nh = 0;
   const bool lens = a.cam.lens_radius > 0;
+  Sink sink;
+  sink.begin();
   for (uint32_t e = threadIdx.x; e < count; e += kRedoEngines) {
     const uint32_t at = a.redo[1 + e];
     if (at >= a.npix) continue;  // (never)
     const uint32_t py = at / a.wt, px = at - py * a.wt;
     const uint32_t x = image_x(a, px), y = image_y(a, py);
-    double s[kYkFeatChannels], q[kYkFeatChannels];
-#pragma unroll
-    for (uint32_t c = 0; c < kYkFeatChannels; ++c) s[c] = q[c] = 0.0;
-    for (uint32_t k = 0; k < a.n; ++k) {
+    sink.init();
+    const uint32_t n = sink.samples(a, at);
+    for (uint32_t k = 0; k < n; ++k) {
       ykd::mt_full_seed(g, ykd::sample_seed(a.seed_mode, a.seed_key, a.seed0, y, x, a.W, a.spp, k));
       const double uc = ykd::canonical(g);
       const double vc = ykd::canonical(g);
@@ -233,13 +265,21 @@ __global__ __launch_bounds__(kRedoEngines) void yk_film_features_redo(SfArgs a) 
       if (ykquery::in_domain(o, d, a.t_min, INFINITY, a.q.extent))
         ykquery::scan_hit(a.q, o, d, ykd::len2(d), a.t_min, INFINITY, false, h);
       nh += h.id >= 0 ? 1u : 0u;
-      fold_sample(a, o, d, h.id, h.t, s, q);
+      sink.add(a, o, d, h.id, h.t);
     }
-    store_planes(a, at, s, q);
+    sink.store(a, at);
   }
   const uint32_t wh = ykquery::wave_sum(nh);
   if (threadIdx.x == 0 && wh) atomicAdd(a.hits, (unsigned long long)wh);
+  sink.tally(a, threadIdx.x == 0);
 }
+
+template <class Gen>
+__global__ __launch_bounds__(kThreads) void yk_film_features_sampled(SfArgs a) {
+  sampled_block<Gen, FeatureSink>(a);
+}
+
+__global__ __launch_bounds__(kRedoEngines) void yk_film_features_redo(SfArgs a) { sampled_redo<FeatureSink>(a); }
 
 // the lazy-word limit of the next passes; 0: ykd::kLazyDraws (yk_features_sampled_lazy_words below)
 std::atomic<uint32_t> g_lazy_words{0};
@@ -258,14 +298,80 @@ int check(const ykgpu_film* film, uint32_t n_samples) {
   return YK_OK;
 }
 
+// the arguments a pass over the film's tile shares (its outputs and work memory apart)
+SfArgs film_args(const ykgpu_film* film, uint32_t n) {
+  const ykgpu_context* ctx = film->ctx;
+  const yk_render_params& p = film->p;
+  SfArgs a{};
+  a.cam = ctx->cam;
+  a.q = ykquery::query_tree(ctx);
+  a.t_min = p.t_min;
+  a.seed_key = p.seed_key;
+  a.seed0 = p.seed0;
+  a.seed_mode = p.seed_mode == YK_SEED_RANDOM_DEVICE ? 1u : 0u;
+  a.spp = p.samples_per_pixel;
+  a.n = n;
+  const uint32_t lw = g_lazy_words.load();
+  a.lazy_words = lw ? std::max(kLazyMin, std::min(lw, ykd::kLazyDraws)) : ykd::kLazyDraws;
+  a.scan_only = (p.flags & YK_FLAG_LINEAR_SCAN) ? 1u : 0u;
+  a.W = p.image_width;
+  a.H = p.image_height;
+  a.rows = p.row_count;
+  a.wt = tile_width(&p);
+  a.npix = (uint32_t)((size_t)a.rows * a.wt);
+  const TileCols cols = film_cols(film);
+  a.row_begin = p.row_begin;
+  a.row_stride = p.row_stride;
+  a.row_band = p.row_band_log2;
+  a.col_begin = cols.begin;
+  a.col_stride = cols.stride;
+  a.col_band = cols.band;
+  return a;
+}
+
+// what a pass leaves in the head of its work memory: the counters and the redo list's count
+struct PassBack {
+  unsigned long long hits, tally[2], pad;
+  uint32_t listed;
+};
+constexpr size_t kPassHead = offsetof(PassBack, listed);
+
+// One pass on the context's stream, synchronous: the pass's own memory (the counters, the redo list
+// and its engines), `launch(a, blocks, lds, stream, xor128)` between two events, the counters back.
+template <class Launch>
+int run_pass(const ykgpu_film* film, SfArgs& a, const char* who, PassBack* back, float* ms, Launch launch) {
+  const hipStream_t stream = film->ctx->stream;  // (film calls are synchronous on it)
+  const size_t redo_words = 1 + (size_t)a.npix + (size_t)kRedoEngines * ykd::kMtN;
+  char* d_work = nullptr;
+  YK_HIP(hipMalloc(&d_work, kPassHead + redo_words * sizeof(uint32_t)));
+  a.hits = (unsigned long long*)d_work;
+  a.tally = (unsigned long long*)(d_work + offsetof(PassBack, tally));
+  a.redo = (uint32_t*)(d_work + kPassHead);
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  hipError_t e = hipEventCreate(&ev[0]);
+  if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+  if (e == hipSuccess) e = hipMemsetAsync(d_work, 0, kPassHead + sizeof(uint32_t), stream);  // the counters and the list's count
+  if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
+  if (e == hipSuccess) {
+    const dim3 blocks((a.wt + kBlockW - 1) / kBlockW, (a.rows + kBlockH - 1) / kBlockH);
+    e = launch(a, blocks, ykquery::query_stack_lds(a.q.stack_cap, kThreads), stream, film->p.rng == YK_RNG_XOR128);
+  }
+  if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(back, d_work, kPassHead + sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e == hipSuccess) e = hipEventElapsedTime(ms, ev[0], ev[1]);
+  for (hipEvent_t v : ev)
+    if (v) (void)hipEventDestroy(v);
+  (void)hipFree(d_work);
+  if (e != hipSuccess)
+    return fail(e == hipErrorOutOfMemory ? YK_ERR_NOMEM : YK_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+  return YK_OK;
+}
+
 int ensure(ykgpu_film* film, uint32_t n, const double** planes, yk_sampled_features_stats* stats) {
   if (int rc = check(film, n)) return rc;
-  const ykgpu_context* ctx = film->ctx;
   YK_HIP(hipSetDevice(film->device));
-  const yk_render_params& p = film->p;
-  const uint32_t rows = p.row_count, wt = tile_width(&p);
-  const hipStream_t stream = ctx->stream;  // (film calls are synchronous on it)
-  const size_t npix = (size_t)rows * wt;
+  const size_t npix = (size_t)film->p.row_count * tile_width(&film->p);
   if (!film->d_features) {  // (a film's tile never changes size)
     film->feature_grid = film->feature_n = 0;
     YK_HIP(hipMalloc(&film->d_features, kYkFeatPlanes * npix * sizeof(double)));
@@ -280,73 +386,24 @@ int ensure(ykgpu_film* film, uint32_t n, const double** planes, yk_sampled_featu
     return YK_OK;
   }
   film->feature_grid = film->feature_n = 0;  // (until the pass is whole)
-
-  // the pass's own memory: the hit counter, the redo list and its engines
-  const size_t redo_words = 1 + npix + (size_t)kRedoEngines * ykd::kMtN;
-  char* d_work = nullptr;
-  YK_HIP(hipMalloc(&d_work, 16 + redo_words * sizeof(uint32_t)));
-  SfArgs a{};
-  a.cam = ctx->cam;
-  a.q = ykquery::query_tree(ctx);
+  SfArgs a = film_args(film, n);
   a.out = (double*)film->d_features;
-  a.hits = (unsigned long long*)d_work;
-  a.redo = (uint32_t*)(d_work + 16);
-  a.t_min = p.t_min;
-  a.seed_key = p.seed_key;
-  a.seed0 = p.seed0;
-  a.seed_mode = p.seed_mode == YK_SEED_RANDOM_DEVICE ? 1u : 0u;
-  a.spp = p.samples_per_pixel;
-  a.n = n;
-  const uint32_t lw = g_lazy_words.load();
-  a.lazy_words = lw ? std::max(kLazyMin, std::min(lw, ykd::kLazyDraws)) : ykd::kLazyDraws;
-  a.scan_only = (p.flags & YK_FLAG_LINEAR_SCAN) ? 1u : 0u;
-  a.W = p.image_width;
-  a.H = p.image_height;
-  a.rows = rows;
-  a.wt = wt;
-  a.npix = (uint32_t)npix;
-  const TileCols cols = film_cols(film);
-  a.row_begin = p.row_begin;
-  a.row_stride = p.row_stride;
-  a.row_band = p.row_band_log2;
-  a.col_begin = cols.begin;
-  a.col_stride = cols.stride;
-  a.col_band = cols.band;
-  const bool x128 = p.rng == YK_RNG_XOR128;
-
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  hipError_t e = hipEventCreate(&ev[0]);
-  if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-  if (e == hipSuccess) e = hipMemsetAsync(d_work, 0, 16 + sizeof(uint32_t), stream);  // the counter and the list's count
-  if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
-  if (e == hipSuccess) {
-    const dim3 blocks((wt + kBlockW - 1) / kBlockW, (rows + kBlockH - 1) / kBlockH);
-    const size_t lds = ykquery::query_stack_lds(a.q.stack_cap, kThreads);
-    if (x128)
-      hipLaunchKernelGGL(yk_film_features_sampled<ykd::X128Lane>, blocks, dim3(kThreads), lds, stream, a);
-    else
-      hipLaunchKernelGGL(yk_film_features_sampled<ykd::MtLane>, blocks, dim3(kThreads), lds, stream, a);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess && !x128) {  // (almost always finds its list empty)
-    hipLaunchKernelGGL(yk_film_features_redo, dim3(1), dim3(kRedoEngines), 0, stream, a);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
-  struct {
-    unsigned long long hits, pad;
-    uint32_t listed;
-  } back{};
-  if (e == hipSuccess) e = hipMemcpyAsync(&back, d_work, 16 + sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  PassBack back{};
   float ms = 0;
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-  for (hipEvent_t v : ev)
-    if (v) (void)hipEventDestroy(v);
-  (void)hipFree(d_work);
-  if (e != hipSuccess)
-    return fail(e == hipErrorOutOfMemory ? YK_ERR_NOMEM : YK_ERR_DEVICE,
-                std::string("ykgpu_film_features_sampled: ") + hipGetErrorString(e));
+  if (int rc = run_pass(film, a, "ykgpu_film_features_sampled", &back, &ms,
+                        [](const SfArgs& a, dim3 blocks, size_t lds, hipStream_t stream, bool x128) {
+                          if (x128)
+                            hipLaunchKernelGGL(yk_film_features_sampled<ykd::X128Lane>, blocks, dim3(kThreads), lds, stream, a);
+                          else
+                            hipLaunchKernelGGL(yk_film_features_sampled<ykd::MtLane>, blocks, dim3(kThreads), lds, stream, a);
+                          hipError_t e = hipGetLastError();
+                          if (e == hipSuccess && !x128) {  // (almost always finds its list empty)
+                            hipLaunchKernelGGL(yk_film_features_redo, dim3(1), dim3(kRedoEngines), 0, stream, a);
+                            e = hipGetLastError();
+                          }
+                          return e;
+                        }))
+    return rc;
   film->feature_n = n;
   film->feature_hits = back.hits;
   film->feature_redo = back.listed;
@@ -388,5 +445,8 @@ int ykgpu_film_features_sampled(ykgpu_film* film, uint32_t n_samples, double* me
 }
 
 }  // extern "C"
+
+// ... and the film mattes (ykgpu_film_mattes ...), the same loop with a table of ids as its sink
+#include "yk_mattes.hpp"
 
 #endif

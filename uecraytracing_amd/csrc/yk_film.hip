@@ -301,7 +301,7 @@ int ykgpu_film_destroy(ykgpu_film* film) {
   (void)hipFree(film->d_order);
   (void)hipFree(film->d_result);
   for (void* q : {(void*)film->d_count, (void*)film->d_take, (void*)film->d_blocks, (void*)film->d_gorder,
-                  (void*)film->d_gmap, (void*)film->d_hist, film->d_denoise, film->d_features})
+                  (void*)film->d_gmap, (void*)film->d_hist, film->d_denoise, film->d_features, film->d_mattes})
     (void)hipFree(q);
   delete film;
   return YK_OK;

@@ -629,6 +629,66 @@ int ykgpu_group_film_denoise_guided_sampled(ykgpu_group_film* f, const yk_denois
   return gf_denoise(f, dp, &fp, n_samples, mean_host, rgb_host, stats);
 }
 
+// The film mattes (include/ykgpu.h "film mattes"): a pixel's table depends on that pixel alone, so
+// each entry runs the single film's call on the rows it was dealt and no halo is needed.
+int ykgpu_group_film_mattes(ykgpu_group_film* f, uint32_t n_samples, yk_matte_pixel* table_host, yk_matte_stats* stats) {
+  if (int rc = gf_ready(f)) return rc;
+  if (n_samples > f->p.samples_per_pixel) return fail(YK_ERR_INVALID, "mattes: n_samples is larger than the film's target");
+  if (int rc = gf_stale(f)) return rc;
+  std::vector<std::vector<yk_matte_pixel>> t(f->k);
+  yk_matte_stats sum{};
+  for (uint32_t e = 0; e < f->k; ++e) {
+    if (!f->film[e]) continue;
+    if (table_host) t[e].resize(gf_sub_npix(f, e));
+    yk_matte_stats st{};
+    if (const int rc = ykgpu_film_mattes(f->film[e], n_samples, table_host ? t[e].data() : nullptr, &st))
+      return entry_fail(e, rc);
+    sum.ms = std::max(sum.ms, st.ms);
+    sum.samples += st.samples;
+    sum.hits += st.hits;
+    sum.other_samples += st.other_samples;
+    sum.overflow_pixels += st.overflow_pixels;
+    sum.redo_pixels += st.redo_pixels;
+  }
+  // (the caller's array is written only once every entry's pass is in)
+  for (uint32_t e = 0; table_host && e < f->k; ++e)
+    if (f->film[e]) gf_scatter(f, e, t[e].data(), table_host, 1);
+  if (stats) *stats = sum;
+  return YK_OK;
+}
+
+int ykgpu_group_film_matte_coverage(ykgpu_group_film* f, const uint32_t* ids, uint32_t n_ids, double* cov_host,
+                                    uint8_t* grey_host, yk_matte_coverage_stats* stats) {
+  if (int rc = gf_ready(f)) return rc;
+  std::vector<std::vector<double>> c(f->k);
+  std::vector<std::vector<uint8_t>> g(f->k);
+  yk_matte_coverage_stats sum{};
+  bool any = false;
+  for (uint32_t e = 0; e < f->k; ++e) {
+    if (!f->film[e]) continue;
+    any = true;
+    if (cov_host) c[e].resize(gf_sub_npix(f, e));
+    if (grey_host) g[e].resize(gf_sub_npix(f, e));
+    yk_matte_coverage_stats st{};
+    // (the entries hold tables of the same call and the same scene: a refusal is the first entry's)
+    if (const int rc = ykgpu_film_matte_coverage(f->film[e], ids, n_ids, cov_host ? c[e].data() : nullptr,
+                                                 grey_host ? g[e].data() : nullptr, &st))
+      return entry_fail(e, rc);
+    sum.ms = std::max(sum.ms, st.ms);
+    sum.pixels_selected += st.pixels_selected;
+    sum.pixels_uncertain += st.pixels_uncertain;
+    sum.samples_selected += st.samples_selected;
+  }
+  if (!any) return fail(YK_ERR_INVALID, "matte coverage: the film holds no matte table");
+  for (uint32_t e = 0; e < f->k; ++e) {
+    if (!f->film[e]) continue;
+    if (cov_host) gf_scatter(f, e, c[e].data(), cov_host, 1);
+    if (grey_host) gf_scatter(f, e, g[e].data(), grey_host, 1);
+  }
+  if (stats) *stats = sum;
+  return YK_OK;
+}
+
 }  // extern "C"
 
 #endif

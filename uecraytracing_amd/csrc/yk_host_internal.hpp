@@ -240,6 +240,13 @@ struct ykgpu_film {
   uint32_t feature_grid = 0;
   uint32_t feature_n = 0, feature_redo = 0;
   uint64_t feature_hits = 0;
+  // ykgpu_film_mattes' table (yk_mattes.hpp), npix yk_matte_pixel records allocated at the first
+  // pass, and its key: whether it holds a whole pass, that pass's n_samples (0: the film's own
+  // counts, never reused) and its counts
+  void* d_mattes = nullptr;
+  bool matte_valid = false;
+  uint32_t matte_n = 0;
+  yk_matte_stats matte_stats{};
   bool uniform() const { return hist.size() <= 1; }
 };
 

@@ -250,6 +250,50 @@ class SampledFeaturesStats(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved"}
 
 
+MATTE_SKY = 0xFFFFFFFF  # YK_MATTE_SKY: the sky among a matte's ids, and the id of an unused slot
+MATTE_SLOTS = 8
+
+
+class MattePixel(ctypes.Structure):
+    """yk_matte_pixel (include/ykgpu.h "film mattes"): the id-coverage table of one pixel."""
+    _fields_ = [
+        ("id", ctypes.c_uint32 * 8),  # by count descending, equal counts by id ascending; unused: MATTE_SKY
+        ("count", ctypes.c_uint32 * 8),
+        ("n", ctypes.c_uint32),  # sum(count) + miss + other
+        ("miss", ctypes.c_uint32),
+        ("other", ctypes.c_uint32),  # hits that found the 8 slots taken by other ids
+        ("used", ctypes.c_uint32),
+    ]
+
+
+class MatteStats(ctypes.Structure):
+    """yk_matte_stats (include/ykgpu.h "film mattes"): the pass that made a film's matte table."""
+    _fields_ = [
+        ("ms", ctypes.c_double),  # 0 when the cached table was reused
+        ("samples", ctypes.c_uint64),  # the sum of n over the pixels
+        ("hits", ctypes.c_uint64),
+        ("other_samples", ctypes.c_uint64),
+        ("overflow_pixels", ctypes.c_uint32),  # pixels with other > 0
+        ("redo_pixels", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class MatteCoverageStats(ctypes.Structure):
+    """yk_matte_coverage_stats (include/ykgpu.h "film mattes"): one coverage call."""
+    _fields_ = [
+        ("ms", ctypes.c_double),
+        ("pixels_selected", ctypes.c_uint64),  # pixels with sel > 0
+        ("pixels_uncertain", ctypes.c_uint64),  # pixels with other > 0
+        ("samples_selected", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 HIT_HIT = 1  # yk_hit.flags (include/ykgpu.h "ray queries")
 HIT_FRONT_FACE = 2
 HIT_OUT_OF_DOMAIN = 4
@@ -305,6 +349,8 @@ def _np_dtype(names, formats, itemsize):
 # numpy views of yk_ray and yk_hit: arrays of these dtypes are the C records, byte for byte
 RAY_DTYPE = _np_dtype(["origin", "direction", "t_min", "t_max"], [("<f8", 3), ("<f8", 3), "<f8", "<f8"], 64)
 HIT_DTYPE = _np_dtype(["p", "normal", "t", "id", "flags"], [("<f8", 3), ("<f8", 3), "<f8", "<u4", "<u4"], 64)
+# ... and of yk_matte_pixel
+MATTE_DTYPE = _np_dtype(["id", "count", "n", "miss", "other", "used"], [("<u4", 8), ("<u4", 8), "<u4", "<u4", "<u4", "<u4"], 80)
 
 RAD_SKY = 1  # yk_radiance.flags (include/ykgpu.h "radiance queries"): how the path ended
 RAD_ABSORBED = 2
