@@ -181,7 +181,8 @@ typedef struct yk_render_stats {
   double resolve_ms;       /* ordered per-pixel sum + to_color3b kernel, summed           */
   double total_ms;         /* whole call: host wall clock for ykgpu_render / _sums (with
                               the copies), first to last event for ykgpu_render_async   */
-  double warmup_ms;        /* MT seed-walk kernel, summed over its launches             */
+  double warmup_ms;        /* MT seed-walk kernel, summed over its launches (the fill call
+                              of the seed table stores each walk's x_397 beside it)      */
   uint64_t samples;        /* primary samples rendered                                 */
   uint64_t segments;       /* ray_color calls that ran a closest-hit (flag COUNT_WORK) */
   uint64_t sphere_tests;   /* ray-sphere discriminant tests (flag COUNT_WORK)          */
@@ -213,7 +214,9 @@ typedef struct yk_render_stats {
   uint64_t device_bytes;   /* device memory the context holds after the call: scene, BVHs,
                               processing order, start-record (xor128: colour) ring, running
                               sums, MT and attenuation scratch, the warm-ups' lens-retry rings,
-                              output buffers.
+                              the seed table (4 bytes per sample of the last FP64 / mt19937 /
+                              counter-seed tile, kept across ykgpu_set_scene), output buffers
+                              (DESIGN.md §6).
                               Buffers follow the calls: grown when a call needs more, given
                               back when it needs less than half                            */
   uint64_t call_bytes;     /* device memory THIS call needed (the same items sized to it):

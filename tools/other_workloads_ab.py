@@ -1,6 +1,7 @@
 """The workloads beside the contract bench for one library (YKGPU_LIB_OVERRIDE names another build of
 libykgpu.so, else the tree's): the median of 40 ykgpu_set_scene calls, the first frame call, synced
-calls of the frame, rank 0's tile of the 8-way split, the FP32 frame, config 5 and a frame without sky
+calls of the frame, frames with a new seed0 each (the seed table's fill calls), the xor128 frame, rank 0's
+tile of the 8-way split, the FP32 frame, config 5 and a frame without sky
 (tests/golden/room5.yks at 64 spp).  One JSON line; run it once per library, alternating, to compare
 two builds (profiles/r18_sky_blocks/other_workloads_ab.json).  AB_ONLY=tile stops after the tile.
 usage: python tools/other_workloads_ab.py <tag>"""
@@ -15,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402,F401
 import uecraytracing_amd as yk  # noqa: E402
-from uecraytracing_amd.records import PRECISION_FP32, make_params  # noqa: E402
+from uecraytracing_amd.records import PRECISION_FP32, RNG_XOR128, make_params  # noqa: E402
 from uecraytracing_amd.tiles import rank_tile  # noqa: E402
 
 out = {"tag": sys.argv[1], "lib": os.environ.get("YKGPU_LIB_OVERRIDE", "tree")}
@@ -62,6 +63,17 @@ with yk.Renderer(0) as ren:
     st = ren.stats()
     out["frame_stats"] = {k: st[k] for k in ("launches", "launch_spp", "device_bytes", "call_bytes", "kernel_ms",
                                              "warmup_ms", "resolve_ms", "render_busy_ms")}
+    # seed0 changed on every call: with the seed table every such call fills it and none reads it
+    ts = []
+    for k in range(6):
+        t = time.perf_counter()
+        ren.render(make_params(W, H, 512, 50, 1000 + k))
+        ts.append(round((time.perf_counter() - t) * 1e3, 3))
+    out["new_seed0_every_call_ms"] = ts
+    ren.render(p)
+    # the walk-free engine on the same build: the floor under any saving on the walks
+    out["xor128_frame"] = timed(ren, make_params(W, H, 512, 50, 404, rng=RNG_XOR128), 3)
+    ren.render(p)
     out["tile_rank0_of_8"] = timed(ren, make_params(W, H, 512, 50, 404, **rank_tile(0, 8, H, W, "rows")), 6)
     if os.environ.get("AB_ONLY") == "tile":
         print(json.dumps(out), flush=True)

@@ -177,6 +177,11 @@ def load_library():
         f.argtypes, f.restype = args, res
     # (a test hook, not part of the C-ABI: _feature_lazy_words below)
     lib.yk_features_sampled_lazy_words.argtypes, lib.yk_features_sampled_lazy_words.restype = [c.c_uint32], None
+    # (likewise: the seed table's switches, Renderer.__init__, and its test hook; a library of an
+    # earlier revision, which the A/B tools load through YKGPU_LIB_OVERRIDE, has neither)
+    if hasattr(lib, "yk_seed_table_configure"):
+        lib.yk_seed_table_configure.argtypes, lib.yk_seed_table_configure.restype = [c.c_void_p, c.c_int, c.c_uint64], None
+        lib.yk_seed_table_test.argtypes, lib.yk_seed_table_test.restype = [c.c_uint32], None
     if lib.ykgpu_abi_version() != ABI_VERSION:
         raise YkError("ABI version mismatch")
     _lib = lib
@@ -656,6 +661,16 @@ class Renderer:
         self._films = weakref.WeakSet()
         _check(self._lib.ykgpu_context_create(device, ctypes.byref(self._ctx)))
         self.device = device
+        # the seed table's switches, read here, when the context is created: the
+        # package reads them, not the library, and hands them over through a hook outside the C-ABI
+        off = os.environ.get("YKGPU_SEED_TABLE", "").strip() == "0"
+        cap = os.environ.get("YKGPU_SEED_TABLE_MAX_MB")
+        if (off or cap is not None) and hasattr(self._lib, "yk_seed_table_configure"):
+            try:
+                max_bytes = min(max(int(cap), 0), 1 << 40) << 20 if cap is not None else 8 << 30
+            except ValueError:
+                max_bytes = 8 << 30  # (the library's default cap)
+            self._lib.yk_seed_table_configure(self._ctx, 0 if off else 1, max_bytes)
 
     def film(self, params: RenderParams) -> Film:
         """A progressive film of the tile `params` names (include/ykgpu.h)."""

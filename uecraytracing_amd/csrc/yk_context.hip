@@ -53,6 +53,7 @@ uint64_t device_bytes(const ykgpu_context* ctx) {
   b += (uint64_t)ctx->order_slots * sizeof(uint32_t) + (uint64_t)ctx->counter_cap * sizeof(uint32_t);
   b += kCounters * sizeof(unsigned long long);
   b += sky_bytes(ctx);
+  b += ctx->seed_tab_words * sizeof(uint32_t);
   if (ctx->d_mt) b += 2ull * ctx->scratch_lanes * ykd::kMtN * sizeof(uint32_t);
   if (ctx->d_ids) b += 2ull * ctx->id_lanes * ctx->id_stride * sizeof(uint16_t);
   b += ctx->rgb_cap + ctx->sums_cap * sizeof(double);
@@ -330,6 +331,9 @@ int ykgpu_context_destroy(ykgpu_context* ctx) {
   (void)hipFree(ctx->d_sky_mt);
   (void)hipFree(ctx->d_sky_off);
   if (ctx->sky_ev) (void)hipEventDestroy(ctx->sky_ev);
+  (void)hipFree(ctx->d_seed_tab);
+  if (ctx->seed_ev_aux) (void)hipEventDestroy(ctx->seed_ev_aux);
+  if (ctx->seed_ev_red) (void)hipEventDestroy(ctx->seed_ev_red);
   ctx->t64.release();
   ctx->t32.release();
   (void)hipFree(ctx->d_mt);

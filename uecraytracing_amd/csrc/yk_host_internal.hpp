@@ -19,6 +19,7 @@
 
 #include "../../include/ykgpu.h"
 #include "yk_render_device.hpp"
+#include "yk_seed_table.hpp"
 
 namespace ykhost {
 // sets ykgpu_last_error's message for the calling thread and returns code
@@ -106,6 +107,30 @@ struct ykgpu_context {
   size_t sky_cap = 0;             // slots of the whole order the five buffers were allocated for
   uint32_t sky_path_slots = 0, sky_slots = 0, sky_full_slots = 0;
   hipEvent_t sky_ev = nullptr;  // the end of a call of sky blocks only (no reduce follows its samples)
+  // Seed table (yk_seed_table.hpp): x_397 of every sample of the production
+  // instance's tile, one word each, for one key (what the counter seeds depend on).  Only calls
+  // with sky slots use it: the first such call of a key walks, the second consecutive one fills the
+  // table beside its walks, in the calls after it the sky kernel reads it instead of walking.
+  // seed_tab_filled: every launch of the fill call was enqueued.  seed_tab_part: the
+  // sky split (sky_key; empty: no sky slots) of the last call that used the table, i.e. which words
+  // the sky kernel touched and which the warm-up; a call under another split makes both streams
+  // wait for both kernels of that call (seed_ev_aux after its last warm-up, seed_ev_red after its
+  // last sky kernel; yk_pipeline.hip seed_table_wait).  Kept across ykgpu_set_scene; freed
+  // when a call's rings need the room, and with the context.  seed_tab_on / seed_tab_max_bytes: the
+  // switches yk_seed_table_configure sets (the Python package's YKGPU_SEED_TABLE=0 and
+  // YKGPU_SEED_TABLE_MAX_MB, read when it creates the context).
+  uint32_t* d_seed_tab = nullptr;
+  uint64_t seed_tab_words = 0;
+  ykseed::Key seed_tab_key{};
+  // the key of the last call that could have used the table: a key is filled by its second
+  // consecutive call, not its first (a caller that changes seed0 every call never pays a fill)
+  ykseed::Key seed_tab_seen_key{};
+  bool seed_tab_seen = false;
+  bool seed_tab_filled = false, seed_ev_set = false;
+  std::vector<uint64_t> seed_tab_part;
+  hipEvent_t seed_ev_aux = nullptr, seed_ev_red = nullptr;
+  bool seed_tab_on = true;
+  uint64_t seed_tab_max_bytes = 8ull << 30;  // (the frame's table is 4.25 GB; config 5's 34 GB is not taken by default)
   hipStream_t stream = nullptr;
   hipStream_t aux = nullptr;  // the MT warm-ups run here, beside the render launches
   hipStream_t red = nullptr;  // the ordered reduces run here, beside the next render launch

@@ -38,6 +38,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <random>
@@ -48,6 +49,7 @@
 #include "yk_film_internal.hpp"
 #include "yk_host_internal.hpp"
 #include "yk_schedule.hpp"
+#include "yk_seed_table.hpp"
 #include "yk_sky.hpp"
 
 namespace {
@@ -78,6 +80,28 @@ struct WarmArgs {
   uint32_t* counter;  // the launch's sample-slot counter: cleared here (the render waits for this kernel)
   uint4* retry;         // yk_mt_warmup_defer: the lens retries, retry_cap records of 48 B per wave
   uint32_t retry_cap, retry_pad;
+};
+
+// The seed table's behaviours, as template instances (DESIGN.md §3 "Seed table"): kTabWalk is the
+// walk alone; kTabFill walks and also stores each x_397 (the second consecutive eligible call
+// of a key: the warm-ups and the sky kernel); kTabRead loads x_397 instead of walking (the sky kernel in the calls
+// after it).  Everything after the walk is the same code.  The warm-ups have no reading instance:
+// one was built and measured, and the render beside it slowed down by more than the walks cost
+// (the frame 141 -> 150 ms; profiles/r23_seed_table/), so they keep walking.  Their
+// fill instance stores every word all the same: a pixel it fills may be a sky pixel under the
+// next camera.
+constexpr int kTabWalk = 0, kTabFill = 1, kTabRead = 2;
+constexpr uint64_t kNoTabIndex = ~0ull;  // (kTabFill) a slot without a pixel stores nothing
+// the table as the kTabFill / kTabRead instances take it, behind the walking instances' own
+// arguments (whose records, and so whose code, stay as they were): T its tile pixels
+// (flip: xor-ed into every word the fill stores; 0 but under the test hook yk_seed_table_test)
+struct SeedTab {
+  uint32_t* tab;
+  uint32_t T, flip;
+};
+struct WarmTabArgs {
+  WarmArgs wa;
+  SeedTab st;
 };
 
 // Thin-lens retries after the walks (yk_mt_warmup_defer): a sample whose first random_in_unit_disk candidate is
@@ -116,8 +140,9 @@ __device__ __forceinline__ uint32_t retry_get(const uint4* r, ykd::MtLane& g, do
 
 // kIlp: the seed walks of kIlp slots interleaved per lane (i, i + stride, ...; the walk is a
 // chain of dependent instructions), their starts then one after the other
-template <bool kLens, bool kF32, bool kDefer, uint32_t kIlp>
-__device__ __forceinline__ void mt_warmup_body(const WarmArgs& wa) {
+template <bool kLens, bool kF32, bool kDefer, uint32_t kIlp, int kTab = kTabWalk>
+__device__ __forceinline__ void mt_warmup_body(const WarmArgs& wa, const SeedTab& st = SeedTab{}) {
+  static_assert(kTab == kTabWalk || (kTab == kTabFill && !kF32), "the FP64 production instance's warm-ups walk or fill");
   constexpr uint32_t kWarmBlock = 256;  // (every warm-up launches 256-thread blocks)
   // (32-bit indices: a launch keeps its slots below 2^31 and the grid below 2^21 threads)
   const uint32_t n = (uint32_t)wa.n;
@@ -131,8 +156,9 @@ __device__ __forceinline__ void mt_warmup_body(const WarmArgs& wa) {
                               wa.retry_cap * 3
              : nullptr;
   uint32_t rcount = 0;
-  // slot i's pixel (xx, y) and seed; an empty slot gets column kPadX (its record is marked)
-  auto slot_seed = [&](uint32_t i, uint32_t& xx, uint32_t& y) -> uint32_t {
+  // slot i's pixel (xx, y) and seed; an empty slot gets column kPadX (its record is marked).  ti
+  // (kTabFill): the slot's word of the seed table; an empty slot stores none
+  auto slot_seed = [&](uint32_t i, uint32_t& xx, uint32_t& y, uint64_t& ti) -> uint32_t {
     const uint32_t sl = fdiv(i, wa.nps_m, wa.nps_sh), pp = i - sl * wa.npix_slots;
     const uint32_t q = wa.order[pp];
     const uint32_t pix = q == kNoPixel ? 0u : q;
@@ -141,6 +167,7 @@ __device__ __forceinline__ void mt_warmup_body(const WarmArgs& wa) {
     y = tile_row_y(wa.row_begin, wa.row_stride, wa.band_log2, tr);
     const uint32_t seed = ykd::sample_seed(wa.seed_mode, wa.seed_key, wa.seed0, y, xx, wa.W, wa.spp, wa.s0 + sl);
     xx = q == kNoPixel ? kPadX : xx;
+    if constexpr (kTab == kTabFill) ti = q == kNoPixel ? kNoTabIndex : ykseed::table_index(wa.s0 + sl, pix, st.T);
     return seed;
   };
   // the start of slot i after its walk: draws, lens, camera ray, record
@@ -220,20 +247,25 @@ __device__ __forceinline__ void mt_warmup_body(const WarmArgs& wa) {
   if constexpr (kIlp > 1) {
     for (uint32_t i = blockIdx.x * kWarmBlock + threadIdx.x; i < n; i += kIlp * stride) {
       uint32_t xx, y, x[kIlp];
+      uint64_t ti = 0, tk = 0;
 #pragma unroll
       for (uint32_t k = kIlp - 1; k > 0; --k) {
         const uint32_t ik = i + k * stride;
-        x[k] = slot_seed(ik < n ? ik : i, xx, y);
+        x[k] = slot_seed(ik < n ? ik : i, xx, y, tk);
       }
-      const uint32_t seed = slot_seed(i, xx, y);
+      const uint32_t seed = slot_seed(i, xx, y, ti);
       x[0] = seed;
       ykd::mt_walk397xn<kIlp>(x);
+      if constexpr (kTab == kTabFill)
+        if (ti != kNoTabIndex) st.tab[ti] = (x[0] ^ st.flip);
       start_slot(i, xx, y, seed, x[0]);
 #pragma unroll
       for (uint32_t k = 1; k < kIlp; ++k) {
         const uint32_t ik = i + k * stride;
         if (ik < n) {
-          const uint32_t sk = slot_seed(ik, xx, y);
+          const uint32_t sk = slot_seed(ik, xx, y, tk);
+          if constexpr (kTab == kTabFill)
+            if (tk != kNoTabIndex) st.tab[tk] = (x[k] ^ st.flip);
           start_slot(ik, xx, y, sk, x[k]);
         }
       }
@@ -241,9 +273,12 @@ __device__ __forceinline__ void mt_warmup_body(const WarmArgs& wa) {
   } else {
     for (uint32_t i = blockIdx.x * kWarmBlock + threadIdx.x; i < n; i += stride) {
       uint32_t xx, y;
-      const uint32_t seed = slot_seed(i, xx, y);
+      uint64_t ti = 0;
+      const uint32_t seed = slot_seed(i, xx, y, ti);
       uint32_t x[1] = {seed};
       ykd::mt_walk397xn<1>(x);
+      if constexpr (kTab == kTabFill)
+        if (ti != kNoTabIndex) st.tab[ti] = (x[0] ^ st.flip);
       start_slot(i, xx, y, seed, x[0]);
     }
   }
@@ -310,6 +345,16 @@ __global__ __launch_bounds__(256) void yk_mt_warmup(WarmArgs wa) {
 // 128-VGPR render waves of a SIMD (the attribute counts gfx950's unified register file: twice)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(YK_DEFER_VGPRS / 2))) void yk_mt_warmup_defer(WarmArgs wa) {
   mt_warmup_body<true, false, true, kWalkIlp>(wa);
+}
+// the FP64 warm-ups of a call that fills the seed table (kTabFill): the same
+// grids, blocks and register budget as the walking instances above
+template <bool kLens, int kTab>
+__global__ __launch_bounds__(256) void yk_mt_warmup_tab(WarmTabArgs ta) {
+  mt_warmup_body<kLens, false, false, 1, kTab>(ta.wa, ta.st);
+}
+template <int kTab>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(YK_DEFER_VGPRS / 2))) void yk_mt_warmup_defer_tab(WarmTabArgs ta) {
+  mt_warmup_body<true, false, true, kWalkIlp, kTab>(ta.wa, ta.st);
 }
 
 // Ordered sum of a launch's sample colours per pixel: pixel_color of source.cpp:137-167 is the
@@ -387,6 +432,10 @@ struct SkyArgs {
   uint32_t* engines;             // [0]: slots listed for yk_sky_redo, [1, 1 + n): the list, then its 64 engines
   unsigned long long* counters;  // [3]: MT fallbacks
 };
+struct SkyTabArgs {
+  SkyArgs sa;
+  SeedTab st;
+};
 // the sky of the camera ray of pixel (xx, y) for the start's draws, added to the pixel's sums
 __device__ __forceinline__ void sky_add(const SkyArgs& sa, uint32_t xx, uint32_t y, double uc, double vc, double px,
                                         double py, double (&a)[3]) {
@@ -407,7 +456,11 @@ constexpr uint32_t kSkyLazyWords = YK_SKY_LAZY_FORCE;
 #else
 constexpr uint32_t kSkyLazyWords = ykd::kLazyDraws;
 #endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(YK_DEFER_VGPRS / 2))) void yk_sky_samples(SkyArgs sa) {
+// kTab: the seed table, as the warm-up's (kTabFill stores the x_397 of the samples it walks, also
+// those of a pixel it leaves to yk_sky_redo; kTabRead loads them)
+template <int kTab>
+__device__ __forceinline__ void sky_samples_body(const SkyArgs& sa, uint32_t* const tab = nullptr, const uint32_t tab_T = 0,
+                                                 const uint32_t flip = 0) {
   const uint32_t p = blockIdx.x * 256u + threadIdx.x;
   if (p >= sa.n) return;
   const uint32_t q = sa.list[p];
@@ -424,7 +477,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(YK_DEFER_VGPRS 
     uint32_t x[kWalkIlp];
 #pragma unroll
     for (uint32_t j = 0; j < kWalkIlp; ++j) x[j] = seed_s0 + k + j;  // (past ks: walked, not used)
-    ykd::mt_walk397xn<kWalkIlp>(x);
+    if constexpr (kTab == kTabRead) {
+#pragma unroll
+      for (uint32_t j = 0; j < kWalkIlp; ++j)
+        if (k + j < sa.ks) x[j] = tab[ykseed::table_index(sa.s0 + k + j, q, tab_T)];
+    } else {
+      ykd::mt_walk397xn<kWalkIlp>(x);
+      if constexpr (kTab == kTabFill) {
+#pragma unroll
+        for (uint32_t j = 0; j < kWalkIlp; ++j)
+          if (k + j < sa.ks) tab[ykseed::table_index(sa.s0 + k + j, q, tab_T)] = (x[j] ^ flip);
+      }
+    }
 #pragma unroll
     for (uint32_t j = 0; j < kWalkIlp; ++j) {
       if (k + j >= sa.ks) break;
@@ -440,6 +504,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(YK_DEFER_VGPRS 
             // (never seen) the lens loop outran the lazy cursors: the pixel keeps its carried sums
             // and yk_sky_redo runs this launch's samples of it from a whole engine
             sa.engines[1 + atomicAdd(sa.engines, 1u)] = p;
+            if constexpr (kTab == kTabFill) {
+              // (the table still gets the launch's other samples of the pixel)
+              for (uint32_t k2 = k + kWalkIlp; k2 < sa.ks; k2 += kWalkIlp) {
+                uint32_t x2[kWalkIlp];
+#pragma unroll
+                for (uint32_t j2 = 0; j2 < kWalkIlp; ++j2) x2[j2] = seed_s0 + k2 + j2;
+                ykd::mt_walk397xn<kWalkIlp>(x2);
+#pragma unroll
+                for (uint32_t j2 = 0; j2 < kWalkIlp; ++j2)
+                  if (k2 + j2 < sa.ks) tab[ykseed::table_index(sa.s0 + k2 + j2, q, tab_T)] = (x2[j2] ^ flip);
+              }
+            }
             return;
           }
           px = ykd::uniform<true>(g, -1, 1);
@@ -456,6 +532,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(YK_DEFER_VGPRS 
     return;
   }
   pixel_store(sa.sums, sa.rgb, q, a, sa.spp);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(YK_DEFER_VGPRS / 2))) void yk_sky_samples(SkyArgs sa) {
+  sky_samples_body<kTabWalk>(sa);
+}
+template <int kTab>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(YK_DEFER_VGPRS / 2))) void yk_sky_samples_tab(SkyTabArgs ta) {
+  sky_samples_body<kTab>(ta.sa, ta.st.tab, ta.st.T, ta.st.flip);
 }
 // The sky slots yk_sky_samples listed (never seen: a lens loop of ~55 rejections): this launch's
 // samples of each from the carried sums, every draw from a whole engine in global memory, seeded
@@ -752,6 +835,29 @@ static bool sky_eligible(const yk_render_params* p, const ykgpu_film* film, cons
   return kTile != 0 && !film && p->precision == YK_PRECISION_FP64 && p->rng == YK_RNG_MT19937 &&
          p->seed_mode == YK_SEED_COUNTER && p->flags == 0 && p->max_depth > 0 && plan.in_lds;
 }
+// Seed table (yk_seed_table.hpp): the same production instance, whatever its scene
+// and camera — FP64, mt19937, counter seeds, no flags, a one-shot call, which always covers the
+// samples [0, spp) of its tile.  FP32, xor128, random-device seeds, the counting, trace and
+// linear-scan instances and every film pass neither read nor write it.
+// (test hook yk_seed_table_test, below: the word xor-ed into what a fill stores)
+static std::atomic<uint32_t> g_seed_tab_flip{0};
+static bool seed_table_eligible(const ykgpu_context* ctx, const yk_render_params* p, const ykgpu_film* film,
+                                uint32_t s_begin, uint32_t s_end) {
+  return ctx->seed_tab_on && !film && p->precision == YK_PRECISION_FP64 && p->rng == YK_RNG_MT19937 &&
+         p->seed_mode == YK_SEED_COUNTER && p->flags == 0 && s_begin == 0 && s_end == p->samples_per_pixel;
+}
+// gives the table back (a call's rings need the room, or its next key has another size); false:
+// there was none
+static bool seed_table_drop(ykgpu_context* ctx) {
+  if (!ctx->d_seed_tab) return false;
+  for (hipStream_t s : {ctx->aux, ctx->red, ctx->ren, ctx->alt, ctx->stream}) (void)hipStreamSynchronize(s);
+  (void)hipFree(ctx->d_seed_tab);
+  ctx->d_seed_tab = nullptr;
+  ctx->seed_tab_words = 0;
+  ctx->seed_tab_filled = false;
+  return true;
+}
+
 // The two orders of the call's tile: ctx->d_sky_path, the processing order over the blocks that can
 // hit something (padded to whole warm-up blocks of 256 slots), and ctx->d_sky_list, the slots of
 // the sky blocks.  A function of the scene, the camera and the geometry: built once per key and
@@ -921,6 +1027,13 @@ struct LaunchPlan {
   size_t welem;  // start records (StartRec, FP32 StartRecF: each sample's whole start)
   uint32_t retry_cap;  // records per wave
   size_t retry_n;
+  // the seed table: kTabWalk (none), kTabFill or kTabRead; tab_part: which of its words the sky
+  // kernel touches (the sky split's key; empty: none); tab_sync: that differs from the last call
+  // that used the table, so the warm-up and the sky stream first wait for that call's kernels
+  int tab_mode = 0;  // (kTabWalk; initialised: launch() reads it after a plan_launch that failed early)
+  bool tab_sync = false;
+  uint32_t tab_T = 0;
+  std::vector<uint64_t> tab_part;
 };
 
 // slots per warm-up wave of an FP64 launch of nl slots
@@ -1048,7 +1161,8 @@ static int plan_launch(ykgpu_context* ctx, const yk_render_params* p, uint32_t s
       if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
         const size_t held = ctx->warm_cap + ctx->col_cap * sizeof(double);
         if (need_warm + need_col + kMemReserve > free_b + held) {
-          shrink();
+          // (the seed table goes before the launches shrink: it is never the cause of a shrink)
+          if (!seed_table_drop(ctx)) shrink();
           continue;
         }
       }
@@ -1057,7 +1171,7 @@ static int plan_launch(ykgpu_context* ctx, const yk_render_params* p, uint32_t s
     if (!rc) rc = grow(ctx->d_col, ctx->col_cap, (size_t)kColRing * nps_ring * K * kColStride, sizeof(double));
     if (rc == YK_ERR_NOMEM && kmax > kfloor) {
       (void)hipGetLastError();  // (the failed hipMalloc's error must not surface at a later launch)
-      shrink();
+      if (!seed_table_drop(ctx)) shrink();
       continue;
     }
     if (rc) return rc;
@@ -1094,6 +1208,59 @@ static int plan_launch(ykgpu_context* ctx, const yk_render_params* p, uint32_t s
     (void)hipGetLastError();
     retry_cap = 0;
     retry_n = 0;
+  }
+  // The seed table, last: the call's rings fit, and the table takes only room the device still has
+  // beyond the reserve the rings leave (a call whose launches were shrunk has none to give).  Only
+  // a call with sky slots takes part: the sky kernel is the table's one reader, so a view without a
+  // sky block (an enclosed room) neither allocates nor fills nor reads, and keeps whatever table
+  // the context holds for a later view (a camera that then shows sky under another key runs a
+  // walking call and then a fill call).  A filled table of the call's key is read; the second
+  // consecutive such call of a key fills — the same buffer when the size is the key's, a new one
+  // otherwise.  Without room the call walks as ever.
+  lp.tab_mode = kTabWalk;
+  lp.tab_sync = false;
+  lp.tab_T = 0;
+  if (culled && seed_table_eligible(ctx, p, film, s_begin, s_end) && !warm_first && !mem_shrinks) {
+    const ykseed::Key key = ykseed::make_key(p->seed0, p->image_width, p->samples_per_pixel, p->row_begin, p->row_count,
+                                             p->row_stride, p->row_band_log2, p->col_begin, p->col_count,
+                                             p->col_stride, p->col_band_log2);
+    const uint64_t words = ykseed::table_words(key);
+    lp.tab_T = ykseed::tile_pixels(key);
+    if (words * sizeof(uint32_t) <= ctx->seed_tab_max_bytes) {
+      if (ctx->d_seed_tab && ctx->seed_tab_filled && ykseed::same_key(ctx->seed_tab_key, key)) {
+        lp.tab_mode = kTabRead;
+      } else if (!(ctx->seed_tab_seen && ykseed::same_key(ctx->seed_tab_seen_key, key))) {
+        // the first call of a key walks as ever: only a key that comes again is worth a fill (a
+        // frame whose every call has a new seed0 measured +1.0% when each one filled, outside the
+        // parent's run-to-run spread; profiles/r23_seed_table/)
+      } else {
+        if (ctx->d_seed_tab && ctx->seed_tab_words != words) seed_table_drop(ctx);
+        if (!ctx->d_seed_tab) {
+          size_t free_b = 0, total_b = 0;
+          if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && words * sizeof(uint32_t) + kMemReserve <= free_b) {
+            if (hipMalloc((void**)&ctx->d_seed_tab, words * sizeof(uint32_t)) == hipSuccess) {
+              ctx->seed_tab_words = words;
+            } else {
+              (void)hipGetLastError();
+              ctx->d_seed_tab = nullptr;
+            }
+          }
+        }
+        if (ctx->d_seed_tab) {
+          if (!ctx->seed_ev_aux) YK_HIP(hipEventCreateWithFlags(&ctx->seed_ev_aux, hipEventDisableTiming));
+          if (!ctx->seed_ev_red) YK_HIP(hipEventCreateWithFlags(&ctx->seed_ev_red, hipEventDisableTiming));
+          ctx->seed_tab_key = key;
+          ctx->seed_tab_filled = false;  // (until every launch of this call has been enqueued)
+          lp.tab_mode = kTabFill;
+        }
+      }
+    }
+    ctx->seed_tab_seen_key = key;
+    ctx->seed_tab_seen = true;
+    if (lp.tab_mode != kTabWalk) {
+      lp.tab_part = ctx->sky_key;
+      lp.tab_sync = lp.tab_part != ctx->seed_tab_part;
+    }
   }
   return YK_OK;
 }
@@ -1265,13 +1432,19 @@ static int fill_args(const ykgpu_context* ctx, const yk_render_params* p, uint8_
 // call writes the caller's image: a call that overlaps the one before it (wait_caller) has not made
 // its streams wait for the caller's yet.
 static int enqueue_sky(ykgpu_context* ctx, hipStream_t s, SkyArgs& sa, uint32_t s0, uint32_t ks, uint32_t s_end,
-                       bool wait_caller) {
+                       bool wait_caller, int tab_mode, uint32_t tab_T) {
   sa.s0 = s0;
   sa.ks = ks;
   sa.first = s0 == 0;
   sa.last = s0 + ks == s_end;
   if (sa.last && wait_caller) YK_HIP(hipStreamWaitEvent(s, ctx->ev0, 0));
-  hipLaunchKernelGGL(yk_sky_samples, dim3((sa.n + 255) / 256), dim3(256), 0, s, sa);
+  const SkyTabArgs ta{sa, SeedTab{ctx->d_seed_tab, tab_T, g_seed_tab_flip.load()}};
+  if (tab_mode == kTabRead)
+    hipLaunchKernelGGL(yk_sky_samples_tab<kTabRead>, dim3((sa.n + 255) / 256), dim3(256), 0, s, ta);
+  else if (tab_mode == kTabFill)
+    hipLaunchKernelGGL(yk_sky_samples_tab<kTabFill>, dim3((sa.n + 255) / 256), dim3(256), 0, s, ta);
+  else
+    hipLaunchKernelGGL(yk_sky_samples, dim3((sa.n + 255) / 256), dim3(256), 0, s, sa);
   YK_HIP(hipGetLastError());
   // (the lens: without one no sample can outrun the lazy cursors, and nothing is ever listed)
   if (sa.lens) {
@@ -1283,7 +1456,34 @@ static int enqueue_sky(ykgpu_context* ctx, hipStream_t s, SkyArgs& sa, uint32_t 
 
 // A call whose every block is a sky block: no path launch, no rings, one yk_sky_samples over the
 // call's samples, behind whatever the context still runs and the caller's stream.
-static int enqueue_sky_only(ykgpu_context* ctx, hipStream_t st, uint32_t s_begin, uint32_t s_end, LaunchArgs& la) {
+// The seed table's ordering: warm-ups run in order on ctx->aux and sky kernels in
+// order on ctx->red, and while the sky split stays what it was each word is touched by one of the
+// two streams only, whatever the calls do with it (fill, read, fill again under a new seed0).  When
+// the split changes (a new scene or camera, another tile) a word stored by one kernel may be read
+// or stored again by the other: such a call (tab_sync) makes both streams wait for both kernels of
+// the last call that used the table.  Every call that uses the table records the two events once
+// its launches are enqueued (seed_table_used).  Stream waits only: nothing here waits on the host,
+// and back-to-back calls of one view overlap exactly as without the table.
+static int seed_table_wait(ykgpu_context* ctx, const LaunchPlan& lp) {
+  if (!lp.tab_sync || !ctx->seed_ev_set) return YK_OK;
+  for (hipStream_t s : {ctx->aux, ctx->red}) {
+    YK_HIP(hipStreamWaitEvent(s, ctx->seed_ev_aux, 0));
+    YK_HIP(hipStreamWaitEvent(s, ctx->seed_ev_red, 0));
+  }
+  return YK_OK;
+}
+static int seed_table_used(ykgpu_context* ctx, const LaunchPlan& lp) {
+  if (lp.tab_mode == kTabWalk) return YK_OK;
+  YK_HIP(hipEventRecord(ctx->seed_ev_aux, ctx->aux));
+  YK_HIP(hipEventRecord(ctx->seed_ev_red, ctx->red));
+  ctx->seed_ev_set = true;
+  ctx->seed_tab_part = lp.tab_part;
+  if (lp.tab_mode == kTabFill) ctx->seed_tab_filled = true;
+  return YK_OK;
+}
+
+static int enqueue_sky_only(ykgpu_context* ctx, hipStream_t st, uint32_t s_begin, uint32_t s_end, const LaunchPlan& lp,
+                            LaunchArgs& la) {
   int rc = YK_OK;
   // (yk_sky_redo adds to d_stats[3], the MT-fallback count, on ctx->red: a later call that clears
   // d_stats from another caller stream, or on ctx->aux when it overlaps this one, is not ordered
@@ -1297,7 +1497,8 @@ static int enqueue_sky_only(ykgpu_context* ctx, hipStream_t st, uint32_t s_begin
   YK_HIP(hipMemsetAsync(ctx->d_stats + 16, 0xff, 2 * sizeof(unsigned long long), st));  // minima
   YK_HIP(hipEventRecord(ctx->ev0, st));
   YK_HIP(hipStreamWaitEvent(ctx->red, ctx->ev0, 0));
-  if ((rc = enqueue_sky(ctx, ctx->red, la.sa, s_begin, s_end - s_begin, s_end, false))) return rc;
+  if ((rc = seed_table_wait(ctx, lp))) return rc;
+  if ((rc = enqueue_sky(ctx, ctx->red, la.sa, s_begin, s_end - s_begin, s_end, false, lp.tab_mode, lp.tab_T))) return rc;
   YK_HIP(hipEventRecord(ctx->sky_ev, ctx->red));
   YK_HIP(hipStreamWaitEvent(st, ctx->sky_ev, 0));
   YK_HIP(hipEventRecord(ctx->ev1, st));
@@ -1408,6 +1609,7 @@ static int enqueue_launches(ykgpu_context* ctx, hipStream_t st, uint32_t s_end, 
       if (after_prev) YK_HIP(hipStreamWaitEvent(s, ctx->lev_prev[6 * (ctx->prev_n - 1) + 5], 0));
     }
   }
+  if ((rc = seed_table_wait(ctx, lp))) return rc;
   while (ctx->gev.size() < 2ull * kDepRing) {
     hipEvent_t e;
     YK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1431,13 +1633,20 @@ static int enqueue_launches(ykgpu_context* ctx, hipStream_t st, uint32_t s_end, 
     const uint32_t wblocks =
         warm_blocks_for(wa.n, (uint64_t)ctx->cus * warm_per_cu(f32), defer ? kWalkIlp : 1u, lp.warm_align);
     YK_HIP(hipEventRecord(ev[0], ctx->aux));
+    const WarmTabArgs ta{wa, SeedTab{ctx->d_seed_tab, lp.tab_T, g_seed_tab_flip.load()}};
     if (!x128) {
       if (f32 && wa.lens)
         hipLaunchKernelGGL((yk_mt_warmup<true, true>), dim3(wblocks), dim3(256), 0, ctx->aux, wa);
       else if (f32)
         hipLaunchKernelGGL((yk_mt_warmup<false, true>), dim3(wblocks), dim3(256), 0, ctx->aux, wa);
+      else if (defer && lp.tab_mode == kTabFill)
+        hipLaunchKernelGGL(yk_mt_warmup_defer_tab<kTabFill>, dim3(wblocks), dim3(256), 0, ctx->aux, ta);
       else if (defer)
         hipLaunchKernelGGL(yk_mt_warmup_defer, dim3(wblocks), dim3(256), 0, ctx->aux, wa);
+      else if (lp.tab_mode == kTabFill && wa.lens)
+        hipLaunchKernelGGL((yk_mt_warmup_tab<true, kTabFill>), dim3(wblocks), dim3(256), 0, ctx->aux, ta);
+      else if (lp.tab_mode == kTabFill)
+        hipLaunchKernelGGL((yk_mt_warmup_tab<false, kTabFill>), dim3(wblocks), dim3(256), 0, ctx->aux, ta);
       else if (wa.lens)
         hipLaunchKernelGGL((yk_mt_warmup<true, false>), dim3(wblocks), dim3(256), 0, ctx->aux, wa);
       else
@@ -1503,7 +1712,7 @@ static int enqueue_launches(ykgpu_context* ctx, hipStream_t st, uint32_t s_end, 
     // warm-ups on ctx->aux, which is busy 97% of a step, they delayed every warm-up after them:
     // bench +1.2%, profiles/r18_sky_blocks/); the last one writes the caller's image, and the
     // call's last reduce, which the caller waits for, follows it
-    if (lp.culled && (rc = enqueue_sky(ctx, ctx->red, la.sa, s0, ks, s_end, ov))) return rc;
+    if (lp.culled && (rc = enqueue_sky(ctx, ctx->red, la.sa, s0, ks, s_end, ov, lp.tab_mode, lp.tab_T))) return rc;
     YK_HIP(hipStreamWaitEvent(ctx->red, ev[3], 0));
     if (ov && !film && ra.last) YK_HIP(hipStreamWaitEvent(ctx->red, ctx->ev0, 0));  // the caller's image
     YK_HIP(hipEventRecord(ev[4], ctx->red));
@@ -1585,11 +1794,51 @@ int launch(ykgpu_context* ctx, const yk_render_params* p, uint8_t* rgb_dev, doub
   int rc = plan_launch(ctx, p, s_begin, s_end, film, lp);
   if (!rc) rc = fill_args(ctx, p, rgb_dev, sums_dev, film, lp, la);
   if (!rc && lp.culled && lp.nps == 0)
-    rc = enqueue_sky_only(ctx, st, s_begin, s_end, la);
+    rc = enqueue_sky_only(ctx, st, s_begin, s_end, lp, la);
   else if (!rc)
     rc = enqueue_launches(ctx, st, s_end, film, lp, la, &launches);
+  if (!rc) rc = seed_table_used(ctx, lp);
+  // A call that failed part-way may have enqueued table kernels under its split.  The two events
+  // are recorded behind whatever it enqueued (best effort: the streams may be what failed) and the
+  // split is set to a value no sky_key has, so the next call that uses the table makes both streams
+  // wait for both events whatever its own split; the host wait ctx->dirty brings comes on top.
+  if (rc && lp.tab_mode != kTabWalk) {
+    if (ctx->seed_ev_aux && ctx->seed_ev_red && hipEventRecord(ctx->seed_ev_aux, ctx->aux) == hipSuccess &&
+        hipEventRecord(ctx->seed_ev_red, ctx->red) == hipSuccess)
+      ctx->seed_ev_set = true;
+    else
+      (void)hipGetLastError();
+    ctx->seed_tab_part = {~0ull};
+  }
   if (!rc) call_stats(ctx, p, sums_dev, film, lp, launches);
   return rc;
 }
 
+// (the hooks below)
+bool seed_table_drop_hook(ykgpu_context* ctx) { return seed_table_drop(ctx); }
+void seed_table_test_hook(uint32_t flip) { g_seed_tab_flip.store(flip); }
+
 }  // namespace ykhost
+
+extern "C" {
+
+// The seed table's switches and its test hook: not part of the C-ABI (include/ykgpu.h does not
+// declare them), like yk_features_sampled_lazy_words.  The library reads no environment variable
+// for the table (tests/test_integration_doc.py pins the two it reads); the Python package reads YKGPU_SEED_TABLE and YKGPU_SEED_TABLE_MAX_MB when it
+// creates a context and hands them over here.
+// on == 0 turns the context's table off (and gives back one it holds); max_bytes caps its size.
+void yk_seed_table_configure(ykgpu_context* ctx, int on, uint64_t max_bytes) {
+  if (!ctx) return;
+  (void)hipSetDevice(ctx->device);
+  ctx->seed_tab_on = on != 0;
+  ctx->seed_tab_max_bytes = max_bytes;
+  if (!on || ctx->seed_tab_words * sizeof(uint32_t) > max_bytes) ykhost::seed_table_drop_hook(ctx);
+}
+// For the tests (tests/test_gpu_seed_table.py), process-wide: flip is xor-ed into every word a fill
+// stores from now on, so that the pixels of a kernel that reads the table come out different from
+// those of one that walks, which proves the read ran.  (A hook and not a build with a -D, as the
+// other fallback tests have: tests/test_build_knobs.py pins the Makefile's list of test variants.
+// A caller that sets it gets wrong images from reading calls; nothing in the product calls it.)
+void yk_seed_table_test(uint32_t flip) { ykhost::seed_table_test_hook(flip); }
+
+}  // extern "C"
